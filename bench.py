@@ -18,8 +18,16 @@ are double-buffered: the gather of scan k runs on RCCL's stream under the kernel
 reused only after its gather has finished; all K kernels and all K gathers complete inside the timed region;
 --no-overlap serialises them).
 
-Adds to the JSON line: "roofline" (algorithmic bytes / HIP-event kernel time vs 8 TB/s) and,
-at N=1, "cpu_baseline" (the CPU oracle timed on the host cores on the same scan).
+Adds to the JSON line: "roofline" (algorithmic bytes / HIP-event kernel time of the timed steps vs 8 TB/s).
+
+A plain run sets up, warms up, times the K steps and prints the line, nothing else.  --full adds, at N=1, every
+measurement that takes runs of its own: the other accumulate mode and the general kernel instance (roofline.ordered /
+.double_sum, .general_instance), the out-of-cache and depth-4 legs, scale_n1, end_to_end, the gp / lv / bgkl legs and
+"cpu_baseline" (the CPU oracle timed on the host cores on the same scan); the --no-* options leave parts of it out.
+
+--dump-outputs DIR writes what the last timed step computed (the leaf alpha / beta / state arrays the hot path
+updates; a map's leaves in --mode shard) as DIR/<name>.npy in float32, for comparing two builds output for output:
+the inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import ctypes as C
@@ -77,7 +85,19 @@ def main():
                     help="add roofline.kernel_function_variants: the headline launch with cheaper / no kernel-function evaluation (VERDICT r05 #2)")
     ap.add_argument("--no-cpu-omp", dest="cpu_omp", action="store_false",
                     help="skip the all-core OpenMP run of the oracle (cpu_baseline_omp)")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: add every measurement that takes runs of its own (other accumulate mode, general instance, "
+                         "out-of-cache / depth-4 legs, scale_n1, end_to_end, gp / lv / bgkl legs, CPU baselines); the --no-* "
+                         "options above and --variants apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.variants and not args.full:
+        ap.error("--variants: a leg of --full")
+    if args.dump_outputs and args.workload != "bgk":
+        ap.error("--dump-outputs: supported for --workload bgk only")
 
     import torch
     import la3dm_amd
@@ -235,10 +255,30 @@ def main():
         m.set_option("time_kernel", 0)
         return dt_, (float(kt[:nk.value].mean()) if nk.value else float("nan"))
 
-    # the other accumulate mode first (N = 1 only, its own short run), then the mode the line is quoted on
+    def restore_leaves():
+        # the steps update the leaves in place: back to the scan's own leaves, so that what the timed steps compute
+        # (--dump-outputs) depends on --warmup and --steps only
+        torch.cuda.synchronize()
+        for alpha_t, beta_t, state_t in keep:
+            alpha_t.copy_(up(pk.alpha))
+            beta_t.copy_(up(pk.beta))
+            state_t.zero_()
+
     sum_mode = args.sum if args.sum >= 0 else int(os.environ.get("LA3DM_BGK_SUM", "1"))
+    if world == 1:
+        # bring the GPU to steady state before anything is timed (>= 100 launches and >= 0.2 s of them): --warmup's few
+        # launches of a < 0.1 ms step do not (configs[1], --warmup 5: 0.080 ms per step after them alone, 0.072 after this)
+        m.set_option("bgk_sum", sum_mode)
+        t0, n_settle = time.perf_counter(), 0
+        while n_settle < 100 or time.perf_counter() - t0 < 0.2:
+            for _ in range(10):
+                step()
+            n_settle += 10
+            torch.cuda.synchronize()
+        restore_leaves()
+    # the other accumulate mode first (N = 1 only, its own short run), then the mode the line is quoted on
     other = None
-    if world == 1 and not args.no_other_mode:
+    if args.full and world == 1 and not args.no_other_mode:
         m.set_option("bgk_sum", 1 - sum_mode)
         dt_o, k_o = timed(min(args.steps, 20))
         other = {"bgk_sum": 1 - sum_mode, "ms_per_step": dt_o / min(args.steps, 20) * 1e3, "kernel_ms": k_o}
@@ -246,14 +286,21 @@ def main():
     # the same launch without LA3DM_SCAN_FULL_BLOCKS (what a scan into a map with pruned blocks runs: the instance that
     # carries the general path beside the table path) — its own short run, quoted next to the headline
     general = None
-    if world == 1 and sum_mode == 1 and not args.no_other_mode and (scans[0].flags & 4):
+    if args.full and world == 1 and sum_mode == 1 and not args.no_other_mode and (scans[0].flags & 4):
         for sc in scans:
             sc.flags &= ~4
         _, k_g = timed(min(args.steps, 20))
         for sc in scans:
             sc.flags |= 4
         general = {"kernel_ms": k_g, "what": "the same scan without LA3DM_SCAN_FULL_BLOCKS: the kernel instance with the general (pruned-block) path compiled in"}
+    if other or general:
+        restore_leaves()
     dt, k_ms = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        # the buffer the last timed step wrote (this rank's own leaves)
+        alpha_t, beta_t, state_t = keep[(counter[0] - 1) % n_buf]
+        dump_outputs(args.dump_outputs, {"alpha": alpha_t.cpu().numpy(), "beta": beta_t.cpu().numpy(),
+                                         "state": state_t.cpu().numpy()})
 
     total_U = U
     if world > 1:
@@ -320,9 +367,9 @@ def main():
         else:
             out["roofline"]["traffic_note"] = ("profiles/bgk_traffic.json has no entry stamped with this build's kernel source "
                                                "hash for this workload: counters omitted (tools/prof/update_traffic.sh regenerates)")
-        if world == 1 and not shard_mode and not args.no_e2e:
+        if args.full and world == 1 and not shard_mode and not args.no_e2e:
             out["end_to_end"] = end_to_end(la3dm_amd, params, args)
-        if world == 1 and not args.no_big and args.rays == 200000:
+        if args.full and world == 1 and not args.no_big and args.rays == 200000:
             out["roofline"]["out_of_cache"] = out_of_cache_leg(la3dm_amd, _lib, torch, dev)
             out["roofline"]["depth4"] = depth4_leg(la3dm_amd, _lib, torch, dev)
             if args.variants:
@@ -330,7 +377,7 @@ def main():
             # the N = 1 point of the multi-GPU series (`--gpus N` times configs[4]'s whole insert, not this line's kernel-only step):
             # the same W + K inserts `--gpus N --mode shard` runs, on this GPU — equals that line's `single_gpu`
             out["scale_n1"] = scale_n1_leg(la3dm_amd, torch, dev, args)
-        if world == 1 and not args.no_side:
+        if args.full and world == 1 and not args.no_side:
             # the other BASELINE configs on this GPU, each with its own roofline and CPU leg (same protocol as --workload X);
             # every GPU measurement of the run comes before the first all-core CPU leg
             del m
@@ -342,7 +389,7 @@ def main():
             out["lv"] = lv_leg(side, torch, la3dm_amd, _lib, cpu=False)
             out["gp"] = {"depth3": gp_leg(side, torch, la3dm_amd, _lib, depth=3, cpu=False)}
             out["gp"]["depth4"] = gp_leg(side, torch, la3dm_amd, _lib, depth=4, cpu=False)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             out["cpu_baseline"] = cpu_baseline(params, xyz, origin, args, U)
             if args.cpu_omp:
                 out["cpu_baseline_omp"] = cpu_baseline(params, xyz, origin, args, U, omp=True)
@@ -363,6 +410,26 @@ ACC_SIDE = {0: "the reference's fp32 running sums in row / gather order (bit-ide
             1: "double sums of the same fp32 terms, rounded once per neighbour (BGK-L) / voxel (BGK-LV) — library default since round 5"}
 ACC_NAMES = {0: "the reference's fp32 summation order (bit-identical to the CPU restatement)",
              1: "double accumulators per leaf, alpha / beta rounded once (library default; |dp| <= ~4e-7 from the reference order)"}
+
+
+DUMP_MAX_BYTES = 60 * 10 ** 6      # array data of one dump: with the .npy headers, under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array (all of one length, one entry per leaf) as <path>/<name>.npy in float32.  Above
+    DUMP_MAX_BYTES in all, the same fixed, seeded sample of the leaves from every array, its indices in
+    sample_index.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v).astype(np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    assert all(len(v) == n for v in arrays.values())
+    if 4 * len(arrays) * n > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (4 * len(arrays) + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(v))
 
 
 def kernel_name(m, sum_mode, flags, pk):
@@ -448,6 +515,9 @@ def sharded_insert_bench(args, torch, dist, la3dm_amd, rank, world, local_rank, 
     nk = C.c_uint32()
     _lib.hip().la3dm_kernel_times(m.ctx(), kt.ctypes.data, kt.size, C.byref(nk))
     k_ms = float(kt[max(0, nk.value - args.steps):nk.value].mean()) if nk.value else float("nan")
+    if args.dump_outputs and rank == 0:
+        lv = m.leaves()        # the map after the last timed insert (a replica: the same on every rank)
+        dump_outputs(args.dump_outputs, {"A": lv["A"], "B": lv["B"], "state": lv["state"]})
     if world > 1:
         tt = torch.tensor([dt, dt1], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

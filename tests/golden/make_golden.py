@@ -9,6 +9,8 @@ for the first file; the GPU box only reads the committed outputs).
                    point6f.cpp; oracle/_ref/libla3dm_ref_lv.so): node update sequences incl. the min_W floor and the
                    UNCERTAIN state, the (A, B) constructor, get_prob / get_var, the 28-bit node key, LUT up to depth 5,
                    leaf order / update / prune rounds of whole blocks, block hashing, point6f's constructors.
+  ref_live.npz     the reference's answers to the inputs of test_oracle.py's direct comparisons with oracle/_ref (block
+                   hashing on random points, BGK-LV node sequences, R-tree query orders on a real scan), for where it is not built.
   oracle_kat.npz   known answers of the CPU restatement for the parts the reference cannot pin
                    (Eigen/PCL absent): kernel table k(r), per-block predict cases, voxel-grid
                    filter case.  Regression pins + inputs for the GPU parity tests.
@@ -354,6 +356,92 @@ def scan_kat():
     print("scan_kat.npz:", len(out), "arrays,", {k: int(v.shape[0]) for k, v in out.items() if k.endswith("_A")})
 
 
+# ref_live.npz: the reference's answers to the inputs of test_oracle.py's three direct comparisons with oracle/_ref, so that
+# they also run where the reference layer is not built.  The tests call these same functions when it is.
+LIVE_LV_CFGS = ([0.05, 5, 0.1, 0.2, 0.3, 0.7, 0.2, 0.001, 0.001, 0.001], [0.1, 4, 1.0, 1.0, 0.3, 0.7, 1.0, 1.0, 1.0, 0.1],
+                [0.1, 4, 1.0, 0.2, 0.3, 0.7, 0.15, 0.001, 0.001, 0.05])
+
+
+def live_inputs():
+    """the seeded inputs: block-hash points (depths 3, 4) and BGK-LV node update steps per config"""
+    rng = np.random.default_rng(5)
+    out = {f"d{depth}_pts": rng.uniform(-100, 100, (2000, 3)).astype(np.float32) for depth in (3, 4)}
+    rng = np.random.default_rng(11)
+    for c in range(len(LIVE_LV_CFGS)):
+        n = 4000
+        kb = (rng.uniform(0, 1, n) * rng.choice([1.0, 0.01, 0.1], n)).astype(np.float32)
+        out[f"lv{c}_kb"], out[f"lv{c}_yb"] = kb, (kb * rng.choice([0.0, 1.0, 0.5, 0.2], n)).astype(np.float32)
+    return out
+
+
+def live_hash(R, depth, pts):
+    """block_to_hash_key and get_extended_block of the reference at (YAML, depth)"""
+    R.ref_configure(YAML[0], depth, *YAML[2:])
+    keys = np.array([R.ref_block_to_hash_key(*map(float, p)) for p in pts], np.int64)
+    eb = np.zeros((len(pts), 7), np.int64)
+    for i, k in enumerate(keys):
+        R.ref_get_extended_block(int(k), eb[i])
+    return keys, eb
+
+
+def live_lv(R, cfg, yb, kb):
+    """the reference's BGK-LV node through sequences of 50 update steps from a default node: A, B, state, prob, var"""
+    R.ref_configure(*cfg[:9])
+    R.ref_configure_lv(1, cfg[9])
+    n = len(yb)
+    A = np.zeros(n, np.float32); B = A.copy(); S = np.zeros(n, np.uint8); P = A.copy(); V = A.copy()
+    for lo in range(0, n, 50):
+        a, b, s, p, v = (np.zeros(50, x.dtype) for x in (A, B, S, P, V))
+        R.ref_node_sequence(np.ascontiguousarray(yb[lo:lo + 50]), np.ascontiguousarray(kb[lo:lo + 50]), 50, a, b, s, p, v)
+        A[lo:lo + 50], B[lo:lo + 50], S[lo:lo + 50], P[lo:lo + 50], V[lo:lo + 50] = a, b, s, p, v
+    return dict(A=A, B=B, S=S, P=P, V=V)
+
+
+def live_rtree_inputs():
+    """training points of sim_structured scan 1 (the restatement's front end) and ~150 block keys they fall in"""
+    import la3dm_amd
+    xyz, origin = la3dm_amd.load_pcd(os.path.join(HERE, "data", "sim_structured", "sim_structured_1.pcd"))
+    xy = O.get_training_data(xyz, origin, 0.1, 0.5, 8.0)
+    pts = np.ascontiguousarray(xy[:, :3])
+    m = O.OracleMap(resolution=YAML[0], block_depth=YAML[1], sf2=YAML[2], ell=YAML[3], free_thresh=YAML[4],
+                    occupied_thresh=YAML[5], var_thresh=YAML[6], prior_A=YAML[7], prior_B=YAML[8])
+    keys = np.array(sorted({m.block_to_hash_key(*map(float, p)) for p in pts[:: max(1, pts.shape[0] // 150)]}), np.int64)
+    return xy, keys
+
+
+def live_rtree(R, pts, keys):
+    """for every key, its 7 extended-block keys and the point ids the reference's R-tree returns for each, in its order"""
+    R.ref_configure(*YAML)
+    tree = R.ref_rtree_new(pts, pts.shape[0])
+    ids = np.zeros(pts.shape[0], np.int32)
+    e = np.zeros(7, np.int64)
+    nbs, orders = [], []
+    for key in keys:
+        R.ref_get_extended_block(int(key), e)
+        for nb in e:
+            n = R.ref_rtree_block_query(tree, int(nb), ids, ids.size)
+            nbs.append(int(nb))
+            orders.append(ids[:n].copy())
+    R.ref_rtree_free(tree)
+    return dict(rt_nb=np.array(nbs, np.int64), rt_ids=np.concatenate(orders).astype(np.int32),
+                rt_off=np.cumsum([0] + [len(o) for o in orders]).astype(np.int64))
+
+
+def ref_live():
+    R, RL = O.ref(), O.ref_lv()
+    assert R is not None and RL is not None, "oracle/_ref not built (oracle/Makefile: needs the reference sources)"
+    out = live_inputs()
+    for depth in (3, 4):
+        out[f"d{depth}_keys"], out[f"d{depth}_eblocks"] = live_hash(R, depth, out[f"d{depth}_pts"])
+    for c, cfg in enumerate(LIVE_LV_CFGS):
+        for k, v in live_lv(RL, cfg, out[f"lv{c}_yb"], out[f"lv{c}_kb"]).items():
+            out[f"lv{c}_{k}"] = v
+    xy, out["rt_keys"] = live_rtree_inputs()
+    out.update(live_rtree(R, np.ascontiguousarray(xy[:, :3]), out["rt_keys"]))
+    np.savez_compressed(os.path.join(HERE, "ref_live.npz"), **out)
+    print("ref_live.npz:", len(out), "arrays")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "grid":   # added later: does not disturb the older fixtures
         ref_grid_kat()
@@ -361,6 +449,8 @@ if __name__ == "__main__":
         scan_kat()
     elif len(sys.argv) > 1 and sys.argv[1] == "lv":     # round 4: the reference's compiled BGK-LV node / tree / block
         ref_kat_lv()
+    elif len(sys.argv) > 1 and sys.argv[1] == "live":   # the reference's answers to test_oracle.py's direct comparisons
+        ref_live()
     else:
         ref_kat()
         oracle_kat()

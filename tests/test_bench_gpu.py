@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -32,7 +33,7 @@ def _last_json(out):
 
 def test_single_gpu_line(built):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "1", "--rays", "50000",
-                        "--no-cpu-omp"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--no-cpu-omp", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env={k: v for k, v in os.environ.items() if k != "LA3DM_BGK_SUM"})
     assert r.returncode == 0, r.stderr[-2000:]
     d = _last_json(r.stdout)
@@ -63,6 +64,34 @@ def test_single_gpu_line(built):
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] == 1 and d["cpu_baseline"]["value"] > 0
     assert d["value"] > 100 * d["cpu_baseline"]["value"]
     assert d["end_to_end"]["ms_per_insert"] > 0
+
+
+def test_plain_line_dumps_outputs(built, tmp_path):
+    """a plain run: only the timed steps and the line (no leg of --full); --dump-outputs writes the leaves the last step
+    updated, the same on every run with the same arguments"""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--rays", "50000", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _last_json(r.stdout)
+        for k in KEYS:
+            assert k in d, k
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["kernel_ms"] > 0
+        for k in ("cpu_baseline", "end_to_end", "scale_n1", "gp", "lv", "bgkl"):
+            assert k not in d, k
+        assert not {"ordered", "double_sum", "general_instance", "out_of_cache", "depth4"} & set(d["roofline"])
+        assert sorted(p.name for p in out.iterdir()) == ["alpha.npy", "beta.npy", "state.npy"]
+        dumps.append({k: np.load(out / f"{k}.npy") for k in ("alpha", "beta", "state")})
+    a, b = dumps
+    n = a["alpha"].shape[0]
+    assert n > 0 and all(v.dtype == np.float32 and v.shape == (n,) for v in a.values())
+    # state: 0 = leaf not updated, else LA3DM_LEAF_UPDATED (0x80) | the occupancy code (free, occupied, unknown, pruned)
+    assert (a["alpha"] > 0).all() and (a["beta"] > 0).all() and np.isin(a["state"], (0, 128, 129, 130, 131)).all()
+    assert (a["state"] >= 128).any()
+    for k in a:
+        assert (a[k].view(np.uint32) == b[k].view(np.uint32)).all(), k
 
 
 @pytest.mark.parametrize("mode,scaling", [("scans", "weak"), ("shard", "strong")])

@@ -1,11 +1,12 @@
 """CPU tests of the ORACLE itself (not gpu): the restatement is pinned against
   * tests/golden/ref_kat.npz  — answers captured from the reference's own std-only sources
     compiled in place (oracle/_ref), and
-  * oracle/_ref directly when it is present (this container; travels prebuilt to the GPU box),
+  * oracle/_ref directly when it is present, and its answers to the same inputs (tests/golden/ref_live.npz) where it is not,
 and, for the Eigen/PCL-dependent arithmetic the reference cannot pin, against analytic
 properties and a float64 evaluation.
 """
 import ctypes as C
+import importlib.util
 import os
 
 import numpy as np
@@ -20,6 +21,19 @@ YAML = dict(resolution=0.1, block_depth=3, sf2=1.0, ell=0.2, free_thresh=0.3, oc
 @pytest.fixture(scope="module")
 def kat():
     return np.load(os.path.join(GOLDEN, "ref_kat.npz"))
+
+
+@pytest.fixture(scope="module")
+def live():
+    """the reference's answers to the direct comparisons' inputs (tests/golden/make_golden.py live), and that module"""
+    spec = importlib.util.spec_from_file_location("make_golden", os.path.join(GOLDEN, "make_golden.py"))
+    G = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(G)
+    return G, dict(np.load(os.path.join(GOLDEN, "ref_live.npz")))
+
+
+def _same(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and (a.view(np.uint8) == b.view(np.uint8)).all()
 
 
 @pytest.fixture(scope="module")
@@ -107,21 +121,21 @@ def test_closed_box_rule_against_reference_rtree(O, kat):
         assert sorted(ids[:n].tolist()) == kat["rtree_ids"][off[i]:off[i + 1]].tolist()
 
 
-def test_live_reference_layer_if_present(O):
-    """direct comparison with oracle/_ref on fresh random inputs (skipped where it was not built)"""
+def test_live_reference_layer_if_present(O, live):
+    """block hashing against oracle/_ref on random points — live where it was built (and the stored answers checked against
+    it), else its answers to the same points stored in tests/golden/ref_live.npz"""
+    G, kat = live
     R = O.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built here")
-    rng = np.random.default_rng(5)
     for depth in (3, 4):
-        R.ref_configure(0.1, depth, 1.0, 0.2, 0.3, 0.7, 100.0, 0.001, 0.001)
+        pts, keys, eb = kat[f"d{depth}_pts"], kat[f"d{depth}_keys"], kat[f"d{depth}_eblocks"]
+        assert _same(pts, G.live_inputs()[f"d{depth}_pts"])
+        if R is not None:
+            k_live, eb_live = G.live_hash(R, depth, pts)
+            assert _same(keys, k_live) and _same(eb, eb_live)
         m = O.OracleMap(**dict(YAML, block_depth=depth))
-        e1, e2 = np.zeros(7, np.int64), None
-        for p in rng.uniform(-100, 100, (2000, 3)).astype(np.float32):
-            k = R.ref_block_to_hash_key(*map(float, p))
+        for p, k, e in zip(pts, keys, eb):
             assert m.block_to_hash_key(*map(float, p)) == k
-            R.ref_get_extended_block(k, e1)
-            assert (m.get_extended_block(k) == e1).all()
+            assert (m.get_extended_block(int(k)) == e).all()
 
 
 # ---------------------------------------------------------------------------
@@ -227,31 +241,28 @@ def test_lv_block_hash_lut_leaves_prune_against_reference_kat(O, kat_lv, depth):
         L.orc_lv_block_free(b)
 
 
-def test_live_lv_reference_layer_if_present(O):
-    """12 000 fresh random update steps through the reference's compiled LV node and the restatement (skipped where
-    oracle/_ref was not built)"""
+def test_live_lv_reference_layer_if_present(O, live):
+    """12 000 random update steps through the reference's compiled LV node and the restatement — live where oracle/_ref
+    was built (and the stored answers checked against it), else its answers stored in tests/golden/ref_live.npz"""
+    G, kat = live
     R = O.ref_lv()
-    if R is None:
-        pytest.skip("oracle/_ref/libla3dm_ref_lv.so not built here")
-    rng = np.random.default_rng(11)
     L = O.lib()
-    for cfg in ([0.05, 5, 0.1, 0.2, 0.3, 0.7, 0.2, 0.001, 0.001, 0.001], [0.1, 4, 1.0, 1.0, 0.3, 0.7, 1.0, 1.0, 1.0, 0.1],
-                [0.1, 4, 1.0, 0.2, 0.3, 0.7, 0.15, 0.001, 0.001, 0.05]):
-        R.ref_configure(*cfg[:9])
-        R.ref_configure_lv(1, cfg[9])
+    inputs = G.live_inputs()
+    for c, cfg in enumerate(G.LIVE_LV_CFGS):
+        yb, kb = kat[f"lv{c}_yb"], kat[f"lv{c}_kb"]
+        assert _same(yb, inputs[f"lv{c}_yb"]) and _same(kb, inputs[f"lv{c}_kb"])
+        ref = {k: kat[f"lv{c}_{k}"] for k in "ABSPV"}
+        if R is not None:
+            ref_live = G.live_lv(R, cfg, yb, kb)
+            assert all(_same(ref[k], ref_live[k]) for k in "ABSPV")
         m = _lv_map(O, cfg)
-        n = 4000
-        kb = (rng.uniform(0, 1, n) * rng.choice([1.0, 0.01, 0.1], n)).astype(np.float32)
-        yb = (kb * rng.choice([0.0, 1.0, 0.5, 0.2], n)).astype(np.float32)
-        for lo in range(0, n, 50):          # sequences of 50 steps from a default node
-            A = np.zeros(50, np.float32); B = A.copy(); S = np.zeros(50, np.uint8); P = A.copy(); V = A.copy()
-            R.ref_node_sequence(np.ascontiguousarray(yb[lo:lo + 50]), np.ascontiguousarray(kb[lo:lo + 50]), 50, A, B, S, P, V)
+        for lo in range(0, len(yb), 50):          # sequences of 50 steps from a default node
             a, b, s = C.c_float(np.float32(cfg[7])), C.c_float(np.float32(cfg[8])), C.c_uint8(2)
-            for i in range(50):
-                L.orc_lv_node_update(m.h, C.byref(a), C.byref(b), C.byref(s), float(yb[lo + i]), float(kb[lo + i]))
-                assert np.float32(a.value) == A[i] and np.float32(b.value) == B[i] and s.value == S[i]
-                assert np.float32(L.orc_lv_node_prob(m.h, a.value, b.value)) == P[i]
-                assert np.float32(L.orc_lv_node_var(m.h, a.value, b.value)) == V[i]
+            for i in range(lo, lo + 50):
+                L.orc_lv_node_update(m.h, C.byref(a), C.byref(b), C.byref(s), float(yb[i]), float(kb[i]))
+                assert np.float32(a.value) == ref["A"][i] and np.float32(b.value) == ref["B"][i] and s.value == ref["S"][i]
+                assert np.float32(L.orc_lv_node_prob(m.h, a.value, b.value)) == ref["P"][i]
+                assert np.float32(L.orc_lv_node_var(m.h, a.value, b.value)) == ref["V"][i]
 
 
 def test_kernel_properties(O):
@@ -337,28 +348,27 @@ def test_full_scan_fixtures_reproduced(O):
         assert lv[k].shape == kat[f"bgkl_d3_{k}"].shape and (lv[k] == kat[f"bgkl_d3_{k}"]).all(), k
 
 
-def test_reference_rtree_gather_order_stays_within_the_tolerance(O):
+def test_reference_rtree_gather_order_stays_within_the_tolerance(O, live):
     """The restatement gathers a block's training points in ascending index; the reference gets them in the traversal
     order of its R-tree (include/common/rtree.h — compiled from the reference's own source in oracle/_ref), which only
-    permutes the fp32 sums of Ks*y.  Measured here on a real scan with the REAL tree: the per-leaf posterior after the
-    7-neighbour fusion moves by far less than the 1e-5 the north star allows (and the orders do differ)."""
-    R = O.ref()
-    if R is None:
-        pytest.skip("oracle/_ref not built here")
-    import la3dm_amd
-    from conftest import pcd_path
-    R.ref_configure(0.1, 3, 1.0, 0.2, 0.3, 0.7, 100.0, 0.001, 0.001)
+    permutes the fp32 sums of Ks*y.  Measured here on a real scan with the REAL tree's orders (live where oracle/_ref was
+    built, and the stored ones checked against it; else as stored in tests/golden/ref_live.npz): the per-leaf posterior
+    after the 7-neighbour fusion moves by far less than the 1e-5 the north star allows (and the orders do differ)."""
+    G, kat = live
     m = O.OracleMap(**YAML)
-    xyz, origin = la3dm_amd.load_pcd(pcd_path("sim_structured", 1))
-    xy = O.get_training_data(xyz, origin, 0.1, 0.5, 8.0)
+    xy, keys = G.live_rtree_inputs()
     pts = np.ascontiguousarray(xy[:, :3])
-    tree = R.ref_rtree_new(pts, pts.shape[0])
-    ids = np.zeros(pts.shape[0], np.int32)
-    keys = sorted({m.block_to_hash_key(*map(float, p)) for p in pts[:: max(1, pts.shape[0] // 150)]})
+    assert _same(keys, kat["rt_keys"])
+    tree = {k: kat[k] for k in ("rt_nb", "rt_ids", "rt_off")}
+    R = O.ref()
+    if R is not None:
+        tree_live = G.live_rtree(R, pts, keys)
+        assert all(_same(tree[k], tree_live[k]) for k in tree)
+    nbs, ids, off = tree["rt_nb"], tree["rt_ids"], tree["rt_off"]
+    assert nbs.size == 7 * keys.size and ids.max() < pts.shape[0]
     reordered, worst, n_leaf = 0, 0.0, 0
-    e = np.zeros(7, np.int64)
-    for key in keys:
-        c = m.hash_key_to_block(key)
+    for i, key in enumerate(keys):
+        c = m.hash_key_to_block(int(key))
         b = m.L.orc_block_new(m.h, float(c[0]), float(c[1]), float(c[2]))
         lk, loc = np.zeros(64, np.int32), np.zeros((64, 3), np.float32)
         nl = m.L.orc_block_leaves(m.h, b, lk, loc, 64)
@@ -366,12 +376,11 @@ def test_reference_rtree_gather_order_stays_within_the_tolerance(O):
         xs = loc[:nl]
         A = {"ref": np.full(nl, 0.001, np.float32), "asc": np.full(nl, 0.001, np.float32)}
         B = {"ref": np.full(nl, 0.001, np.float32), "asc": np.full(nl, 0.001, np.float32)}
-        R.ref_get_extended_block(key, e)
-        for nb in e:
-            n = R.ref_rtree_block_query(tree, int(nb), ids, ids.size)
-            if n == 0:
+        assert (m.get_extended_block(int(key)) == nbs[7 * i:7 * i + 7]).all()
+        for q in range(7 * i, 7 * i + 7):
+            if off[q + 1] == off[q]:
                 continue
-            order = {"ref": ids[:n].copy(), "asc": np.sort(ids[:n])}
+            order = {"ref": ids[off[q]:off[q + 1]], "asc": np.sort(ids[off[q]:off[q + 1]])}
             reordered += int((order["ref"] != order["asc"]).any())
             for tag in ("ref", "asc"):
                 ybar, kbar = O.bgk_predict(1.0, 0.2, xs, pts[order[tag]], xy[order[tag], 3])
@@ -381,7 +390,6 @@ def test_reference_rtree_gather_order_stays_within_the_tolerance(O):
         p_ref, p_asc = A["ref"] / (A["ref"] + B["ref"]), A["asc"] / (A["asc"] + B["asc"])
         worst = max(worst, float(np.abs(p_ref - p_asc).max()))
         n_leaf += nl
-    R.ref_rtree_free(tree)
     assert reordered > 50 and n_leaf > 5000       # the tree's order really differs from ascending index
     assert worst <= 1e-5, worst
     assert worst < 2e-6                           # in fact: a few ulps of the sums

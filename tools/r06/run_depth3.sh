@@ -8,7 +8,7 @@ timeout 420 python -m pytest -q -m gpu -x tests/test_devmap_gpu.py tests/test_sh
    "tests/test_baseline_configs_gpu.py::test_config1_bgk_200k_rays" tests/test_bgk_sum_gpu.py::test_config4_scan_1m_rays 2>&1 | tail -6 | tee $O/tests.txt
 for v in 0 1; do
   LA3DM_DEPTH3=$v timeout 200 python bench.py --gpus 1 --mode shard --steps 20 --warmup 3 > $O/shard_$v.json 2> $O/shard_$v.err
-  LA3DM_DEPTH3=$v timeout 200 python bench.py --no-side --no-cpu --no-big --no-other-mode --steps 10 > $O/e2e_$v.json 2> $O/e2e_$v.err
+  LA3DM_DEPTH3=$v timeout 200 python bench.py --full --no-side --no-cpu --no-big --no-other-mode --steps 10 > $O/e2e_$v.json 2> $O/e2e_$v.err
 done
 python - <<PY
 import json

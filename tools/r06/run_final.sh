@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 O=gpurun_out/r06/final; mkdir -p $O
 timeout 800 python -m pytest tests -q -m gpu --durations=15 > $O/full_gpu_suite.log 2>&1
 tail -20 $O/full_gpu_suite.log
-timeout 300 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 bash tools/prof/prof_devmap.sh 200000 5 0.1 > /dev/null 2>&1; cp gpurun_out/prof_devmap/timeline.txt $O/devmap_timeline_200k.txt
 bash tools/prof/prof_devmap.sh 1000000 4 0.05 > /dev/null 2>&1; cp gpurun_out/prof_devmap/timeline.txt $O/devmap_timeline_1M.txt
 python - <<PY

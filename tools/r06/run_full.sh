@@ -11,9 +11,9 @@ if [ "$RESTAMP" = "1" ]; then
   timeout 2400 bash tools/prof/restamp_all.sh > $O/restamp.log 2>&1
   tail -4 $O/restamp.log
 fi
-timeout 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 tail -c 300 $O/bench_default.err
-timeout 600 python bench.py --variants --no-side --no-cpu --no-e2e > $O/bench_variants.json 2> $O/bench_variants.err
+timeout 600 python bench.py --full --variants --no-side --no-cpu --no-e2e > $O/bench_variants.json 2> $O/bench_variants.err
 python - <<PY
 import json
 d=json.loads([l for l in open("$O/bench_default.json") if l.startswith("{")][-1])
