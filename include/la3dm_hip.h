@@ -190,7 +190,8 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *scan, void *stre
  * GPR3f::train (include/gpoctomap/gpregressor.h:42-51: Matern-3/2 K + noise I, LLT, alpha) for every
  * training block, GPR3f::predict (:80-92: m = Ks^T alpha, v = L^-1 Ks, var = sf2 - diag(v^T v)) for
  * every (test block, neighbour), and the unconditional BCM Occupancy::update
- * (src/gpoctomap/gpoctree_node.cpp:36-49) in ExtendedBlock order. */
+ * (src/gpoctomap/gpoctree_node.cpp:36-49) in ExtendedBlock order.  A neighbour whose training block holds no
+ * points (train_off[b] == train_off[b + 1]) is skipped like -1: no model, no update. */
 int la3dm_gp_scan_host(la3dm_ctx *ctx, const la3dm_bgk_scan *scan, la3dm_bgk_counters *out);
 int la3dm_gp_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *scan, void *stream, la3dm_bgk_counters *out);
 
