@@ -385,6 +385,48 @@ int la3dm_devmap_download(la3dm_devmap *dm, int64_t *keys, float *A, float *B, u
  * finest-layer node that holds the point (a default node when the block is missing). */
 int la3dm_devmap_search_host(la3dm_devmap *dm, const float *xyz, uint32_t n, uint8_t *exists, float *A, float *B,
                              uint8_t *state);
+/* Batched ray casting on the device pool: the client loop over BGKOctoMap::RayCaster (include/bgkoctomap/bgkoctomap.h:91-214)
+ * for n segments at once, one ray per GPU lane.  rays6: start xyz, end xyz per ray.  Per ray
+ *     steps = 0; counts = {0}; flags = 0
+ *     RayCaster rc(map, start, end)           -- the unchanged voxel walk; starts only inside an existing block
+ *     while (!rc.end()) {
+ *         if (steps == max_steps) { flags |= LA3DM_RAY_TRUNCATED; break; }
+ *         valid = rc.next(p, node, block_key, node_key); ++steps
+ *         cls = valid ? state of the COVERING LEAF of node_key in that block : LA3DM_RAY_MISSING
+ *         ++counts[cls]; last = this row
+ *         if (stop_mask & (1u << cls)) { flags |= LA3DM_RAY_HIT; break; }
+ *     }
+ * Covering leaf: climb from the finest-layer node while its state is PRUNED (prune() leaves the eight children of a
+ * collapsed group PRUNED; the answer lives in an ancestor).  leaf_depth = the layer where the climb ends (block_depth - 1
+ * when nothing was pruned); A, B are that node's.  cls: FREE 0, OCCUPIED 1, UNKNOWN 2, LA3DM_RAY_MISSING 3 (the block does
+ * not exist: A, B = the map's default node, leaf_depth 255); a BGK-LV map's UNCERTAIN leaves report 4 and are counted with
+ * UNKNOWN in counts[2].  A ray that never starts (its start block does not exist, or the map is empty) has steps = 0,
+ * flags = 0, cls = LA3DM_RAY_MISSING, leaf_depth 255, default A / B, everything else 0.  A ray with a non-finite
+ * coordinate or |coordinate / resolution| >= 2^30 is refused on its own: flags = LA3DM_RAY_INVALID, the other outputs as
+ * for a ray that never starts.  stop_mask 0 walks to the end and only counts.  max_steps: 1 ... LA3DM_RAY_MAX_STEPS.
+ * Every pointer of `out` except steps and flags may be NULL.  The result is bit-identical to the host loop. */
+#define LA3DM_RAY_HIT 1u
+#define LA3DM_RAY_TRUNCATED 2u
+#define LA3DM_RAY_INVALID 4u
+#define LA3DM_RAY_MISSING 3u
+#define LA3DM_RAY_MAX_STEPS (1u << 20)
+typedef struct la3dm_raycast_out {
+    uint32_t *steps;     /* [n] rows produced */
+    uint8_t *flags;      /* [n] LA3DM_RAY_* */
+    float *p;            /* [3n] last row: voxel centre (dead-reckoned position inside a missing block) */
+    int64_t *block_key;  /* [n] */
+    int32_t *node_key;   /* [n] finest-layer key of the last row, as next() reports it */
+    uint8_t *cls;        /* [n] */
+    uint8_t *leaf_depth; /* [n] */
+    float *A, *B;        /* [n] */
+    uint32_t *counts;    /* [4n] rows per class: FREE, OCCUPIED, UNKNOWN, MISSING */
+} la3dm_raycast_out;
+/* host pointers: upload, one launch, download, synchronise — on the map's stream */
+int la3dm_devmap_raycast_host(la3dm_devmap *dm, const float *rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
+                              const la3dm_raycast_out *out);
+/* device pointers (rays and outputs already in HBM on the map's device); returns when the results are complete */
+int la3dm_devmap_raycast_device(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
+                                const la3dm_raycast_out *d_out);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

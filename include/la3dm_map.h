@@ -111,6 +111,15 @@ int la3dm_map_search(const la3dm_map *m, float x, float y, float z, float *A, fl
 /* search for n points at once (packed xyz); device-resident maps answer from the device pool without a mirror refresh */
 int la3dm_map_search_many(const la3dm_map *m, const float *xyz, uint64_t n, uint8_t *exists, float *A, float *B,
                           uint8_t *state);
+/* BGKOctoMap::raycast_many: the client loop over a RayCaster for n segments at once (rays6: start xyz, end xyz per ray) —
+ * walk until the end, max_steps rows, or a row whose class (state of the voxel's covering leaf, LA3DM_RAY_MISSING where
+ * the block does not exist) is in stop_mask; semantics and `out` in include/la3dm_hip.h (la3dm_devmap_raycast_host).
+ * Device-resident maps answer from the device pool without a mirror refresh, host-mode maps run the loop on the host;
+ * the results are bit-identical. */
+int la3dm_map_raycast_many(const la3dm_map *m, const float *rays6, uint64_t n, uint32_t stop_mask, uint32_t max_steps,
+                           const la3dm_raycast_out *out);
+/* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
+uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);
 /* Block(center).get_index(p) / get_node / get_point (reference bgkblock.cpp:131-150) */
 void la3dm_map_block_grid(const la3dm_map *m, const float *center3, const float *p3, int32_t *idx3, int32_t *node_key,

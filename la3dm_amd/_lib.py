@@ -72,6 +72,11 @@ class DevmapStats(C.Structure):
                [(k, C.c_double) for k in ("t_frontend", "t_partition", "t_pack", "t_kernel", "t_commit", "t_total", "t_gather")]
 
 
+class RaycastOut(C.Structure):   # la3dm_raycast_out (include/la3dm_hip.h)
+    _fields_ = [(k, C.c_void_p) for k in ("steps", "flags", "p", "block_key", "node_key", "cls", "leaf_depth", "A", "B",
+                                          "counts")]
+
+
 HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_destroy", "la3dm_last_error",
                "la3dm_set_option", "la3dm_get_option", "la3dm_bgk_scan_host", "la3dm_bgk_scan_device", "la3dm_gp_scan_host",
                "la3dm_gp_scan_device", "la3dm_bgklv_scan_host", "la3dm_bgklv_scan_device", "la3dm_kernel_times", "la3dm_diag_eval", "la3dm_diag_sweep",
@@ -82,7 +87,8 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_export_cells", "la3dm_devmap_key_bounds",
                "la3dm_devmap_insert_training_data_host", "la3dm_devmap_set_shard", "la3dm_devmap_wait_event",
                "la3dm_devmap_lv_stats_get", "la3dm_devmap_lv_set_original_size", "la3dm_devmap_lv_training",
-               "la3dm_devmap_diag_scan", "la3dm_devmap_diag_sort"]
+               "la3dm_devmap_diag_scan", "la3dm_devmap_diag_sort", "la3dm_devmap_raycast_host",
+               "la3dm_devmap_raycast_device"]
 MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
                "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
                "la3dm_map_insert_training_data", "la3dm_map_prepare", "la3dm_map_prepare_training_data",
@@ -93,7 +99,8 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_set_device_resident", "la3dm_map_is_device_resident", "la3dm_map_raycast",
                "la3dm_map_block_grid", "la3dm_map_create_l", "la3dm_map_l_training",
                "la3dm_map_search_many", "la3dm_map_export_cells", "la3dm_map_set_shard", "la3dm_map_resolution",
-               "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth"]
+               "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth",
+               "la3dm_map_raycast_many", "la3dm_map_mirror_syncs"]
 
 _hip = None
 _map = None
@@ -163,6 +170,10 @@ def hip():
         L.la3dm_devmap_diag_add_repeat.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 2
         L.la3dm_devmap_search_host.restype = C.c_int
         L.la3dm_devmap_search_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
+        L.la3dm_devmap_raycast_host.restype = C.c_int
+        L.la3dm_devmap_raycast_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
+        L.la3dm_devmap_raycast_device.restype = C.c_int
+        L.la3dm_devmap_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
         L.la3dm_devmap_training_data.restype = C.c_int
         L.la3dm_devmap_training_data.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         _hip = L
@@ -203,6 +214,10 @@ def maplib():
         M.la3dm_map_export_cells.restype = C.c_int
         M.la3dm_map_export_cells.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        M.la3dm_map_raycast_many.restype = C.c_int
+        M.la3dm_map_raycast_many.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
+        M.la3dm_map_mirror_syncs.restype = C.c_uint64
+        M.la3dm_map_mirror_syncs.argtypes = [C.c_void_p]
         M.la3dm_map_raycast.restype = C.c_uint64
         M.la3dm_map_raycast.argtypes = [C.c_void_p, f32p, f32p] + [C.c_void_p] * 7 + [C.c_uint64]
         M.la3dm_map_set_shard.restype = C.c_int

@@ -11,6 +11,10 @@ import numpy as np
 from . import _lib
 
 FREE, OCCUPIED, UNKNOWN, PRUNED = 0, 1, 2, 3
+# raycast_many: class of a row whose block does not exist (a covering leaf is never PRUNED, so the slot is free), ray flags
+MISSING = 3
+RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
+_RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
 class PackedScan:
@@ -179,6 +183,37 @@ class BGKOctoMap:
                                                           ("p", "block_key", "node_key", "valid", "A", "B", "state")], cap)
         n = min(int(n), cap)
         return {k: v[:n] for k, v in out.items()}
+
+    def raycast_many(self, starts, ends, stop=("occupied",), max_steps=4096):
+        """The client loop over a RayCaster for n segments starts[i] -> ends[i] at once: every ray is walked until it
+        ends, produced `max_steps` rows (flags & RAY_TRUNCATED) or met a row whose class is in `stop` (flags & RAY_HIT).
+        The class of a row is the state of the COVERING LEAF of its voxel (after prune() the raw finest-layer node of a
+        collapsed region reads PRUNED; the answer lives in an ancestor) or MISSING where the block does not exist.
+        stop: names out of free / occupied / unknown / missing (/ uncertain on a BGK-LV map), or an integer bit mask;
+        () walks to the end and only counts.  Returns a dict of arrays: steps (rows), flags, and of the last row p,
+        block_key, node_key, cls, leaf_depth, A, B; counts (n, 4) = rows per class FREE, OCCUPIED, UNKNOWN, MISSING.
+        A device-resident map runs one HIP launch on the device pool (no host mirror refresh); a host-mode map runs
+        the loop on the host, with bit-identical results."""
+        s = np.ascontiguousarray(starts, np.float32).reshape(-1, 3)
+        e = np.ascontiguousarray(ends, np.float32).reshape(-1, 3)
+        if s.shape != e.shape:
+            raise ValueError("raycast_many: starts and ends differ in shape")
+        if isinstance(stop, str):
+            stop = (stop,)
+        mask = int(stop) if isinstance(stop, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(stop))
+        n = s.shape[0]
+        rays = np.ascontiguousarray(np.hstack([s, e]))
+        out = dict(steps=np.zeros(n, np.uint32), flags=np.zeros(n, np.uint8), p=np.zeros((n, 3), np.float32),
+                   block_key=np.zeros(n, np.int64), node_key=np.zeros(n, np.int32), cls=np.zeros(n, np.uint8),
+                   leaf_depth=np.zeros(n, np.uint8), A=np.zeros(n, np.float32), B=np.zeros(n, np.float32),
+                   counts=np.zeros((n, 4), np.uint32))
+        o = _lib.RaycastOut(*[out[k].ctypes.data for k, _ in _lib.RaycastOut._fields_])
+        self._chk(self._M.la3dm_map_raycast_many(self._h, rays, n, mask, int(max_steps), C.byref(o)))
+        return out
+
+    def mirror_syncs(self):
+        """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
+        return int(self._M.la3dm_map_mirror_syncs(self._h))
 
     def export_cells(self, state="occupied", original_size=True, min_z=0.0, max_z=0.0):
         """Cube lists of the map (the static node's publish loop + MarkerArrayPub::insert_point3d / heightMapColor,

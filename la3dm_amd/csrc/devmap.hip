@@ -23,6 +23,7 @@
 #include "devmap_lv_kernels.h"
 #include "devmap_depth3.h"
 #include "devmap_grid_keys.h"
+#include "devmap_raycast.h"
 
 using namespace la3dm_dev;
 
@@ -2229,6 +2230,144 @@ int la3dm_devmap_search_host(la3dm_devmap *dm, const float *xyz, uint32_t n, uin
     DM_TRY(hipMemcpyAsync(B, qB, 4ull * n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipMemcpyAsync(exists, qe, n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipMemcpyAsync(state, qs, n, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+// ---- batched ray casting (devmap_raycast.h) -----------------------------------------------------------------
+static int raycast_check(la3dm_devmap *dm, const float *rays6, uint32_t n, uint32_t max_steps, const la3dm_raycast_out *out,
+                         const char *who) {
+    if (!dm) return LA3DM_ERR_ARG;
+    dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (max_steps == 0 || max_steps > LA3DM_RAY_MAX_STEPS)
+        return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": max_steps must be 1 ... 2^20");
+    if (n == 0) return LA3DM_OK;
+    if (!rays6) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": rays6 is NULL");
+    if (!out || !out->steps || !out->flags) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": out, out->steps and out->flags must not be NULL");
+    return LA3DM_OK;
+}
+
+static void raycast_launch(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
+                           const la3dm_raycast_out &o) {
+    RaycastArgs a;
+    memset(&a, 0, sizeof(a));
+    a.rays = d_rays6;
+    a.n = n;
+    a.stop_mask = stop_mask;
+    a.max_steps = max_steps;
+    a.tab_key = dm->tab_key;
+    a.tab_val = dm->tab_val;
+    a.mask = dm->tab_cap - 1;
+    a.A = dm->A;
+    a.B = dm->B;
+    a.S = dm->S;
+    a.lut = dm->ctx->d_lut;
+    a.npb = dm->npb;
+    a.depth = dm->depth;
+    a.block_size = dm->block_size;
+    a.resolution = dm->ctx->p.resolution;
+    a.a0 = dm->init_A;
+    a.b0 = dm->init_B;
+    a.steps = o.steps;
+    a.flags = o.flags;
+    a.p = o.p;
+    a.block_key = (long long *)o.block_key;
+    a.node_key = o.node_key;
+    a.cls = o.cls;
+    a.leaf_depth = o.leaf_depth;
+    a.oA = o.A;
+    a.oB = o.B;
+    a.counts = o.counts;
+    hipLaunchKernelGGL(dm_raycast, dim3(cdiv(n, 256)), dim3(256), 0, dm->ctx->stream, a);
+}
+
+int la3dm_devmap_raycast_device(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
+                                const la3dm_raycast_out *d_out) {
+    int rc = raycast_check(dm, d_rays6, n, max_steps, d_out, "la3dm_devmap_raycast_device");
+    if (rc != LA3DM_OK || n == 0) return rc;
+    DM_TRY(hipSetDevice(dm->ctx->device));
+    hipStream_t st = dm->ctx->stream;
+    const la3dm_raycast_out &o = *d_out;
+    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched (the constant answer is written by memsets)
+        DM_TRY(hipMemsetAsync(o.steps, 0, 4ull * n, st));
+        DM_TRY(hipMemsetAsync(o.flags, 0, n, st));
+        if (o.p) DM_TRY(hipMemsetAsync(o.p, 0, 12ull * n, st));
+        if (o.block_key) DM_TRY(hipMemsetAsync(o.block_key, 0, 8ull * n, st));
+        if (o.node_key) DM_TRY(hipMemsetAsync(o.node_key, 0, 4ull * n, st));
+        if (o.cls) DM_TRY(hipMemsetAsync(o.cls, (int)LA3DM_RAY_MISSING, n, st));
+        if (o.leaf_depth) DM_TRY(hipMemsetAsync(o.leaf_depth, 255, n, st));
+        uint32_t ab[2];
+        memcpy(&ab[0], &dm->init_A, 4);
+        memcpy(&ab[1], &dm->init_B, 4);
+        if (o.A) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.A, (int)ab[0], n, st));
+        if (o.B) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.B, (int)ab[1], n, st));
+        if (o.counts) DM_TRY(hipMemsetAsync(o.counts, 0, 16ull * n, st));
+        DM_TRY(hipStreamSynchronize(st));
+        return LA3DM_OK;
+    }
+    raycast_launch(dm, d_rays6, n, stop_mask, max_steps, o);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_raycast_host(la3dm_devmap *dm, const float *rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
+                              const la3dm_raycast_out *out) {
+    int rc = raycast_check(dm, rays6, n, max_steps, out, "la3dm_devmap_raycast_host");
+    if (rc != LA3DM_OK || n == 0) return rc;
+    const la3dm_raycast_out &h = *out;
+    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched
+        for (uint32_t i = 0; i < n; ++i) {
+            h.steps[i] = 0;
+            h.flags[i] = 0;
+            if (h.p) h.p[3 * (size_t)i] = h.p[3 * (size_t)i + 1] = h.p[3 * (size_t)i + 2] = 0.f;
+            if (h.block_key) h.block_key[i] = 0;
+            if (h.node_key) h.node_key[i] = 0;
+            if (h.cls) h.cls[i] = (uint8_t)LA3DM_RAY_MISSING;
+            if (h.leaf_depth) h.leaf_depth[i] = 255;
+            if (h.A) h.A[i] = dm->init_A;
+            if (h.B) h.B[i] = dm->init_B;
+            if (h.counts) h.counts[4 * (size_t)i] = h.counts[4 * (size_t)i + 1] = h.counts[4 * (size_t)i + 2] = h.counts[4 * (size_t)i + 3] = 0;
+        }
+        return LA3DM_OK;
+    }
+    DM_TRY(hipSetDevice(dm->ctx->device));
+    hipStream_t st = dm->ctx->stream;
+    // arenas as in la3dm_devmap_search_host: rays in `cloud`, results in `q_out` (widest type first: every array aligned)
+    DM_RESERVE(dm->cloud, 24ull * n);
+    DM_RESERVE(dm->q_out, 55ull * n + 64);
+    la3dm_raycast_out d;
+    d.block_key = (int64_t *)dm->q_out.ptr;
+    d.counts = (uint32_t *)(d.block_key + n);
+    d.p = (float *)(d.counts + 4ull * n);
+    d.steps = (uint32_t *)(d.p + 3ull * n);
+    d.node_key = (int32_t *)(d.steps + n);
+    d.A = (float *)(d.node_key + n);
+    d.B = d.A + n;
+    d.flags = (uint8_t *)(d.B + n);
+    d.cls = d.flags + n;
+    d.leaf_depth = d.cls + n;
+    if (!h.p) d.p = nullptr;
+    if (!h.block_key) d.block_key = nullptr;
+    if (!h.node_key) d.node_key = nullptr;
+    if (!h.cls) d.cls = nullptr;
+    if (!h.leaf_depth) d.leaf_depth = nullptr;
+    if (!h.A) d.A = nullptr;
+    if (!h.B) d.B = nullptr;
+    if (!h.counts) d.counts = nullptr;
+    DM_TRY(hipMemcpyAsync(dm->cloud.ptr, rays6, 24ull * n, hipMemcpyHostToDevice, st));
+    raycast_launch(dm, (const float *)dm->cloud.ptr, n, stop_mask, max_steps, d);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipMemcpyAsync(h.steps, d.steps, 4ull * n, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(h.flags, d.flags, n, hipMemcpyDeviceToHost, st));
+    if (h.p) DM_TRY(hipMemcpyAsync(h.p, d.p, 12ull * n, hipMemcpyDeviceToHost, st));
+    if (h.block_key) DM_TRY(hipMemcpyAsync(h.block_key, d.block_key, 8ull * n, hipMemcpyDeviceToHost, st));
+    if (h.node_key) DM_TRY(hipMemcpyAsync(h.node_key, d.node_key, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.cls) DM_TRY(hipMemcpyAsync(h.cls, d.cls, n, hipMemcpyDeviceToHost, st));
+    if (h.leaf_depth) DM_TRY(hipMemcpyAsync(h.leaf_depth, d.leaf_depth, n, hipMemcpyDeviceToHost, st));
+    if (h.A) DM_TRY(hipMemcpyAsync(h.A, d.A, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.B) DM_TRY(hipMemcpyAsync(h.B, d.B, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.counts) DM_TRY(hipMemcpyAsync(h.counts, d.counts, 16ull * n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
     return LA3DM_OK;
 }

@@ -649,6 +649,7 @@ void BGKOctoMap::sync_mirror() const {
         it->second->load_nodes(&A[(size_t)b * npb], &B[(size_t)b * npb], &S[(size_t)b * npb], npb);
     }
     mirror_dirty = false;
+    ++mirror_sync_count;
 }
 
 std::vector<float> BGKOctoMap::device_training_data() const {
@@ -688,6 +689,87 @@ void BGKOctoMap::search_many(const float *xyz, size_t n, uint8_t *exists, float 
         A[i] = nd.m_A;
         B[i] = nd.m_B;
         state[i] = (uint8_t)nd.get_state();
+    }
+}
+
+// The reference leaves this loop to its clients (a planner walks a RayCaster until it meets an OCCUPIED node); what is
+// added is the covering leaf — after prune() the raw finest-layer node of a collapsed region reads PRUNED — and the
+// batch.  The host form below is the definition; the device kernel (csrc/devmap_raycast.h) reproduces it bit for bit.
+void BGKOctoMap::raycast_many(const float *rays6, size_t n, uint32_t stop_mask, uint32_t max_steps,
+                              const la3dm_raycast_out &out) const {
+    bind();
+    if (max_steps == 0 || max_steps > LA3DM_RAY_MAX_STEPS)
+        throw std::invalid_argument("BGKOctoMap::raycast_many: max_steps must be 1 ... 2^20");
+    if (n > 0xFFFFFFFFull) throw std::invalid_argument("BGKOctoMap::raycast_many: more than 2^32 - 1 rays");
+    if (n == 0) return;
+    if (rays6 == nullptr || out.steps == nullptr || out.flags == nullptr)
+        throw std::invalid_argument("BGKOctoMap::raycast_many: rays, steps and flags must not be NULL");
+    if (dmap != nullptr) {
+        if (la3dm_devmap_raycast_host(dmap, rays6, (uint32_t)n, stop_mask, max_steps, &out) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::raycast_many: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const OcTreeNode dflt;
+    const unsigned dl = block_depth - 1u;
+    for (size_t r = 0; r < n; ++r) {
+        const float *q = rays6 + 6 * r;
+        uint32_t steps = 0, counts[4] = {0, 0, 0, 0};
+        uint8_t flags = 0, cls = LA3DM_RAY_MISSING, leaf_depth = 255;
+        point3f p;
+        BlockHashKey bk = 0;
+        OcTreeHashKey nk = 0;
+        float A = dflt.m_A, B = dflt.m_B;
+        bool ok = true;  // refused before any (int) conversion: (int)(x / resolution) is undefined out there
+        for (int a = 0; a < 6; ++a) ok &= std::fabs(q[a] / resolution) < 1073741824.0f;   // false for NaN and inf
+        if (!ok) {
+            flags = LA3DM_RAY_INVALID;
+        } else {
+            RayCaster rc(this, point3f(q[0], q[1], q[2]), point3f(q[3], q[4], q[5]));
+            while (!rc.end()) {
+                if (steps == max_steps) {
+                    flags |= LA3DM_RAY_TRUNCATED;
+                    break;
+                }
+                OcTreeNode nd;
+                const bool valid = rc.next(p, nd, bk, nk);
+                ++steps;
+                if (valid) {
+                    const Block *b = block_arr.find(bk)->second;
+                    unsigned d = dl, i = (unsigned)(nk & 0xFFFF);
+                    while (d > 0 && b->slab[layer_base(d) + i].state == State::PRUNED) {
+                        --d;
+                        i >>= 3;
+                    }
+                    const OcTreeNode &leaf = b->slab[layer_base(d) + i];
+                    cls = (uint8_t)leaf.state;
+                    leaf_depth = (uint8_t)d;
+                    A = leaf.m_A;
+                    B = leaf.m_B;
+                } else {
+                    cls = LA3DM_RAY_MISSING;
+                    leaf_depth = 255;
+                    A = dflt.m_A;
+                    B = dflt.m_B;
+                }
+                ++counts[cls < 4 ? cls : 2];   // (a BGK-LV map's UNCERTAIN leaves count with UNKNOWN)
+                if (stop_mask & (1u << cls)) {
+                    flags |= LA3DM_RAY_HIT;
+                    break;
+                }
+            }
+        }
+        out.steps[r] = steps;
+        out.flags[r] = flags;
+        if (out.p)
+            for (unsigned a = 0; a < 3; ++a) out.p[3 * r + a] = p(a);
+        if (out.block_key) out.block_key[r] = bk;
+        if (out.node_key) out.node_key[r] = nk;
+        if (out.cls) out.cls[r] = cls;
+        if (out.leaf_depth) out.leaf_depth[r] = leaf_depth;
+        if (out.A) out.A[r] = A;
+        if (out.B) out.B[r] = B;
+        if (out.counts)
+            for (unsigned c = 0; c < 4; ++c) out.counts[4 * r + c] = counts[c];
     }
 }
 

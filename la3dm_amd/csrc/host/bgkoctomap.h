@@ -412,6 +412,16 @@ public:
     /// search(x, y, z) for n points at once (packed xyz).  In device-resident mode the answers come straight from the
     /// device pool (no mirror refresh); otherwise from the host blocks.  exists[i] = the block exists.
     void search_many(const float *xyz, size_t n, uint8_t *exists, float *A, float *B, uint8_t *state) const;
+    /// The client loop over a RayCaster, for n segments at once (rays6: start xyz, end xyz per ray).  Per ray: walk with
+    /// next() until the walk ends, `max_steps` rows were produced (flags |= LA3DM_RAY_TRUNCATED) or a row's class is in
+    /// `stop_mask` (flags |= LA3DM_RAY_HIT; bit c of the mask = class c).  The class of a row is the state of the COVERING
+    /// LEAF of its voxel — after prune() the eight children of a collapsed group read PRUNED and the answer lives in an
+    /// ancestor — or LA3DM_RAY_MISSING where the block does not exist.  out (include/la3dm_hip.h): the last row, the number
+    /// of rows and the rows per class.  A device-resident map answers from the device pool (no mirror refresh); a
+    /// host-mode map runs this very loop over its own RayCaster.  Both give the same bits.
+    void raycast_many(const float *rays6, size_t n, uint32_t stop_mask, uint32_t max_steps, const la3dm_raycast_out &out) const;
+    /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
+    uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {
         bind();
         sync_mirror();
@@ -472,6 +482,7 @@ protected:
     la3dm_ctx *ctx;
     la3dm_devmap *dmap = nullptr;
     mutable bool mirror_dirty = false;
+    mutable uint64_t mirror_sync_count = 0;
     la3dm_params create_params;   // what the context was created with (lut_xyz is re-pointed on use)
     void create_context();        // la3dm_create + the device-resident pool from create_params and the current statics
     void reconfigure(float resolution, unsigned short depth);

@@ -351,6 +351,16 @@ int la3dm_map_search_many(const la3dm_map *m, const float *xyz, uint64_t n, uint
     GUARD(m->map->search_many(xyz, (size_t)n, exists, A, B, state); return 0;)
 }
 
+int la3dm_map_raycast_many(const la3dm_map *m, const float *rays6, uint64_t n, uint32_t stop_mask, uint32_t max_steps,
+                           const la3dm_raycast_out *out) {
+    GUARD(
+        if (out == nullptr) throw std::invalid_argument("la3dm_map_raycast_many: out must not be NULL");
+        m->map->raycast_many(rays6, (size_t)n, stop_mask, max_steps, *out);
+        return 0;)
+}
+
+uint64_t la3dm_map_mirror_syncs(const la3dm_map *m) { return m->map->mirror_syncs(); }
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);
