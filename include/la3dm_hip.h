@@ -427,6 +427,60 @@ int la3dm_devmap_raycast_host(la3dm_devmap *dm, const float *rays6, uint32_t n, 
 /* device pointers (rays and outputs already in HBM on the map's device); returns when the results are complete */
 int la3dm_devmap_raycast_device(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
                                 const la3dm_raycast_out *d_out);
+/* Dense region reads on the device pool: an axis-aligned box of voxels as arrays (box), and the same box reduced along
+ * z per (x, y) column (columns).  The region: lo[3] (a world point) and dims[3] = (nx, ny, nz), each >= 1.
+ *   Anchor.  Voxel (0, 0, 0) is the voxel that holds lo the way the RayCaster resolves its start point: per axis the block
+ *     field b = (int64)(lo / block_size + 524288.5) in double (block_to_hash_key) and the cell
+ *     c = clamp((int)((lo - (b - 524288) * block_size) / resolution + lim / 2), 0, lim - 1) in float (Block::get_index,
+ *     truncation), lim = 2^(block_depth - 1).  These are the only floating-point operations of the query.
+ *   Lattice.  With the global index g0 = b * lim + c per axis, voxel (i, j, k) has the global index g = g0 + (i, j, k):
+ *     block field g / lim, cell g % lim, block key (bx << 40) | (by << 20) | bz, finest-layer node as Block::get_node
+ *     builds it (child bit 4 = +x, 2 = +y, 1 = +z per level).  Integers only.  The region need not be aligned to blocks.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written): a non-finite lo or
+ *     |lo / resolution| >= 2^30, a zero dimension, a region whose block fields leave [0, 2^20), more than
+ *     LA3DM_BOX_MAX_CELLS voxels (box), more than 2^30 columns or nz > LA3DM_COLUMNS_MAX_NZ (columns), a NULL lo, dims,
+ *     out or mandatory output.  The limits are checked before any buffer is touched.
+ *   info (optional, host memory in both forms): the anchor's block key and cell, and origin = the centre of voxel
+ *     (0, 0, 0) as Block::get_point gives it (LUT entry + block centre, whether or not the block exists).  The centre of
+ *     voxel (i, j, k) is origin + (i, j, k) * resolution up to fp32 rounding.
+ * box: voxel (i, j, k) at index (i * ny + j) * nz + k (C order of shape (nx, ny, nz)).  cls (mandatory) = state of the
+ *   COVERING LEAF as in raycast_many: FREE 0, OCCUPIED 1, UNKNOWN 2, LA3DM_RAY_MISSING 3 where the block does not exist,
+ *   4 for an UNCERTAIN leaf of a BGK-LV map; leaf_depth = its layer, 255 for a missing block; A, B = its node values
+ *   (m_ivar / ivar on a GP map), the map's default node for a missing block.  An empty map answers all-MISSING without a
+ *   launch.
+ * columns: column (i, j) at index i * ny + j, over k = 0 ... nz - 1 of the same lattice.  counts (mandatory, 4 per
+ *   column): voxels of class FREE, OCCUPIED, UNKNOWN (+ UNCERTAIN), MISSING — they sum to nz; low_occ / top_occ: smallest /
+ *   largest k whose class is OCCUPIED, -1 when there is none.  columns(lo, dims) is the reduction of box(lo, dims).cls
+ *   along its last axis; it reads the pool itself and allocates nothing that grows with nx * ny * nz.
+ * The results are bit-identical to the host form (BGKOctoMap::box / columns on a host-mode map). */
+#define LA3DM_BOX_MAX_CELLS (1u << 30)
+#define LA3DM_COLUMNS_MAX_NZ (1u << 16)
+typedef struct la3dm_region_info {
+    int64_t block_key;   /* block of voxel (0, 0, 0) */
+    int32_t cell[3];     /* its cell inside that block */
+    float origin[3];     /* its centre */
+} la3dm_region_info;
+typedef struct la3dm_box_out {
+    uint8_t *cls;        /* [nx ny nz] */
+    uint8_t *leaf_depth; /* [nx ny nz] or NULL */
+    float *A, *B;        /* [nx ny nz] or NULL */
+} la3dm_box_out;
+typedef struct la3dm_columns_out {
+    uint32_t *counts;    /* [4 nx ny] FREE, OCCUPIED, UNKNOWN, MISSING */
+    int32_t *low_occ;    /* [nx ny] or NULL */
+    int32_t *top_occ;    /* [nx ny] or NULL */
+} la3dm_columns_out;
+/* host pointers: one launch, download, synchronise — on the map's stream */
+int la3dm_devmap_box_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out,
+                          la3dm_region_info *info);
+int la3dm_devmap_columns_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
+                              la3dm_region_info *info);
+/* device pointers (outputs already in HBM on the map's device; lo3, dims3 and info stay host-side); return when the
+ * results are complete */
+int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *d_out,
+                            la3dm_region_info *info);
+int la3dm_devmap_columns_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *d_out,
+                                la3dm_region_info *info);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

@@ -118,6 +118,18 @@ int la3dm_map_search_many(const la3dm_map *m, const float *xyz, uint64_t n, uint
  * the results are bit-identical. */
 int la3dm_map_raycast_many(const la3dm_map *m, const float *rays6, uint64_t n, uint32_t stop_mask, uint32_t max_steps,
                            const la3dm_raycast_out *out);
+/* BGKOctoMap::box / columns: the voxels of an axis-aligned box as dense arrays, and the same box reduced along z per
+ * (x, y) column.  lo3: a world point inside voxel (0, 0, 0) of the region; dims3 = (nx, ny, nz), each >= 1; voxel (i, j, k)
+ * is i, j, k cells of the finest-layer lattice further on, across block borders.  box: index (i * ny + j) * nz + k, the
+ * state of the voxel's covering leaf (LA3DM_RAY_MISSING where the block does not exist), its layer and node values.
+ * columns: index i * ny + j, voxels per class FREE, OCCUPIED, UNKNOWN, MISSING over k and the lowest / highest OCCUPIED k
+ * (-1: none).  info (may be NULL): block key and cell of voxel (0, 0, 0) and its centre; the other centres are
+ * origin + (i, j, k) * resolution.  Contract, limits and the output structs: include/la3dm_hip.h
+ * (la3dm_devmap_box_host).  Device-resident maps answer from the device pool without a mirror refresh, host-mode maps loop
+ * over the host blocks; the results are bit-identical. */
+int la3dm_map_box(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out, la3dm_region_info *info);
+int la3dm_map_columns(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
+                      la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

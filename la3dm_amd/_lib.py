@@ -77,6 +77,18 @@ class RaycastOut(C.Structure):   # la3dm_raycast_out (include/la3dm_hip.h)
                                           "counts")]
 
 
+class BoxOut(C.Structure):       # la3dm_box_out
+    _fields_ = [(k, C.c_void_p) for k in ("cls", "leaf_depth", "A", "B")]
+
+
+class ColumnsOut(C.Structure):   # la3dm_columns_out
+    _fields_ = [(k, C.c_void_p) for k in ("counts", "low_occ", "top_occ")]
+
+
+class RegionInfo(C.Structure):   # la3dm_region_info
+    _fields_ = [("block_key", C.c_int64), ("cell", C.c_int32 * 3), ("origin", C.c_float * 3)]
+
+
 HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_destroy", "la3dm_last_error",
                "la3dm_set_option", "la3dm_get_option", "la3dm_bgk_scan_host", "la3dm_bgk_scan_device", "la3dm_gp_scan_host",
                "la3dm_gp_scan_device", "la3dm_bgklv_scan_host", "la3dm_bgklv_scan_device", "la3dm_kernel_times", "la3dm_diag_eval", "la3dm_diag_sweep",
@@ -88,7 +100,8 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_insert_training_data_host", "la3dm_devmap_set_shard", "la3dm_devmap_wait_event",
                "la3dm_devmap_lv_stats_get", "la3dm_devmap_lv_set_original_size", "la3dm_devmap_lv_training",
                "la3dm_devmap_diag_scan", "la3dm_devmap_diag_sort", "la3dm_devmap_raycast_host",
-               "la3dm_devmap_raycast_device"]
+               "la3dm_devmap_raycast_device", "la3dm_devmap_box_host", "la3dm_devmap_box_device",
+               "la3dm_devmap_columns_host", "la3dm_devmap_columns_device"]
 MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
                "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
                "la3dm_map_insert_training_data", "la3dm_map_prepare", "la3dm_map_prepare_training_data",
@@ -100,7 +113,7 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_block_grid", "la3dm_map_create_l", "la3dm_map_l_training",
                "la3dm_map_search_many", "la3dm_map_export_cells", "la3dm_map_set_shard", "la3dm_map_resolution",
                "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth",
-               "la3dm_map_raycast_many", "la3dm_map_mirror_syncs"]
+               "la3dm_map_raycast_many", "la3dm_map_mirror_syncs", "la3dm_map_box", "la3dm_map_columns"]
 
 _hip = None
 _map = None
@@ -174,6 +187,11 @@ def hip():
         L.la3dm_devmap_raycast_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
         L.la3dm_devmap_raycast_device.restype = C.c_int
         L.la3dm_devmap_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
+        for name, out in (("box", BoxOut), ("columns", ColumnsOut)):
+            for form in ("host", "device"):
+                f = getattr(L, f"la3dm_devmap_{name}_{form}")
+                f.restype = C.c_int
+                f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(out), C.POINTER(RegionInfo)]
         L.la3dm_devmap_training_data.restype = C.c_int
         L.la3dm_devmap_training_data.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         _hip = L
@@ -216,6 +234,10 @@ def maplib():
                                              C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         M.la3dm_map_raycast_many.restype = C.c_int
         M.la3dm_map_raycast_many.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
+        M.la3dm_map_box.restype = C.c_int
+        M.la3dm_map_box.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BoxOut), C.POINTER(RegionInfo)]
+        M.la3dm_map_columns.restype = C.c_int
+        M.la3dm_map_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ColumnsOut), C.POINTER(RegionInfo)]
         M.la3dm_map_mirror_syncs.restype = C.c_uint64
         M.la3dm_map_mirror_syncs.argtypes = [C.c_void_p]
         M.la3dm_map_raycast.restype = C.c_uint64

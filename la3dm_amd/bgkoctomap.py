@@ -211,6 +211,59 @@ class BGKOctoMap:
         self._chk(self._M.la3dm_map_raycast_many(self._h, rays, n, mask, int(max_steps), C.byref(o)))
         return out
 
+    @staticmethod
+    def _region(lo, dims, limit):
+        """(lo, dims as C arrays, dims, cells to allocate): a request over `limit` cells (or with a zero dimension) gets
+        one-element arrays — the call refuses it before it looks at a buffer, and its text is the one that is raised"""
+        lo3 = np.ascontiguousarray(lo, np.float32).reshape(-1)
+        d = [int(v) for v in np.asarray(dims).reshape(-1)]
+        if lo3.shape != (3,) or len(d) != 3 or min(d) < 0 or max(d) >= 2 ** 32:
+            raise ValueError("lo must be 3 floats and dims 3 integers in [0, 2^32)")
+        return lo3, np.array(d, np.uint32), d, limit(d)
+
+    @staticmethod
+    def _region_info(info):
+        return dict(origin=np.array(info.origin[:], np.float32), block_key=int(info.block_key),
+                    cell=np.array(info.cell[:], np.int32))
+
+    def box(self, lo, dims, fields=("cls", "leaf_depth", "A", "B")):
+        """The voxels of an axis-aligned box as dense arrays of shape dims = (nx, ny, nz).  Voxel (0, 0, 0) is the voxel
+        that holds the world point `lo` (resolved as the RayCaster resolves its start point); voxel (i, j, k) lies i, j, k
+        cells of the finest-layer lattice further along x, y, z, across block borders.  Per voxel: cls = the state of
+        its COVERING LEAF (FREE, OCCUPIED, UNKNOWN, MISSING where the block does not exist, 4 = UNCERTAIN on a BGK-LV
+        map; never PRUNED — after prune() the raw node of a collapsed region reads PRUNED and search() reports that),
+        leaf_depth = that leaf's layer (255: missing), A / B = its node values (m_ivar / ivar on a GP map; the default
+        node: missing).  `fields` names the arrays wanted; cls always comes.  Also returned: origin = the centre of
+        voxel (0, 0, 0) (the others: origin + (i, j, k) * resolution), block_key and cell of that voxel.  At most 2^30
+        voxels.  A device-resident map runs one HIP launch on the device pool (no host mirror refresh); a host-mode map
+        loops over its host blocks, with bit-identical results."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 2 ** 30 else 1)(d[0] * d[1] * d[2]))
+        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
+        unknown = set(fields) - {"cls", "leaf_depth", "A", "B"}
+        if unknown:
+            raise ValueError(f"box: unknown fields {sorted(unknown)}")
+        out = {k: np.empty(shape, np.float32 if k in "AB" else np.uint8) for k in ("cls", "leaf_depth", "A", "B")
+               if k == "cls" or k in fields}
+        o = _lib.BoxOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.BoxOut._fields_])
+        info = _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_box(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(o), C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
+    def columns(self, lo, dims):
+        """The box of box(lo, dims) reduced along z, without building it: per (x, y) column counts (nx, ny, 4) = voxels of
+        class FREE, OCCUPIED, UNKNOWN (with UNCERTAIN), MISSING over k = 0 .. nz - 1 (they sum to nz), low_occ / top_occ
+        (nx, ny) = the smallest / largest k whose class is OCCUPIED, -1 when there is none; plus origin, block_key, cell
+        as box() returns them.  The 2-D occupancy grid / height map of a height band.  At most 2^30 columns, nz <= 2^16."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 2 ** 30 and d[2] <= 2 ** 16 else 1)(d[0] * d[1]))
+        shape = (d[0], d[1]) if n == d[0] * d[1] else (n,)
+        out = dict(counts=np.empty(shape + (4,), np.uint32), low_occ=np.empty(shape, np.int32), top_occ=np.empty(shape, np.int32))
+        o = _lib.ColumnsOut(*[out[k].ctypes.data for k, _ in _lib.ColumnsOut._fields_])
+        info = _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_columns(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(o), C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
     def mirror_syncs(self):
         """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
         return int(self._M.la3dm_map_mirror_syncs(self._h))

@@ -24,6 +24,7 @@
 #include "devmap_depth3.h"
 #include "devmap_grid_keys.h"
 #include "devmap_raycast.h"
+#include "devmap_region.h"
 
 using namespace la3dm_dev;
 
@@ -2369,6 +2370,244 @@ int la3dm_devmap_raycast_host(la3dm_devmap *dm, const float *rays6, uint32_t n, 
     if (h.B) DM_TRY(hipMemcpyAsync(h.B, d.B, 4ull * n, hipMemcpyDeviceToHost, st));
     if (h.counts) DM_TRY(hipMemcpyAsync(h.counts, d.counts, 16ull * n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+// ---- dense region reads (devmap_region.h) --------------------------------------------------------------------
+namespace {
+struct RegionGeom {
+    uint32_t g0[3], dims[3];
+    uint64_t total;   // box: voxels; columns: columns
+    la3dm_region_info info;
+};
+}  // namespace
+
+// The region's checks, in the order of the contract (limits before any buffer is looked at), and its anchor: the only
+// floating-point work of the query, done here on the host for both kernels (host twin: BGKOctoMap::region_anchor).
+static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, bool columns, bool has_out, bool has_mandatory,
+                          const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    const std::string w(who);
+    if (!lo3) return dm_fail(dm, LA3DM_ERR_ARG, w + ": lo is NULL");
+    if (!dims3) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims is NULL");
+    const float res = dm->ctx->p.resolution, bs = dm->block_size;
+    const int dl = (int)dm->depth - 1, lim = 1 << dl;
+    for (int k = 0; k < 3; ++k)
+        if (!(fabsf(lo3[k] / res) < 1073741824.0f))   // false for NaN and inf
+            return dm_fail(dm, LA3DM_ERR_ARG, w + ": lo must be finite with |lo / resolution| < 2^30");
+    for (int k = 0; k < 3; ++k) {
+        if (dims3[k] == 0) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims must be >= 1 on every axis");
+        g.dims[k] = dims3[k];
+    }
+    const uint64_t ncol = (uint64_t)dims3[0] * dims3[1];
+    if (columns) {
+        if (ncol > (1ull << 30)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than 2^30 columns");
+        if (dims3[2] > LA3DM_COLUMNS_MAX_NZ) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)");
+        g.total = ncol;
+    } else {
+        if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS)
+            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
+        g.total = ncol * dims3[2];
+    }
+    long long key = 0;
+    uint32_t cell[3];
+    for (int k = 0; k < 3; ++k) {
+        const long long b = (long long)((double)lo3[k] / (double)bs + 524288.5);   // block_to_hash_key, one axis
+        if (b < 0 || b >= (1ll << 20)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": lo: the block field leaves [0, 2^20)");
+        const float center = (float)(b - 524288) * bs;                             // hash_key_to_block
+        const int t = (int)((lo3[k] - center) / res + (float)(lim / 2));           // Block::get_index: truncation, clamped
+        const int c = std::max(0, std::min(t, lim - 1));
+        const long long first = b * lim + c, last = first + (long long)dims3[k] - 1;
+        if (last / lim >= (1ll << 20)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: the region's block fields leave [0, 2^20)");
+        g.g0[k] = (uint32_t)first;
+        cell[k] = (uint32_t)c;
+        g.info.cell[k] = c;
+        g.info.origin[k] = center;
+        key = (key << 20) | b;
+    }
+    g.info.block_key = key;
+    if (!has_out) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out is NULL");
+    if (!has_mandatory) return dm_fail(dm, LA3DM_ERR_ARG, w + (columns ? ": out->counts must not be NULL" : ": out->cls must not be NULL"));
+    // origin = Block::get_point of the anchor cell: the LUT entry of its finest-layer node + the block centre
+    uint32_t index = 0;
+    for (int level = dl - 1; level >= 0; --level)
+        index = index * 8u + ((((cell[0] >> level) & 1u) << 2) | (((cell[1] >> level) & 1u) << 1) | ((cell[2] >> level) & 1u));
+    const uint32_t entry = (0x249249u & ((1u << (3u * (uint32_t)dl)) - 1u)) + index;
+    if (entry >= dm->ctx->lut_count) return dm_fail(dm, LA3DM_ERR_ARG, w + ": the context's voxel LUT does not reach the finest layer");
+    float4 o;
+    DM_TRY(hipSetDevice(dm->ctx->device));
+    DM_TRY(hipMemcpyAsync(&o, dm->ctx->d_lut + entry, sizeof(o), hipMemcpyDeviceToHost, dm->ctx->stream));
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    g.info.origin[0] = o.x + g.info.origin[0];
+    g.info.origin[1] = o.y + g.info.origin[1];
+    g.info.origin[2] = o.z + g.info.origin[2];
+    return LA3DM_OK;
+}
+
+static RegionArgs region_args(la3dm_devmap *dm, const RegionGeom &g) {
+    RegionArgs a;
+    memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 3; ++k) a.g0[k] = g.g0[k];
+    a.nx = g.dims[0];
+    a.ny = g.dims[1];
+    a.nz = g.dims[2];
+    a.total = (uint32_t)g.total;
+    a.tab_key = dm->tab_key;
+    a.tab_val = dm->tab_val;
+    a.mask = dm->tab_cap - 1;
+    a.A = dm->A;
+    a.B = dm->B;
+    a.S = dm->S;
+    a.npb = dm->npb;
+    a.depth = dm->depth;
+    a.a0 = dm->init_A;
+    a.b0 = dm->init_B;
+    return a;
+}
+
+static void box_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_box_out &o) {
+    RegionArgs a = region_args(dm, g);
+    a.cls = o.cls;
+    a.leaf_depth = o.leaf_depth;
+    a.oA = o.A;
+    a.oB = o.B;
+    // four voxels per thread (word / float4 stores) when every output is aligned for them, else one
+    const bool vec = ((uintptr_t)o.cls & 3u) == 0 && ((uintptr_t)o.leaf_depth & 3u) == 0 && ((uintptr_t)o.A & 15u) == 0 && ((uintptr_t)o.B & 15u) == 0;
+    if (vec)
+        hipLaunchKernelGGL(dm_box<4>, dim3(cdiv(cdiv(a.total, 4), 256)), dim3(256), 0, dm->ctx->stream, a);
+    else
+        hipLaunchKernelGGL(dm_box<1>, dim3(cdiv(a.total, 256)), dim3(256), 0, dm->ctx->stream, a);
+}
+
+static void columns_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_columns_out &o) {
+    RegionArgs a = region_args(dm, g);
+    a.counts = o.counts;
+    a.low_occ = o.low_occ;
+    a.top_occ = o.top_occ;
+    a.counts_vec = ((uintptr_t)o.counts & 15u) == 0 ? 1u : 0u;
+    hipLaunchKernelGGL(dm_columns, dim3(cdiv(a.total, 256)), dim3(256), 0, dm->ctx->stream, a);
+}
+
+int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *d_out,
+                            la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = region_resolve(dm, lo3, dims3, false, d_out != nullptr, d_out && d_out->cls, "la3dm_devmap_box_device", g);
+    if (rc != LA3DM_OK) return rc;
+    hipStream_t st = dm->ctx->stream;
+    const la3dm_box_out &o = *d_out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: every block is missing, nothing is launched (the constant answer is written by memsets)
+        DM_TRY(hipMemsetAsync(o.cls, (int)LA3DM_RAY_MISSING, n, st));
+        if (o.leaf_depth) DM_TRY(hipMemsetAsync(o.leaf_depth, 255, n, st));
+        uint32_t ab[2];
+        memcpy(&ab[0], &dm->init_A, 4);
+        memcpy(&ab[1], &dm->init_B, 4);
+        if (o.A) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.A, (int)ab[0], n, st));
+        if (o.B) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.B, (int)ab[1], n, st));
+    } else {
+        box_launch(dm, g, o);
+        DM_TRY(hipGetLastError());
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_box_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out,
+                          la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = region_resolve(dm, lo3, dims3, false, out != nullptr, out && out->cls, "la3dm_devmap_box_host", g);
+    if (rc != LA3DM_OK) return rc;
+    const la3dm_box_out &h = *out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: every block is missing, nothing is launched
+        memset(h.cls, (int)LA3DM_RAY_MISSING, n);
+        if (h.leaf_depth) memset(h.leaf_depth, 255, n);
+        if (h.A) std::fill(h.A, h.A + n, dm->init_A);
+        if (h.B) std::fill(h.B, h.B + n, dm->init_B);
+        if (info) *info = g.info;
+        return LA3DM_OK;
+    }
+    hipStream_t st = dm->ctx->stream;
+    // results in `q_out`, widest type first: every array aligned for the four-voxel stores
+    const size_t n16 = (n + 15) & ~(size_t)15;
+    DM_RESERVE(dm->q_out, 10ull * n16 + 64);
+    la3dm_box_out d;
+    d.A = (float *)dm->q_out.ptr;
+    d.B = d.A + n16;
+    d.cls = (uint8_t *)(d.B + n16);
+    d.leaf_depth = d.cls + n16;
+    if (!h.leaf_depth) d.leaf_depth = nullptr;
+    if (!h.A) d.A = nullptr;
+    if (!h.B) d.B = nullptr;
+    box_launch(dm, g, d);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipMemcpyAsync(h.cls, d.cls, n, hipMemcpyDeviceToHost, st));
+    if (h.leaf_depth) DM_TRY(hipMemcpyAsync(h.leaf_depth, d.leaf_depth, n, hipMemcpyDeviceToHost, st));
+    if (h.A) DM_TRY(hipMemcpyAsync(h.A, d.A, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.B) DM_TRY(hipMemcpyAsync(h.B, d.B, 4ull * n, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_columns_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *d_out,
+                                la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = region_resolve(dm, lo3, dims3, true, d_out != nullptr, d_out && d_out->counts, "la3dm_devmap_columns_device", g);
+    if (rc != LA3DM_OK) return rc;
+    hipStream_t st = dm->ctx->stream;
+    const la3dm_columns_out &o = *d_out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: {0, 0, 0, nz} per column, no occupied voxel; nothing is launched
+        DM_TRY(hipMemsetAsync(o.counts, 0, 16ull * n, st));
+        for (uint32_t byte = 0; byte < 3; ++byte)   // counts[3] = nz <= 2^16, byte by byte down the column of rows
+            if ((g.dims[2] >> (8 * byte)) & 0xFFu)
+                DM_TRY(hipMemset2DAsync((uint8_t *)(o.counts + 3) + byte, 16, (int)((g.dims[2] >> (8 * byte)) & 0xFFu), 1, n, st));
+        if (o.low_occ) DM_TRY(hipMemsetAsync(o.low_occ, 0xFF, 4ull * n, st));
+        if (o.top_occ) DM_TRY(hipMemsetAsync(o.top_occ, 0xFF, 4ull * n, st));
+    } else {
+        columns_launch(dm, g, o);
+        DM_TRY(hipGetLastError());
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_columns_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
+                              la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = region_resolve(dm, lo3, dims3, true, out != nullptr, out && out->counts, "la3dm_devmap_columns_host", g);
+    if (rc != LA3DM_OK) return rc;
+    const la3dm_columns_out &h = *out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: every block is missing, nothing is launched
+        for (size_t c = 0; c < n; ++c) {
+            h.counts[4 * c] = h.counts[4 * c + 1] = h.counts[4 * c + 2] = 0;
+            h.counts[4 * c + 3] = g.dims[2];
+            if (h.low_occ) h.low_occ[c] = -1;
+            if (h.top_occ) h.top_occ[c] = -1;
+        }
+        if (info) *info = g.info;
+        return LA3DM_OK;
+    }
+    hipStream_t st = dm->ctx->stream;
+    DM_RESERVE(dm->q_out, 24ull * n + 64);   // per column, nothing that grows with nz
+    la3dm_columns_out d;
+    d.counts = (uint32_t *)dm->q_out.ptr;
+    d.low_occ = (int32_t *)(d.counts + 4 * n);
+    d.top_occ = d.low_occ + n;
+    if (!h.low_occ) d.low_occ = nullptr;
+    if (!h.top_occ) d.top_occ = nullptr;
+    columns_launch(dm, g, d);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipMemcpyAsync(h.counts, d.counts, 16ull * n, hipMemcpyDeviceToHost, st));
+    if (h.low_occ) DM_TRY(hipMemcpyAsync(h.low_occ, d.low_occ, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.top_occ) DM_TRY(hipMemcpyAsync(h.top_occ, d.top_occ, 4ull * n, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
     return LA3DM_OK;
 }
 

@@ -773,6 +773,149 @@ void BGKOctoMap::raycast_many(const float *rays6, size_t n, uint32_t stop_mask, 
     }
 }
 
+// ---- dense region reads: box / columns.  The host forms below are the definition; the device kernels
+// (csrc/devmap_region.h) reproduce them bit for bit.
+void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, bool columns, bool has_mandatory, const char *who,
+                               uint32_t g0[3], la3dm_region_info &info) const {
+    const std::string w = std::string("BGKOctoMap::") + who;
+    if (lo3 == nullptr) throw std::invalid_argument(w + ": lo is NULL");
+    if (dims3 == nullptr) throw std::invalid_argument(w + ": dims is NULL");
+    for (int k = 0; k < 3; ++k)   // refused before any (int) conversion; false for NaN and inf
+        if (!(std::fabs(lo3[k] / resolution) < 1073741824.0f))
+            throw std::invalid_argument(w + ": lo must be finite with |lo / resolution| < 2^30");
+    for (int k = 0; k < 3; ++k)
+        if (dims3[k] == 0) throw std::invalid_argument(w + ": dims must be >= 1 on every axis");
+    const uint64_t ncol = (uint64_t)dims3[0] * dims3[1];
+    if (columns) {
+        if (ncol > (1ull << 30)) throw std::invalid_argument(w + ": dims: more than 2^30 columns");
+        if (dims3[2] > LA3DM_COLUMNS_MAX_NZ) throw std::invalid_argument(w + ": dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)");
+    } else if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS) {
+        throw std::invalid_argument(w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
+    }
+    for (int k = 0; k < 3; ++k) {   // (a key only holds fields that fit it: test them before one is built)
+        const long long f = (long long)(lo3[k] / (double)block_size + 524288.5);
+        if (f < 0 || f >= (1ll << 20)) throw std::invalid_argument(w + ": lo: the block field leaves [0, 2^20)");
+    }
+    const BlockHashKey key = block_to_hash_key(lo3[0], lo3[1], lo3[2]);
+    const long long lim = 1ll << (block_depth - 1);
+    const long long b[3] = {(long long)(key >> 40), (long long)((key >> 20) & 0xFFFFF), (long long)(key & 0xFFFFF)};
+    const Block anchor(hash_key_to_block(key));
+    unsigned short c[3];
+    anchor.get_index(point3f(lo3[0], lo3[1], lo3[2]), c[0], c[1], c[2]);
+    for (int k = 0; k < 3; ++k) {
+        const long long first = b[k] * lim + c[k], last = first + (long long)dims3[k] - 1;
+        if (last / lim >= (1ll << 20)) throw std::invalid_argument(w + ": dims: the region's block fields leave [0, 2^20)");
+        g0[k] = (uint32_t)first;
+        info.cell[k] = c[k];
+    }
+    info.block_key = key;
+    const point3f o = anchor.get_point(c[0], c[1], c[2]);
+    info.origin[0] = o.x();
+    info.origin[1] = o.y();
+    info.origin[2] = o.z();
+    if (!has_mandatory) throw std::invalid_argument(w + (columns ? ": out.counts must not be NULL" : ": out.cls must not be NULL"));
+}
+
+void BGKOctoMap::box(const float *lo3, const uint32_t *dims3, const la3dm_box_out &out, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_box_host(dmap, lo3, dims3, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::box: ") + la3dm_last_error(ctx));
+        return;
+    }
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, false, out.cls != nullptr, "box", g0, inf);
+    if (info) *info = inf;
+    const OcTreeNode dflt;
+    const unsigned dl = block_depth - 1u;
+    const uint32_t cm = (1u << dl) - 1u;
+    const size_t ny = dims3[1], nz = dims3[2];
+    for (uint32_t i = 0; i < dims3[0]; ++i)
+        for (uint32_t j = 0; j < dims3[1]; ++j) {
+            const uint32_t gx = g0[0] + i, gy = g0[1] + j;
+            const Block *b = nullptr;
+            BlockHashKey have = -1;
+            for (uint32_t k = 0; k < dims3[2]; ++k) {
+                const uint32_t gz = g0[2] + k;
+                const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
+                if (key != have) {
+                    auto it = block_arr.find(key);
+                    b = it == block_arr.end() ? nullptr : it->second;
+                    have = key;
+                }
+                const size_t o = ((size_t)i * ny + j) * nz + k;
+                if (b == nullptr) {
+                    out.cls[o] = LA3DM_RAY_MISSING;
+                    if (out.leaf_depth) out.leaf_depth[o] = 255;
+                    if (out.A) out.A[o] = dflt.m_A;
+                    if (out.B) out.B[o] = dflt.m_B;
+                    continue;
+                }
+                unsigned d = dl, n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
+                while (d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED) {
+                    --d;
+                    n >>= 3;
+                }
+                const OcTreeNode &leaf = b->slab[layer_base(d) + n];
+                out.cls[o] = (uint8_t)leaf.state;
+                if (out.leaf_depth) out.leaf_depth[o] = (uint8_t)d;
+                if (out.A) out.A[o] = leaf.m_A;
+                if (out.B) out.B[o] = leaf.m_B;
+            }
+        }
+}
+
+void BGKOctoMap::columns(const float *lo3, const uint32_t *dims3, const la3dm_columns_out &out, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_columns_host(dmap, lo3, dims3, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::columns: ") + la3dm_last_error(ctx));
+        return;
+    }
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, true, out.counts != nullptr, "columns", g0, inf);
+    if (info) *info = inf;
+    const unsigned dl = block_depth - 1u;
+    const uint32_t cm = (1u << dl) - 1u;
+    for (uint32_t i = 0; i < dims3[0]; ++i)
+        for (uint32_t j = 0; j < dims3[1]; ++j) {
+            const uint32_t gx = g0[0] + i, gy = g0[1] + j;
+            uint32_t counts[4] = {0, 0, 0, 0};
+            int32_t low = -1, top = -1;
+            const Block *b = nullptr;
+            BlockHashKey have = -1;
+            for (uint32_t k = 0; k < dims3[2]; ++k) {
+                const uint32_t gz = g0[2] + k;
+                const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
+                if (key != have) {
+                    auto it = block_arr.find(key);
+                    b = it == block_arr.end() ? nullptr : it->second;
+                    have = key;
+                }
+                unsigned cls = LA3DM_RAY_MISSING;
+                if (b != nullptr) {
+                    unsigned d = dl, n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
+                    while (d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED) {
+                        --d;
+                        n >>= 3;
+                    }
+                    cls = (unsigned)b->slab[layer_base(d) + n].state;
+                }
+                ++counts[cls < 4 ? cls : 2];   // (a BGK-LV map's UNCERTAIN leaves count with UNKNOWN)
+                if (cls == (unsigned)State::OCCUPIED) {
+                    if (low < 0) low = (int32_t)k;
+                    top = (int32_t)k;
+                }
+            }
+            const size_t c = (size_t)i * dims3[1] + j;
+            for (unsigned q = 0; q < 4; ++q) out.counts[4 * c + q] = counts[q];
+            if (out.low_occ) out.low_occ[c] = low;
+            if (out.top_occ) out.top_occ[c] = top;
+        }
+}
+
 namespace {
 // heightMapColor, include/common/markerarray_pub.h:21-76 (s = v = 1)
 void height_map_color(double h, float *rgba) {

@@ -420,6 +420,19 @@ public:
     /// of rows and the rows per class.  A device-resident map answers from the device pool (no mirror refresh); a
     /// host-mode map runs this very loop over its own RayCaster.  Both give the same bits.
     void raycast_many(const float *rays6, size_t n, uint32_t stop_mask, uint32_t max_steps, const la3dm_raycast_out &out) const;
+    /// Dense region reads (contract: include/la3dm_hip.h, la3dm_devmap_box_host).  The region is the nx x ny x nz voxels of
+    /// the finest-layer lattice whose voxel (0, 0, 0) holds `lo` the way the RayCaster resolves its start point
+    /// (block_to_hash_key + Block::get_index); voxel (i, j, k) is the one i, j, k cells further along x, y, z, across
+    /// block borders, in integer arithmetic.  box: per voxel, index (i * ny + j) * nz + k, the state of the COVERING LEAF
+    /// (FREE 0, OCCUPIED 1, UNKNOWN 2, LA3DM_RAY_MISSING where the block does not exist, 4 = UNCERTAIN on a BGK-LV map),
+    /// its layer (255: missing) and its node values (the default node: missing).  columns: per column (i, j), index
+    /// i * ny + j, the voxels per class FREE, OCCUPIED, UNKNOWN (+ UNCERTAIN), MISSING over k, and the smallest / largest k
+    /// whose class is OCCUPIED (-1: none) — the reduction of box's cls along z, computed without the box.  `info` (may
+    /// be null): the anchor's block key and cell and the centre of voxel (0, 0, 0) (Block::get_point).  Bad arguments throw
+    /// std::invalid_argument.  A device-resident map answers from the device pool (no mirror refresh); a host-mode map
+    /// loops over its host blocks: that form is the definition, and both give the same bits.
+    void box(const float *lo3, const uint32_t *dims3, const la3dm_box_out &out, la3dm_region_info *info = nullptr) const;
+    void columns(const float *lo3, const uint32_t *dims3, const la3dm_columns_out &out, la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {
@@ -483,6 +496,9 @@ protected:
     la3dm_devmap *dmap = nullptr;
     mutable bool mirror_dirty = false;
     mutable uint64_t mirror_sync_count = 0;
+    /// checks of a region query in the contract's order + its anchor: global voxel index g0 of voxel (0, 0, 0), info
+    void region_anchor(const float *lo3, const uint32_t *dims3, bool columns, bool has_mandatory, const char *who,
+                       uint32_t g0[3], la3dm_region_info &info) const;
     la3dm_params create_params;   // what the context was created with (lut_xyz is re-pointed on use)
     void create_context();        // la3dm_create + the device-resident pool from create_params and the current statics
     void reconfigure(float resolution, unsigned short depth);

@@ -361,6 +361,21 @@ int la3dm_map_raycast_many(const la3dm_map *m, const float *rays6, uint64_t n, u
 
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m) { return m->map->mirror_syncs(); }
 
+int la3dm_map_box(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out, la3dm_region_info *info) {
+    GUARD(
+        if (out == nullptr) throw std::invalid_argument("la3dm_map_box: out must not be NULL");
+        m->map->box(lo3, dims3, *out, info);
+        return 0;)
+}
+
+int la3dm_map_columns(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
+                      la3dm_region_info *info) {
+    GUARD(
+        if (out == nullptr) throw std::invalid_argument("la3dm_map_columns: out must not be NULL");
+        m->map->columns(lo3, dims3, *out, info);
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);
