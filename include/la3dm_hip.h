@@ -481,6 +481,38 @@ int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *
                             la3dm_region_info *info);
 int la3dm_devmap_columns_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *d_out,
                                 la3dm_region_info *info);
+/* Distance field of a region: the exact Euclidean distance transform of box(lo, dims).  The region (anchor, lattice,
+ * info, index (i * ny + j) * nz + k) is box's.
+ *   Obstacles.  Voxel (i, j, k) is an obstacle when obstacle_mask & (1u << cls) is set, cls being what box reports for
+ *     it (FREE 0, OCCUPIED 1, UNKNOWN 2, MISSING 3, a BGK-LV map's UNCERTAIN 4): the bit convention of raycast_many's
+ *     stop_mask.
+ *   Definition.  D(v) = the minimum over the obstacles o INSIDE THE REGION of |v - o|^2, an integer in voxel units.
+ *     d2[v] = D(v) if D(v) <= radius^2, else LA3DM_DF_FAR (a region without obstacles: FAR everywhere).
+ *     dist[v] = sqrtf((float)d2[v]) * resolution — one correctly rounded fp32 square root, one fp32 multiply — and +inf
+ *     for FAR.  Every finite d2 is below 2^24, hence exact in fp32.
+ *   Obstacles outside the region are not seen: a caller who needs the distances of a region to be true up to `radius`
+ *     pads the region by `radius` voxels on every side.  The distance INSIDE obstacles (to the nearest voxel that is
+ *     none) is the same call with the complementary mask (0x1F & ~obstacle_mask); there is no signed form.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, no buffer touched, no scratch reserved): what box
+ *     refuses for lo and dims; an obstacle_mask of 0 or with bits above 0x1F; a radius of 0 or above
+ *     LA3DM_DF_MAX_RADIUS; more than LA3DM_DF_MAX_CELLS voxels; a NULL out or an out with both arrays NULL.
+ *   An empty map (every voxel MISSING) answers all 0 if the mask holds bit 3 and all FAR / +inf otherwise, without a launch.
+ *   Working storage: 4 bytes per voxel in a grow-only arena of the devmap (released with it), next to the outputs.
+ * The results are bit-identical to the host form (BGKOctoMap::distance_field on a host-mode map). */
+#define LA3DM_DF_FAR        0xFFFFFFFFu
+#define LA3DM_DF_MAX_RADIUS 1024u
+#define LA3DM_DF_MAX_CELLS  (1u << 28)
+typedef struct la3dm_distance_out {
+    uint32_t *d2;   /* [nx ny nz] or NULL */
+    float *dist;    /* [nx ny nz] or NULL; at least one of the two */
+} la3dm_distance_out;
+/* host pointers: the launches, download, synchronise — on the map's stream */
+int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                               uint32_t radius, const la3dm_distance_out *out, la3dm_region_info *info);
+/* device pointers (outputs already in HBM on the map's device, 4-byte aligned; lo3, dims3 and info stay host-side);
+ * returns when the results are complete.  An output array doubles as working storage until the last pass fills it. */
+int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                                 uint32_t radius, const la3dm_distance_out *d_out, la3dm_region_info *info);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

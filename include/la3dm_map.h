@@ -130,6 +130,15 @@ int la3dm_map_raycast_many(const la3dm_map *m, const float *rays6, uint64_t n, u
 int la3dm_map_box(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out, la3dm_region_info *info);
 int la3dm_map_columns(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
                       la3dm_region_info *info);
+/* BGKOctoMap::distance_field: the exact Euclidean distance transform of box's region.  A voxel is an obstacle when
+ * obstacle_mask & (1u << cls) is set (cls as box reports it; the bits of raycast_many's stop_mask); d2 = the squared
+ * distance, an integer in voxel units, to the nearest obstacle INSIDE THE REGION, LA3DM_DF_FAR beyond radius^2 (pad the
+ * region by `radius` where that matters); dist = sqrtf(d2) * resolution, +inf for FAR.  At least one of out->d2, out->dist.
+ * The distance inside obstacles is the call with the complementary mask.  Contract, limits and refusals:
+ * include/la3dm_hip.h (la3dm_devmap_distance_host).  Device-resident maps run the transform on the device pool without a
+ * mirror refresh, host-mode maps on the CPU; the results are bit-identical. */
+int la3dm_map_distance_field(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                             const la3dm_distance_out *out, la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

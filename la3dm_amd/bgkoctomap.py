@@ -14,6 +14,7 @@ FREE, OCCUPIED, UNKNOWN, PRUNED = 0, 1, 2, 3
 # raycast_many: class of a row whose block does not exist (a covering leaf is never PRUNED, so the slot is free), ray flags
 MISSING = 3
 RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
+DF_FAR = 0xFFFFFFFF                 # LA3DM_DF_FAR: beyond the radius of distance_field (dist: +inf)
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
@@ -261,6 +262,37 @@ class BGKOctoMap:
         o = _lib.ColumnsOut(*[out[k].ctypes.data for k, _ in _lib.ColumnsOut._fields_])
         info = _lib.RegionInfo()
         self._chk(self._M.la3dm_map_columns(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(o), C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
+    def distance_field(self, lo, dims, obstacles=("occupied",), radius=32, fields=("d2", "dist")):
+        """The exact Euclidean distance transform of the region of box(lo, dims): per voxel the distance to the nearest
+        obstacle INSIDE THE REGION, an obstacle being a voxel whose class (box's cls) is in `obstacles` — names out of
+        free / occupied / unknown / missing (/ uncertain on a BGK-LV map) or an integer bit mask, as raycast_many's
+        `stop`.  d2 (uint32) = the squared distance in voxel units, an integer, 0 on the obstacles and DF_FAR
+        (0xFFFFFFFF) beyond radius^2 or where the region holds no obstacle; dist (float32) = sqrt(d2) * resolution in
+        metres, +inf for FAR.  radius: 1 .. 1024 voxels.  Obstacles outside the region are not seen: pad the region by
+        `radius` where that matters.  The distance inside obstacles is the call with the complementary classes.
+        `fields` names the arrays wanted (at least one).  Also returned: origin, block_key, cell as box() returns them.
+        At most 2^28 voxels.  A device-resident map runs the transform on the device pool (no host mirror refresh); a
+        host-mode map runs it on the CPU, with bit-identical results."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 2 ** 28 else 1)(d[0] * d[1] * d[2]))
+        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
+        if isinstance(fields, str):
+            fields = (fields,)
+        unknown = set(fields) - {"d2", "dist"}
+        if unknown:
+            raise ValueError(f"distance_field: unknown fields {sorted(unknown)}")
+        if isinstance(obstacles, str):
+            obstacles = (obstacles,)
+        mask = int(obstacles) if isinstance(obstacles, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(obstacles))
+        if not 0 <= mask < 2 ** 32 or not 0 <= int(radius) < 2 ** 32:
+            raise ValueError("distance_field: obstacles and radius must fit 32 bits")
+        out = {k: np.empty(shape, t) for k, t in (("d2", np.uint32), ("dist", np.float32)) if k in fields}
+        o = _lib.DistanceOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.DistanceOut._fields_])
+        info = _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_distance_field(self._h, lo3.ctypes.data, d3.ctypes.data, mask, int(radius), C.byref(o),
+                                                   C.byref(info)))
         out.update(self._region_info(info))
         return out
 

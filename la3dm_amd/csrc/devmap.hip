@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
+#include <limits>
 #include <cstring>   // (before rocPRIM: one of its iterator headers calls memset unqualified)
 
 #include <rocprim/rocprim.hpp>
@@ -25,6 +26,7 @@
 #include "devmap_grid_keys.h"
 #include "devmap_raycast.h"
 #include "devmap_region.h"
+#include "devmap_distance.h"
 
 using namespace la3dm_dev;
 
@@ -72,6 +74,7 @@ struct la3dm_devmap {
     bool counters_clean = false;  // the last insert's final launch left the counter block as dm_begin would (dm_commit_prune)
     int spec_bits = 32;           // key digits (x 8 bits) the cloud's own voxel filter needed last time (voxel_grid)
     Arena train, grid, axis_tab, m_code, q_out;
+    Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -667,7 +670,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -2384,8 +2387,10 @@ struct RegionGeom {
 
 // The region's checks, in the order of the contract (limits before any buffer is looked at), and its anchor: the only
 // floating-point work of the query, done here on the host for both kernels (host twin: BGKOctoMap::region_anchor).
-static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, bool columns, bool has_out, bool has_mandatory,
+// kind: 0 box, 1 columns, 2 distance field (box's region under its own voxel limit)
+static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, int kind, bool has_out, bool has_mandatory,
                           const char *who, RegionGeom &g) {
+    const bool columns = kind == 1;
     if (!dm) return LA3DM_ERR_ARG;
     dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
     const std::string w(who);
@@ -2405,6 +2410,10 @@ static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *di
         if (ncol > (1ull << 30)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than 2^30 columns");
         if (dims3[2] > LA3DM_COLUMNS_MAX_NZ) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)");
         g.total = ncol;
+    } else if (kind == 2) {
+        if (ncol > LA3DM_DF_MAX_CELLS || ncol * dims3[2] > LA3DM_DF_MAX_CELLS)
+            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels");
+        g.total = ncol * dims3[2];
     } else {
         if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS)
             return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
@@ -2428,7 +2437,8 @@ static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *di
     }
     g.info.block_key = key;
     if (!has_out) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out is NULL");
-    if (!has_mandatory) return dm_fail(dm, LA3DM_ERR_ARG, w + (columns ? ": out->counts must not be NULL" : ": out->cls must not be NULL"));
+    if (!has_mandatory)
+        return dm_fail(dm, LA3DM_ERR_ARG, w + (columns ? ": out->counts must not be NULL" : kind == 2 ? ": out: d2 or dist must not be NULL" : ": out->cls must not be NULL"));
     // origin = Block::get_point of the anchor cell: the LUT entry of its finest-layer node + the block centre
     uint32_t index = 0;
     for (int level = dl - 1; level >= 0; --level)
@@ -2606,6 +2616,123 @@ int la3dm_devmap_columns_host(la3dm_devmap *dm, const float *lo3, const uint32_t
     DM_TRY(hipMemcpyAsync(h.counts, d.counts, 16ull * n, hipMemcpyDeviceToHost, st));
     if (h.low_occ) DM_TRY(hipMemcpyAsync(h.low_occ, d.low_occ, 4ull * n, hipMemcpyDeviceToHost, st));
     if (h.top_occ) DM_TRY(hipMemcpyAsync(h.top_occ, d.top_occ, 4ull * n, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+// ---- distance field of a region (devmap_distance.h) -------------------------------------------------------------
+static int distance_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                            const la3dm_distance_out *out, const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    const std::string w(who);
+    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu))
+        return dm_fail(dm, LA3DM_ERR_ARG, w + ": obstacle_mask must hold at least one of the bits 0x1F and no other");
+    if (radius == 0 || radius > LA3DM_DF_MAX_RADIUS)
+        return dm_fail(dm, LA3DM_ERR_ARG, w + ": radius must lie in [1, LA3DM_DF_MAX_RADIUS (1024)]");
+    return region_resolve(dm, lo3, dims3, 2, out != nullptr, out && (out->d2 || out->dist), who, g);
+}
+
+// The four stages on the map's stream.  Two buffers take turns: `work` (4 bytes per voxel, the devmap's) and `spare` (an
+// output array, d2 or dist, free until the last pass fills it).  The last pass reads `work`, so the pass before it — y, or
+// z where ny = 1 and the y pass is left out — writes there, and each earlier stage writes where its successor does not.
+static void distance_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t obstacle_mask, uint32_t radius, void *work,
+                            const la3dm_distance_out &o) {
+    hipStream_t st = dm->ctx->stream;
+    RegionArgs a = region_args(dm, g);
+    void *spare = o.d2 ? (void *)o.d2 : (void *)o.dist;
+    const bool y_pass = a.ny > 1;
+    uint32_t *bits = (uint32_t *)(y_pass ? work : spare);   // ceil(total / 32) words <= 4 bytes per voxel
+    uint16_t *fz = (uint16_t *)(y_pass ? spare : work);
+    hipLaunchKernelGGL(dm_df_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, obstacle_mask, bits);
+    hipLaunchKernelGGL(dm_df_z, dim3(cdiv(a.total, 256)), dim3(256), 0, st, bits, fz, a.total, a.nz, radius);
+    DfPassArgs p;
+    memset(&p, 0, sizeof(p));
+    p.radius = radius;
+    p.r2 = radius * radius;
+    p.resolution = dm->ctx->p.resolution;
+    const uint32_t rows = kDfRows + 2u * radius;   // what a workgroup stages at most
+    if (y_pass) {
+        p.in = fz;
+        p.out = (uint32_t *)work;
+        p.L = a.ny;
+        p.S = a.nz;
+        p.n_lt = cdiv(p.L, kDfRows);
+        p.n_ct = cdiv(p.S, 64);
+        const uint32_t grid = a.nx * p.n_lt * p.n_ct, lds = rows * 64u * 2u;
+        if (lds <= kDfLdsBytes)
+            hipLaunchKernelGGL((dm_df_pass<uint16_t, true>), dim3(grid), dim3(256), lds, st, p);
+        else
+            hipLaunchKernelGGL((dm_df_pass<uint16_t, false>), dim3(grid), dim3(256), 0, st, p);
+    }
+    p.in = work;
+    p.out = nullptr;
+    p.d2 = o.d2;
+    p.dist = o.dist;
+    p.last = 1;
+    p.L = a.nx;
+    p.S = a.ny * a.nz;
+    p.n_lt = cdiv(p.L, kDfRows);
+    p.n_ct = cdiv(p.S, 64);
+    const uint32_t grid = p.n_lt * p.n_ct, wide = y_pass ? 4u : 2u, lds = rows * 64u * wide;
+    if (y_pass) {
+        if (lds <= kDfLdsBytes)
+            hipLaunchKernelGGL((dm_df_pass<uint32_t, true>), dim3(grid), dim3(256), lds, st, p);
+        else
+            hipLaunchKernelGGL((dm_df_pass<uint32_t, false>), dim3(grid), dim3(256), 0, st, p);
+    } else if (lds <= kDfLdsBytes) {
+        hipLaunchKernelGGL((dm_df_pass<uint16_t, true>), dim3(grid), dim3(256), lds, st, p);
+    } else {
+        hipLaunchKernelGGL((dm_df_pass<uint16_t, false>), dim3(grid), dim3(256), 0, st, p);
+    }
+}
+
+int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                                 uint32_t radius, const la3dm_distance_out *d_out, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = distance_resolve(dm, lo3, dims3, obstacle_mask, radius, d_out, "la3dm_devmap_distance_device", g);
+    if (rc != LA3DM_OK) return rc;
+    hipStream_t st = dm->ctx->stream;
+    const la3dm_distance_out &o = *d_out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: every voxel is MISSING — all obstacles or none; nothing is launched
+        const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
+        if (o.d2) DM_TRY(hipMemsetAsync(o.d2, all ? 0 : 0xFF, 4ull * n, st));
+        if (o.dist) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.dist, all ? 0 : 0x7F800000, n, st));
+    } else {
+        DM_RESERVE(dm->df_work, 4ull * n);
+        distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, o);
+        DM_TRY(hipGetLastError());
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                               uint32_t radius, const la3dm_distance_out *out, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = distance_resolve(dm, lo3, dims3, obstacle_mask, radius, out, "la3dm_devmap_distance_host", g);
+    if (rc != LA3DM_OK) return rc;
+    const la3dm_distance_out &h = *out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: every voxel is MISSING — all obstacles or none; nothing is launched
+        const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
+        if (h.d2) std::fill(h.d2, h.d2 + n, all ? 0u : LA3DM_DF_FAR);
+        if (h.dist) std::fill(h.dist, h.dist + n, all ? 0.0f : std::numeric_limits<float>::infinity());
+        if (info) *info = g.info;
+        return LA3DM_OK;
+    }
+    hipStream_t st = dm->ctx->stream;
+    DM_RESERVE(dm->df_work, 4ull * n);
+    DM_RESERVE(dm->q_out, 4ull * n * ((h.d2 ? 1 : 0) + (h.dist ? 1 : 0)));   // the outputs asked for
+    la3dm_distance_out d;
+    d.d2 = h.d2 ? (uint32_t *)dm->q_out.ptr : nullptr;
+    d.dist = h.dist ? (float *)dm->q_out.ptr + (h.d2 ? n : 0) : nullptr;
+    distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, d);
+    DM_TRY(hipGetLastError());
+    if (h.d2) DM_TRY(hipMemcpyAsync(h.d2, d.d2, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.dist) DM_TRY(hipMemcpyAsync(h.dist, d.dist, 4ull * n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
     if (info) *info = g.info;
     return LA3DM_OK;

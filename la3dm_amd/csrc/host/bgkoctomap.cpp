@@ -775,8 +775,9 @@ void BGKOctoMap::raycast_many(const float *rays6, size_t n, uint32_t stop_mask, 
 
 // ---- dense region reads: box / columns.  The host forms below are the definition; the device kernels
 // (csrc/devmap_region.h) reproduce them bit for bit.
-void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, bool columns, bool has_mandatory, const char *who,
+void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, int kind, bool has_mandatory, const char *who,
                                uint32_t g0[3], la3dm_region_info &info) const {
+    const bool columns = kind == 1;
     const std::string w = std::string("BGKOctoMap::") + who;
     if (lo3 == nullptr) throw std::invalid_argument(w + ": lo is NULL");
     if (dims3 == nullptr) throw std::invalid_argument(w + ": dims is NULL");
@@ -789,6 +790,9 @@ void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, bool col
     if (columns) {
         if (ncol > (1ull << 30)) throw std::invalid_argument(w + ": dims: more than 2^30 columns");
         if (dims3[2] > LA3DM_COLUMNS_MAX_NZ) throw std::invalid_argument(w + ": dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)");
+    } else if (kind == 2) {
+        if (ncol > LA3DM_DF_MAX_CELLS || ncol * dims3[2] > LA3DM_DF_MAX_CELLS)
+            throw std::invalid_argument(w + ": dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels");
     } else if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS) {
         throw std::invalid_argument(w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
     }
@@ -813,7 +817,8 @@ void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, bool col
     info.origin[0] = o.x();
     info.origin[1] = o.y();
     info.origin[2] = o.z();
-    if (!has_mandatory) throw std::invalid_argument(w + (columns ? ": out.counts must not be NULL" : ": out.cls must not be NULL"));
+    if (!has_mandatory)
+        throw std::invalid_argument(w + (columns ? ": out.counts must not be NULL" : kind == 2 ? ": out: d2 or dist must not be NULL" : ": out.cls must not be NULL"));
 }
 
 void BGKOctoMap::box(const float *lo3, const uint32_t *dims3, const la3dm_box_out &out, la3dm_region_info *info) const {
@@ -914,6 +919,82 @@ void BGKOctoMap::columns(const float *lo3, const uint32_t *dims3, const la3dm_co
             if (out.low_occ) out.low_occ[c] = low;
             if (out.top_occ) out.top_occ[c] = top;
         }
+}
+
+// ---- distance field of a region.  The host form below is the definition; the device kernels (csrc/devmap_distance.h)
+// reproduce it bit for bit.  Separable and exact: the distance along z to the nearest obstacle of the line (saturated at
+// radius + 1, squared), then min-plus passes along y and x over a window of +-radius — if D(v) <= radius^2 every axis
+// offset to the minimiser is <= radius, and a sum that holds a saturated term exceeds radius^2 and ends as FAR.
+namespace {
+// out[l] = min over |d| <= radius of in[l + d] + d^2 along lines of length L whose elements lie S apart
+void df_min_plus(const uint32_t *in, uint32_t *out, size_t planes, size_t L, size_t S, uint32_t radius) {
+#pragma omp parallel for collapse(2) schedule(static)
+    for (size_t p = 0; p < planes; ++p)
+        for (size_t l = 0; l < L; ++l) {
+            const uint32_t *line = in + p * L * S;
+            for (size_t c = 0; c < S; ++c) {
+                uint32_t best = line[l * S + c];
+                for (uint32_t d = 1; d <= radius && d * d < best; ++d) {
+                    if (l >= d) best = std::min(best, line[(l - d) * S + c] + d * d);
+                    if (l + d < L) best = std::min(best, line[(l + d) * S + c] + d * d);
+                }
+                out[(p * L + l) * S + c] = best;
+            }
+        }
+}
+}  // namespace
+
+void BGKOctoMap::distance_field(const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                                const la3dm_distance_out &out, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_distance_host(dmap, lo3, dims3, obstacle_mask, radius, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::distance_field: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::distance_field";
+    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu))
+        throw std::invalid_argument(w + ": obstacle_mask must hold at least one of the bits 0x1F and no other");
+    if (radius == 0 || radius > LA3DM_DF_MAX_RADIUS)
+        throw std::invalid_argument(w + ": radius must lie in [1, LA3DM_DF_MAX_RADIUS (1024)]");
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, 2, out.d2 != nullptr || out.dist != nullptr, "distance_field", g0, inf);
+    if (info) *info = inf;
+    const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2], n = nx * ny * nz;
+    std::vector<uint8_t> cls(n);
+    la3dm_box_out bo;
+    bo.cls = cls.data();
+    bo.leaf_depth = nullptr;
+    bo.A = bo.B = nullptr;
+    box(lo3, dims3, bo, nullptr);
+    std::vector<uint32_t> f(n), g(n);
+    const uint32_t sat = radius + 1u;
+#pragma omp parallel for schedule(static)
+    for (size_t line = 0; line < nx * ny; ++line) {   // z: a sweep up and a sweep down the line
+        const uint8_t *c = cls.data() + line * nz;
+        uint32_t *p = f.data() + line * nz;
+        uint32_t run = sat;
+        for (size_t k = 0; k < nz; ++k) {
+            run = ((obstacle_mask >> c[k]) & 1u) ? 0u : std::min(run + 1u, sat);
+            p[k] = run;
+        }
+        run = sat;
+        for (size_t k = nz; k-- > 0;) {
+            run = ((obstacle_mask >> c[k]) & 1u) ? 0u : std::min(run + 1u, sat);
+            p[k] = std::min(p[k], run);
+        }
+        for (size_t k = 0; k < nz; ++k) p[k] *= p[k];
+    }
+    df_min_plus(f.data(), g.data(), nx, ny, nz, radius);        // y
+    df_min_plus(g.data(), f.data(), 1, nx, ny * nz, radius);    // x
+    const uint32_t r2 = radius * radius;
+    const float res = resolution;
+    for (size_t v = 0; v < n; ++v) {
+        const bool far = f[v] > r2;
+        if (out.d2) out.d2[v] = far ? LA3DM_DF_FAR : f[v];
+        if (out.dist) out.dist[v] = far ? std::numeric_limits<float>::infinity() : sqrtf((float)f[v]) * res;
+    }
 }
 
 namespace {

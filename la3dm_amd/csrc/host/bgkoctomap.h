@@ -433,6 +433,15 @@ public:
     /// loops over its host blocks: that form is the definition, and both give the same bits.
     void box(const float *lo3, const uint32_t *dims3, const la3dm_box_out &out, la3dm_region_info *info = nullptr) const;
     void columns(const float *lo3, const uint32_t *dims3, const la3dm_columns_out &out, la3dm_region_info *info = nullptr) const;
+    /// Distance field of box's region (contract: include/la3dm_hip.h, la3dm_devmap_distance_host): per voxel the squared
+    /// Euclidean distance, an integer in voxel units, to the nearest voxel of the region whose class (box's cls) has its bit
+    /// in `obstacle_mask` — d2, LA3DM_DF_FAR beyond radius^2 — and dist = sqrtf(d2) * resolution, +inf for FAR.  Obstacles
+    /// outside the region are not seen (pad the region by `radius`); the distance inside obstacles is the call with the
+    /// complementary mask.  Bad arguments throw std::invalid_argument.  A device-resident map runs the transform on the
+    /// device pool (no mirror refresh); a host-mode map runs an exact separable transform (windowed min-plus) over the host
+    /// form of box's classes: that form is the definition, and both give the same bits.
+    void distance_field(const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                        const la3dm_distance_out &out, la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {
@@ -497,7 +506,8 @@ protected:
     mutable bool mirror_dirty = false;
     mutable uint64_t mirror_sync_count = 0;
     /// checks of a region query in the contract's order + its anchor: global voxel index g0 of voxel (0, 0, 0), info
-    void region_anchor(const float *lo3, const uint32_t *dims3, bool columns, bool has_mandatory, const char *who,
+    /// (kind: 0 box, 1 columns, 2 distance field)
+    void region_anchor(const float *lo3, const uint32_t *dims3, int kind, bool has_mandatory, const char *who,
                        uint32_t g0[3], la3dm_region_info &info) const;
     la3dm_params create_params;   // what the context was created with (lut_xyz is re-pointed on use)
     void create_context();        // la3dm_create + the device-resident pool from create_params and the current statics

@@ -376,6 +376,16 @@ int la3dm_map_columns(const la3dm_map *m, const float *lo3, const uint32_t *dims
         return 0;)
 }
 
+int la3dm_map_distance_field(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                             const la3dm_distance_out *out, la3dm_region_info *info) {
+    GUARD(
+        la3dm_distance_out none;
+        none.d2 = nullptr;
+        none.dist = nullptr;
+        m->map->distance_field(lo3, dims3, obstacle_mask, radius, out ? *out : none, info);
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);
