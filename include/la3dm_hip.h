@@ -513,6 +513,51 @@ int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_
  * returns when the results are complete.  An output array doubles as working storage until the last pass fills it. */
 int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
                                  uint32_t radius, const la3dm_distance_out *d_out, la3dm_region_info *info);
+/* Frontier of a region: the voxels of box(lo, dims) that are open and border unexplored space, as an ordered list.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's.
+ *   Classes.  cls(v) is what box reports for voxel v, the class of the covering leaf: FREE 0, OCCUPIED 1, UNKNOWN 2,
+ *     MISSING 3, a BGK-LV map's UNCERTAIN 4.
+ *   Reading past the faces.  The lattice does not stop at the region's faces: cls of a voxel one step outside the region
+ *     is read from the map exactly as box would read it at that lattice position.  In this the query differs from
+ *     distance_field: a frontier voxel on a face of the region is still found, and the answers of two boxes that tile a
+ *     third merge into the third's.
+ *   Neighbourhood.  The neighbours of v are v + (di, dj, dk), (di, dj, dk) in {-1, 0, 1}^3 without 0, chosen by
+ *     connectivity: 6 = the offsets with |di| + |dj| + |dk| = 1, 18 = those with a sum <= 2, 26 = all of them.
+ *   Score.  c(v) = the number of neighbours w of v with unknown_mask & (1u << cls(w)) set;
+ *     score[v] = c(v) if open_mask & (1u << cls(v)) is set, else 0.
+ *   Frontier.  v is a frontier voxel when score[v] >= min_neighbours.  *n_found = the number of frontier voxels of the
+ *     region, whatever cap is; index[t], t < min(*n_found, cap), = the flat index of the t-th frontier voxel in ascending
+ *     order of f; nbrs[t] = score[index[t]].  Entries at t >= *n_found are not written.  score (dense, optional) does not
+ *     depend on cap.
+ *   Count-only call.  cap = 0 with out NULL (or with only out->score set) returns *n_found (and score): the two-call
+ *     protocol of la3dm_devmap_export_cells.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, no buffer touched, nothing reserved): an
+ *     open_mask or unknown_mask of 0 or with bits above 0x1F (overlapping masks are legal); a connectivity other than 6,
+ *     18, 26; min_neighbours of 0 or above connectivity; what box refuses for lo and dims; (nx + 2)(ny + 2)(nz + 2) >
+ *     LA3DM_FR_MAX_CELLS; a region that, padded by one voxel on every side, fails box's block-field range check; cap > 0
+ *     with out or out->index NULL; n_found NULL.  The limits are checked before any buffer is looked at.
+ *   An empty map (every voxel and its surroundings MISSING) answers from the definition without reading the pool: every
+ *     voxel with score = connectivity if both masks hold bit 3, no voxel otherwise.
+ *   Everything is integer arithmetic on classes: the results equal the host form (BGKOctoMap::frontier on a host-mode
+ *     map) exactly.
+ *   Working storage: two bit streams, one popcount and one prefix per 32 voxels of the padded box — 1/2 byte per padded
+ *     voxel — in a grow-only arena of the devmap (released with it; a smaller request after a larger one allocates
+ *     nothing).  No per-voxel byte is kept: a dense score is written only where the caller asks for it. */
+#define LA3DM_FR_MAX_CELLS (1u << 28)
+typedef struct la3dm_frontier_out {
+    uint32_t *index;   /* [cap] or NULL */
+    uint8_t  *nbrs;    /* [cap] or NULL */
+    uint8_t  *score;   /* [nx ny nz] or NULL, independent of cap */
+} la3dm_frontier_out;
+/* host pointers: the launches, download of min(*n_found, cap) entries, synchronise — on the map's stream */
+int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
+                               uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
+                               const la3dm_frontier_out *out, uint64_t *n_found, la3dm_region_info *info);
+/* device pointers (out's arrays already in HBM on the map's device, index 4-byte aligned; lo3, dims3, n_found and info
+ * stay host-side); returns when the results are complete */
+int la3dm_devmap_frontier_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
+                                 uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
+                                 const la3dm_frontier_out *d_out, uint64_t *n_found, la3dm_region_info *info);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

@@ -139,6 +139,17 @@ int la3dm_map_columns(const la3dm_map *m, const float *lo3, const uint32_t *dims
  * mirror refresh, host-mode maps on the CPU; the results are bit-identical. */
 int la3dm_map_distance_field(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
                              const la3dm_distance_out *out, la3dm_region_info *info);
+/* BGKOctoMap::frontier: the voxels of box's region whose class is in open_mask and that have at least min_neighbours
+ * neighbours (connectivity 6, 18 or 26) whose class is in unknown_mask — cls as box reports it, the bits of raycast_many's
+ * stop_mask — with the neighbours one step outside the region read from the map.  *n_found = their number, whatever cap is;
+ * out->index = the flat indices (i * ny + j) * nz + k of the first min(*n_found, cap) in ascending order, out->nbrs = their
+ * scores, out->score (dense, optional) = the score of every voxel.  cap = 0 with out NULL (or only out->score set) counts:
+ * call once for *n_found, then with buffers of that size.  Contract, limits and refusals: include/la3dm_hip.h
+ * (la3dm_devmap_frontier_host).  Device-resident maps run the query on the device pool without a mirror refresh, host-mode
+ * maps on the CPU; the results are identical. */
+int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask,
+                       uint32_t connectivity, uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out *out,
+                       uint64_t *n_found, la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

@@ -1,7 +1,7 @@
 """la3dm_amd — MI355X-native (gfx950) implementation of la3dm's per-scan occupancy-inference
 hot path behind the reference's BGKOctoMap interface.  See DESIGN.md / INTEGRATION.md."""
 from .bgkoctomap import BGKOctoMap, GPOctoMap, BGKLVOctoMap, BGKLOctoMap, PackedScan, FREE, OCCUPIED, UNKNOWN, PRUNED  # noqa: F401
-from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR  # noqa: F401
+from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR_MAX_CELLS  # noqa: F401
 from .pcd import load_pcd  # noqa: F401
 from .synth import synthetic_scan  # noqa: F401
 

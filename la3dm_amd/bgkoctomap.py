@@ -15,6 +15,7 @@ FREE, OCCUPIED, UNKNOWN, PRUNED = 0, 1, 2, 3
 MISSING = 3
 RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
 DF_FAR = 0xFFFFFFFF                 # LA3DM_DF_FAR: beyond the radius of distance_field (dist: +inf)
+FR_MAX_CELLS = 1 << 28             # LA3DM_FR_MAX_CELLS: voxels of frontier's region padded by one on every side
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
@@ -293,6 +294,64 @@ class BGKOctoMap:
         info = _lib.RegionInfo()
         self._chk(self._M.la3dm_map_distance_field(self._h, lo3.ctypes.data, d3.ctypes.data, mask, int(radius), C.byref(o),
                                                    C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
+    def frontier(self, lo, dims, open=("free",), unknown=("unknown", "missing"), connectivity=6, min_neighbours=1,
+                 fields=("index", "nbrs"), cap=None):
+        """The frontier of the region of box(lo, dims) as an ordered list: the voxels whose class (box's cls) is in `open`
+        and that have at least `min_neighbours` neighbours whose class is in `unknown` — names out of free / occupied /
+        unknown / missing (/ uncertain on a BGK-LV map) or an integer bit mask, as raycast_many's `stop`; the masks may
+        overlap.  connectivity: 6 (faces), 18 (+ edges) or 26 (+ corners).  The neighbours one step outside the region are
+        read from the map, so a frontier voxel on a face of the region is found.  Returns n = the number of frontier
+        voxels, index (uint32) = their flat indices (i * ny + j) * nz + k in ascending order (np.unravel_index(index, dims)
+        gives i, j, k), nbrs (uint8) = their scores (the number of such neighbours), and with "score" in `fields` the
+        dense score (uint8, shape dims; 0 where the voxel is not open); plus origin, block_key, cell as box() returns
+        them.  cap=None counts first and then fills exactly n entries; an integer cap fills the first min(n, cap) and n is
+        still the total.  At most 2^28 voxels in the region padded by one.  A device-resident map runs the query on the
+        device pool (no host mirror refresh); a host-mode map runs it on the CPU, with identical results."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and (d[0] + 2) * (d[1] + 2) * (d[2] + 2) <= 2 ** 28 else 1)(d[0] * d[1] * d[2]))
+        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - {"index", "nbrs", "score"}
+        if bad:
+            raise ValueError(f"frontier: unknown fields {sorted(bad)}")
+        masks = []
+        for m in (open, unknown):
+            if isinstance(m, str):
+                m = (m,)
+            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
+        if not all(0 <= v < 2 ** 32 for v in masks + [int(connectivity), int(min_neighbours)]):
+            raise ValueError("frontier: open, unknown, connectivity and min_neighbours must fit 32 bits")
+        if cap is not None and not 0 <= int(cap) < 2 ** 64:
+            raise ValueError("frontier: cap must fit 64 bits")
+        info = _lib.RegionInfo()
+        found = C.c_uint64(0)
+
+        def call(k, o):
+            self._chk(self._M.la3dm_map_frontier(self._h, lo3.ctypes.data, d3.ctypes.data, masks[0], masks[1], int(connectivity),
+                                                 int(min_neighbours), k, C.byref(o) if o is not None else None, C.byref(found),
+                                                 C.byref(info)))
+            return int(found.value)
+
+        out = {}
+        if "score" in fields:
+            out["score"] = np.empty(shape, np.uint8)
+        score = out["score"].ctypes.data if "score" in out else None
+        if cap is None:   # the two-call protocol: count (the dense score comes with this call), then fill exactly n
+            k = call(0, _lib.FrontierOut(None, None, score) if score else None)
+            score = None
+        else:
+            k = min(int(cap), n)
+        out["index"] = np.empty(k, np.uint32)
+        out["nbrs"] = np.empty(k, np.uint8)
+        total = k
+        if cap is not None or k:
+            total = call(k, _lib.FrontierOut(out["index"].ctypes.data if k else None, out["nbrs"].ctypes.data if k else None, score))
+        m = min(total, k)
+        out["index"], out["nbrs"] = out["index"][:m], out["nbrs"][:m]
+        out["n"] = total
         out.update(self._region_info(info))
         return out
 

@@ -27,6 +27,7 @@
 #include "devmap_raycast.h"
 #include "devmap_region.h"
 #include "devmap_distance.h"
+#include "devmap_frontier.h"
 
 using namespace la3dm_dev;
 
@@ -75,6 +76,7 @@ struct la3dm_devmap {
     int spec_bits = 32;           // key digits (x 8 bits) the cloud's own voxel filter needed last time (voxel_grid)
     Arena train, grid, axis_tab, m_code, q_out;
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
+    Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -670,7 +672,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -2387,7 +2389,8 @@ struct RegionGeom {
 
 // The region's checks, in the order of the contract (limits before any buffer is looked at), and its anchor: the only
 // floating-point work of the query, done here on the host for both kernels (host twin: BGKOctoMap::region_anchor).
-// kind: 0 box, 1 columns, 2 distance field (box's region under its own voxel limit)
+// kind: 0 box, 1 columns, 2 distance field (box's region under its own voxel limit), 3 frontier (box's region, its limit and
+// its block-field range both taken on the region padded by one voxel on every side)
 static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, int kind, bool has_out, bool has_mandatory,
                           const char *who, RegionGeom &g) {
     const bool columns = kind == 1;
@@ -2414,6 +2417,11 @@ static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *di
         if (ncol > LA3DM_DF_MAX_CELLS || ncol * dims3[2] > LA3DM_DF_MAX_CELLS)
             return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels");
         g.total = ncol * dims3[2];
+    } else if (kind == 3) {
+        const uint64_t pcol = ((uint64_t)dims3[0] + 2) * ((uint64_t)dims3[1] + 2);
+        if (std::max(dims3[0], std::max(dims3[1], dims3[2])) > LA3DM_FR_MAX_CELLS || pcol > LA3DM_FR_MAX_CELLS || pcol * ((uint64_t)dims3[2] + 2) > LA3DM_FR_MAX_CELLS)
+            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region");
+        g.total = ncol * dims3[2];
     } else {
         if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS)
             return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
@@ -2429,6 +2437,8 @@ static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *di
         const int c = std::max(0, std::min(t, lim - 1));
         const long long first = b * lim + c, last = first + (long long)dims3[k] - 1;
         if (last / lim >= (1ll << 20)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: the region's block fields leave [0, 2^20)");
+        if (kind == 3 && (first == 0 || (last + 1) / lim >= (1ll << 20)))
+            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: the block fields of the region padded by one voxel leave [0, 2^20)");
         g.g0[k] = (uint32_t)first;
         cell[k] = (uint32_t)c;
         g.info.cell[k] = c;
@@ -2734,6 +2744,170 @@ int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_
     if (h.d2) DM_TRY(hipMemcpyAsync(h.d2, d.d2, 4ull * n, hipMemcpyDeviceToHost, st));
     if (h.dist) DM_TRY(hipMemcpyAsync(h.dist, d.dist, 4ull * n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+// ---- frontier of a region (devmap_frontier.h) -----------------------------------------------------------------
+static int frontier_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask,
+                            uint32_t connectivity, uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out *out,
+                            const uint64_t *n_found, const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    const std::string w(who);
+    if (open_mask == 0 || (open_mask & ~0x1Fu))
+        return dm_fail(dm, LA3DM_ERR_ARG, w + ": open_mask must hold at least one of the bits 0x1F and no other");
+    if (unknown_mask == 0 || (unknown_mask & ~0x1Fu))
+        return dm_fail(dm, LA3DM_ERR_ARG, w + ": unknown_mask must hold at least one of the bits 0x1F and no other");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        return dm_fail(dm, LA3DM_ERR_ARG, w + ": connectivity must be 6, 18 or 26");
+    if (min_neighbours == 0 || min_neighbours > connectivity)
+        return dm_fail(dm, LA3DM_ERR_ARG, w + ": min_neighbours must lie in [1, connectivity]");
+    int rc = region_resolve(dm, lo3, dims3, 3, true, true, who, g);   // lo, dims, the limit and the range: before any buffer
+    if (rc != LA3DM_OK) return rc;
+    if (cap > 0 && !out) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out is NULL with cap > 0");
+    if (cap > 0 && !out->index) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out->index must not be NULL with cap > 0");
+    if (!n_found) return dm_fail(dm, LA3DM_ERR_ARG, w + ": n_found is NULL");
+    return LA3DM_OK;
+}
+
+// Bits, stencil, scan and (cap > 0) emit on the map's stream; o's arrays are device memory.  d_total: where the launches
+// leave the number of frontier voxels (a word of the query's working storage).
+static int frontier_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity,
+                           uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out &o, const uint32_t *&d_total) {
+    hipStream_t st = dm->ctx->stream;
+    RegionArgs a = region_args(dm, g);
+    for (int k = 0; k < 3; ++k) a.g0[k] = g.g0[k] - 1u;   // (frontier_resolve: g0 >= 1)
+    a.nx = g.dims[0] + 2u;
+    a.ny = g.dims[1] + 2u;
+    a.nz = g.dims[2] + 2u;
+    a.total = a.nx * a.ny * a.nz;   // <= LA3DM_FR_MAX_CELLS
+    const uint32_t n_words = cdiv(a.total, 32);
+    const size_t stride = ((size_t)n_words + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
+    DM_RESERVE(dm->fr_work, 16ull * stride);
+    uint32_t *base = (uint32_t *)dm->fr_work.ptr;
+    FrontierArgs f;
+    memset(&f, 0, sizeof(f));
+    f.nx = g.dims[0];
+    f.ny = g.dims[1];
+    f.nz = g.dims[2];
+    f.PY = a.ny;
+    f.PZ = a.nz;
+    f.total = a.total;
+    f.n_words = n_words;
+    f.min_neighbours = min_neighbours;
+    f.open = base;
+    f.unknown = base + stride;
+    f.count = base + 2 * stride;
+    f.offset = base + 3 * stride;
+    f.cap = cap;
+    f.index = cap ? o.index : nullptr;
+    f.nbrs = cap ? o.nbrs : nullptr;
+    f.score = o.score;
+    if (o.score) DM_TRY(hipMemsetAsync(o.score, 0, (size_t)g.total, st));
+    hipLaunchKernelGGL(dm_fr_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, open_mask, unknown_mask, f.open, base + stride);
+    const dim3 wgrid(cdiv(n_words + 1, 256));
+    if (connectivity == 6)
+        hipLaunchKernelGGL(dm_fr_stencil<6>, wgrid, dim3(256), 0, st, f);
+    else if (connectivity == 18)
+        hipLaunchKernelGGL(dm_fr_stencil<18>, wgrid, dim3(256), 0, st, f);
+    else
+        hipLaunchKernelGGL(dm_fr_stencil<26>, wgrid, dim3(256), 0, st, f);
+    DM_TRY(hipGetLastError());
+    dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
+    int rc = exclusive_scan(dm, f.count, base + 3 * stride, n_words + 1);
+    if (rc != LA3DM_OK) return rc;
+    if (cap) {
+        if (connectivity == 6)
+            hipLaunchKernelGGL(dm_fr_emit<6>, wgrid, dim3(256), 0, st, f);
+        else if (connectivity == 18)
+            hipLaunchKernelGGL(dm_fr_emit<18>, wgrid, dim3(256), 0, st, f);
+        else
+            hipLaunchKernelGGL(dm_fr_emit<26>, wgrid, dim3(256), 0, st, f);
+        DM_TRY(hipGetLastError());
+    }
+    d_total = f.offset + n_words;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_frontier_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
+                                 uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
+                                 const la3dm_frontier_out *d_out, uint64_t *n_found, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = frontier_resolve(dm, lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, d_out, n_found,
+                              "la3dm_devmap_frontier_device", g);
+    if (rc != LA3DM_OK) return rc;
+    hipStream_t st = dm->ctx->stream;
+    la3dm_frontier_out o;
+    memset(&o, 0, sizeof(o));
+    if (d_out) o = *d_out;
+    const size_t n = (size_t)g.total;
+    uint32_t total = 0;
+    if (dm->n_blocks == 0) {  // empty map: every voxel and its surroundings are MISSING — all voxels or none; the pool is not read
+        const bool all = ((open_mask & unknown_mask) >> LA3DM_RAY_MISSING) & 1u;
+        total = all ? (uint32_t)n : 0u;
+        if (o.score) DM_TRY(hipMemsetAsync(o.score, all ? (int)connectivity : 0, n, st));
+        const uint32_t m = (uint32_t)std::min<uint64_t>(total, cap);
+        if (m) {
+            hipLaunchKernelGGL(dm_fr_all, dim3(cdiv(m, 256)), dim3(256), 0, st, o.index, o.nbrs, m, connectivity);
+            DM_TRY(hipGetLastError());
+        }
+    } else {
+        const uint32_t *d_total = nullptr;
+        rc = frontier_launch(dm, g, open_mask, unknown_mask, connectivity, min_neighbours, cap, o, d_total);
+        if (rc != LA3DM_OK) return rc;
+        DM_TRY(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    *n_found = total;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
+                               uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
+                               const la3dm_frontier_out *out, uint64_t *n_found, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = frontier_resolve(dm, lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, out, n_found,
+                              "la3dm_devmap_frontier_host", g);
+    if (rc != LA3DM_OK) return rc;
+    la3dm_frontier_out h;
+    memset(&h, 0, sizeof(h));
+    if (out) h = *out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {  // empty map: every voxel and its surroundings are MISSING — all voxels or none; nothing is launched
+        const bool all = ((open_mask & unknown_mask) >> LA3DM_RAY_MISSING) & 1u;
+        if (h.score) memset(h.score, all ? (int)connectivity : 0, n);
+        const uint64_t m = all ? std::min<uint64_t>(n, cap) : 0;
+        for (uint64_t t = 0; t < m; ++t) {
+            h.index[t] = (uint32_t)t;
+            if (h.nbrs) h.nbrs[t] = (uint8_t)connectivity;
+        }
+        *n_found = all ? n : 0;
+        if (info) *info = g.info;
+        return LA3DM_OK;
+    }
+    hipStream_t st = dm->ctx->stream;
+    // outputs staged in `q_out`: index (at most one entry per voxel, and no more than cap), then nbrs, then score
+    const size_t room = (size_t)std::min<uint64_t>(cap, n), room4 = (room + 3) & ~(size_t)3;
+    DM_RESERVE(dm->q_out, 4ull * room + (h.nbrs ? room4 : 0) + (h.score ? n : 0) + 16);
+    la3dm_frontier_out d;
+    d.index = (uint32_t *)dm->q_out.ptr;
+    d.nbrs = h.nbrs ? (uint8_t *)(d.index + room) : nullptr;
+    d.score = h.score ? (uint8_t *)(d.index + room) + (h.nbrs ? room4 : 0) : nullptr;
+    const uint32_t *d_total = nullptr;
+    rc = frontier_launch(dm, g, open_mask, unknown_mask, connectivity, min_neighbours, room, d, d_total);
+    if (rc != LA3DM_OK) return rc;
+    uint32_t total = 0;
+    DM_TRY(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
+    if (h.score) DM_TRY(hipMemcpyAsync(h.score, d.score, n, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    const size_t m = (size_t)std::min<uint64_t>(total, room);   // only what was found is downloaded
+    if (m) {
+        DM_TRY(hipMemcpyAsync(h.index, d.index, 4ull * m, hipMemcpyDeviceToHost, st));
+        if (h.nbrs) DM_TRY(hipMemcpyAsync(h.nbrs, d.nbrs, m, hipMemcpyDeviceToHost, st));
+        DM_TRY(hipStreamSynchronize(st));
+    }
+    *n_found = total;
     if (info) *info = g.info;
     return LA3DM_OK;
 }

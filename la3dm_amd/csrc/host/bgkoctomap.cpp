@@ -793,6 +793,10 @@ void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, int kind
     } else if (kind == 2) {
         if (ncol > LA3DM_DF_MAX_CELLS || ncol * dims3[2] > LA3DM_DF_MAX_CELLS)
             throw std::invalid_argument(w + ": dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels");
+    } else if (kind == 3) {
+        const uint64_t pcol = ((uint64_t)dims3[0] + 2) * ((uint64_t)dims3[1] + 2);
+        if (std::max(dims3[0], std::max(dims3[1], dims3[2])) > LA3DM_FR_MAX_CELLS || pcol > LA3DM_FR_MAX_CELLS || pcol * ((uint64_t)dims3[2] + 2) > LA3DM_FR_MAX_CELLS)
+            throw std::invalid_argument(w + ": dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region");
     } else if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS) {
         throw std::invalid_argument(w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
     }
@@ -809,6 +813,8 @@ void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, int kind
     for (int k = 0; k < 3; ++k) {
         const long long first = b[k] * lim + c[k], last = first + (long long)dims3[k] - 1;
         if (last / lim >= (1ll << 20)) throw std::invalid_argument(w + ": dims: the region's block fields leave [0, 2^20)");
+        if (kind == 3 && (first == 0 || (last + 1) / lim >= (1ll << 20)))
+            throw std::invalid_argument(w + ": dims: the block fields of the region padded by one voxel leave [0, 2^20)");
         g0[k] = (uint32_t)first;
         info.cell[k] = c[k];
     }
@@ -994,6 +1000,110 @@ void BGKOctoMap::distance_field(const float *lo3, const uint32_t *dims3, uint32_
         const bool far = f[v] > r2;
         if (out.d2) out.d2[v] = far ? LA3DM_DF_FAR : f[v];
         if (out.dist) out.dist[v] = far ? std::numeric_limits<float>::infinity() : sqrtf((float)f[v]) * res;
+    }
+}
+
+// ---- frontier of a region.  The host form below is the definition; the device kernels (csrc/devmap_frontier.h)
+// reproduce it bit for bit.  The classes of the region padded by one voxel on every side are read as box reads them (the
+// lattice does not stop at the region's faces); a voxel's score is the number of its neighbours whose class is in
+// unknown_mask if its own class is in open_mask, else 0.
+void BGKOctoMap::frontier(const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity,
+                          uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out &out, uint64_t *n_found,
+                          la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_frontier_host(dmap, lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, &out, n_found, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::frontier: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::frontier";
+    if (open_mask == 0 || (open_mask & ~0x1Fu))
+        throw std::invalid_argument(w + ": open_mask must hold at least one of the bits 0x1F and no other");
+    if (unknown_mask == 0 || (unknown_mask & ~0x1Fu))
+        throw std::invalid_argument(w + ": unknown_mask must hold at least one of the bits 0x1F and no other");
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
+        throw std::invalid_argument(w + ": connectivity must be 6, 18 or 26");
+    if (min_neighbours == 0 || min_neighbours > connectivity)
+        throw std::invalid_argument(w + ": min_neighbours must lie in [1, connectivity]");
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, 3, true, "frontier", g0, inf);
+    if (cap > 0 && out.index == nullptr) throw std::invalid_argument(w + ": out.index must not be NULL with cap > 0");
+    if (n_found == nullptr) throw std::invalid_argument(w + ": n_found is NULL");
+    if (info) *info = inf;
+    const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2];
+    const size_t PY = ny + 2, PZ = nz + 2, P = (nx + 2) * PY * PZ;
+    // classes of the padded box: box's loop at the lattice positions g0 - 1 + (i, j, k)
+    std::vector<uint8_t> cls(P);
+    const unsigned dl = block_depth - 1u;
+    const uint32_t cm = (1u << dl) - 1u;
+#pragma omp parallel for schedule(static)
+    for (size_t row = 0; row < (nx + 2) * PY; ++row) {
+        const uint32_t gx = g0[0] - 1u + (uint32_t)(row / PY), gy = g0[1] - 1u + (uint32_t)(row % PY);
+        const Block *b = nullptr;
+        BlockHashKey have = -1;
+        for (size_t k = 0; k < PZ; ++k) {
+            const uint32_t gz = g0[2] - 1u + (uint32_t)k;
+            const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
+            if (key != have) {
+                auto it = block_arr.find(key);
+                b = it == block_arr.end() ? nullptr : it->second;
+                have = key;
+            }
+            uint8_t c = LA3DM_RAY_MISSING;
+            if (b != nullptr) {
+                unsigned d = dl, n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
+                while (d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED) {
+                    --d;
+                    n >>= 3;
+                }
+                c = (uint8_t)b->slab[layer_base(d) + n].state;
+            }
+            cls[row * PZ + k] = c;
+        }
+    }
+    std::vector<ptrdiff_t> offs;
+    const unsigned reach = connectivity == 6 ? 1u : connectivity == 18 ? 2u : 3u;
+    for (int di = -1; di <= 1; ++di)
+        for (int dj = -1; dj <= 1; ++dj)
+            for (int dk = -1; dk <= 1; ++dk) {
+                const unsigned s = (unsigned)(std::abs(di) + std::abs(dj) + std::abs(dk));
+                if (s >= 1 && s <= reach) offs.push_back(((ptrdiff_t)di * (ptrdiff_t)PY + dj) * (ptrdiff_t)PZ + dk);
+            }
+    // per (i, j) row of the region: its scores and how many of them reach min_neighbours; then the rows' places in the list
+    std::vector<uint8_t> own_score;
+    uint8_t *score = out.score;
+    if (score == nullptr) {
+        own_score.resize(nx * ny * nz);
+        score = own_score.data();
+    }
+    std::vector<uint64_t> row_start(nx * ny + 1, 0);
+#pragma omp parallel for schedule(static)
+    for (size_t row = 0; row < nx * ny; ++row) {
+        const size_t i = row / ny, j = row % ny;
+        const uint8_t *c = cls.data() + ((i + 1) * PY + (j + 1)) * PZ + 1;
+        uint64_t found = 0;
+        for (size_t k = 0; k < nz; ++k) {
+            uint32_t sc = 0;
+            if ((open_mask >> c[k]) & 1u)
+                for (const ptrdiff_t o : offs) sc += (unknown_mask >> c[(ptrdiff_t)k + o]) & 1u;
+            score[row * nz + k] = (uint8_t)sc;
+            found += sc >= min_neighbours ? 1u : 0u;
+        }
+        row_start[row + 1] = found;
+    }
+    for (size_t row = 0; row < nx * ny; ++row) row_start[row + 1] += row_start[row];
+    *n_found = row_start[nx * ny];
+#pragma omp parallel for schedule(static)
+    for (size_t row = 0; row < nx * ny; ++row) {
+        uint64_t t = row_start[row];
+        for (size_t k = 0; k < nz && t < cap; ++k) {
+            const uint8_t sc = score[row * nz + k];
+            if (sc < min_neighbours) continue;
+            out.index[t] = (uint32_t)(row * nz + k);
+            if (out.nbrs) out.nbrs[t] = sc;
+            ++t;
+        }
     }
 }
 

@@ -442,6 +442,16 @@ public:
     /// form of box's classes: that form is the definition, and both give the same bits.
     void distance_field(const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
                         const la3dm_distance_out &out, la3dm_region_info *info = nullptr) const;
+    /// Frontier of box's region (contract: include/la3dm_hip.h, la3dm_devmap_frontier_host): the voxels whose class (box's
+    /// cls) is in `open_mask` and that have at least `min_neighbours` neighbours (connectivity 6, 18 or 26) whose class is in
+    /// `unknown_mask`, neighbours one step outside the region included.  *n_found = their number; out.index = the flat
+    /// indices of the first min(*n_found, cap) in ascending order, out.nbrs = their scores, out.score (dense, optional) = the
+    /// score of every voxel.  cap = 0 only counts.  Bad arguments throw std::invalid_argument.  A device-resident map runs
+    /// the query on the device pool (no mirror refresh); a host-mode map loops over the classes of the padded box: that form
+    /// is the definition, and both give the same integers.
+    void frontier(const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity,
+                  uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out &out, uint64_t *n_found,
+                  la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {
@@ -506,7 +516,7 @@ protected:
     mutable bool mirror_dirty = false;
     mutable uint64_t mirror_sync_count = 0;
     /// checks of a region query in the contract's order + its anchor: global voxel index g0 of voxel (0, 0, 0), info
-    /// (kind: 0 box, 1 columns, 2 distance field)
+    /// (kind: 0 box, 1 columns, 2 distance field, 3 frontier)
     void region_anchor(const float *lo3, const uint32_t *dims3, int kind, bool has_mandatory, const char *who,
                        uint32_t g0[3], la3dm_region_info &info) const;
     la3dm_params create_params;   // what the context was created with (lut_xyz is re-pointed on use)

@@ -386,6 +386,18 @@ int la3dm_map_distance_field(const la3dm_map *m, const float *lo3, const uint32_
         return 0;)
 }
 
+int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask,
+                       uint32_t connectivity, uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out *out,
+                       uint64_t *n_found, la3dm_region_info *info) {
+    GUARD(
+        la3dm_frontier_out none;
+        none.index = nullptr;
+        none.nbrs = nullptr;
+        none.score = nullptr;
+        m->map->frontier(lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, out ? *out : none, n_found, info);
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);
