@@ -24,6 +24,7 @@
 #include "devmap_lv_kernels.h"
 #include "devmap_depth3.h"
 #include "devmap_grid_keys.h"
+#include "host/region_contract.h"
 #include "devmap_raycast.h"
 #include "devmap_region.h"
 #include "devmap_distance.h"
@@ -2253,6 +2254,11 @@ static int raycast_check(la3dm_devmap *dm, const float *rays6, uint32_t n, uint3
     return LA3DM_OK;
 }
 
+// the pool as a query kernel's argument (devmap_pool.h)
+static PoolView pool_view(const la3dm_devmap *dm) {
+    return PoolView{dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->A, dm->B, dm->S, dm->npb, dm->depth, dm->init_A, dm->init_B};
+}
+
 static void raycast_launch(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
                            const la3dm_raycast_out &o) {
     RaycastArgs a;
@@ -2261,19 +2267,10 @@ static void raycast_launch(la3dm_devmap *dm, const float *d_rays6, uint32_t n, u
     a.n = n;
     a.stop_mask = stop_mask;
     a.max_steps = max_steps;
-    a.tab_key = dm->tab_key;
-    a.tab_val = dm->tab_val;
-    a.mask = dm->tab_cap - 1;
-    a.A = dm->A;
-    a.B = dm->B;
-    a.S = dm->S;
+    a.pool = pool_view(dm);
     a.lut = dm->ctx->d_lut;
-    a.npb = dm->npb;
-    a.depth = dm->depth;
     a.block_size = dm->block_size;
     a.resolution = dm->ctx->p.resolution;
-    a.a0 = dm->init_A;
-    a.b0 = dm->init_B;
     a.steps = o.steps;
     a.flags = o.flags;
     a.p = o.p;
@@ -2387,81 +2384,38 @@ struct RegionGeom {
 };
 }  // namespace
 
-// The region's checks, in the order of the contract (limits before any buffer is looked at), and its anchor: the only
-// floating-point work of the query, done here on the host for both kernels (host twin: BGKOctoMap::region_anchor).
-// kind: 0 box, 1 columns, 2 distance field (box's region under its own voxel limit), 3 frontier (box's region, its limit and
-// its block-field range both taken on the region padded by one voxel on every side)
-static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, int kind, bool has_out, bool has_mandatory,
-                          const char *who, RegionGeom &g) {
-    const bool columns = kind == 1;
+// The region's checks and its anchor (host/region_contract.h, shared with the host twin BGKOctoMap::region_anchor), then
+// info.origin, for which the one LUT entry of the anchor cell is fetched from the device.
+static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_region::Query &q, bool has_out,
+                          bool has_mandatory, const char *who, RegionGeom &g) {
     if (!dm) return LA3DM_ERR_ARG;
     dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
     const std::string w(who);
-    if (!lo3) return dm_fail(dm, LA3DM_ERR_ARG, w + ": lo is NULL");
-    if (!dims3) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims is NULL");
-    const float res = dm->ctx->p.resolution, bs = dm->block_size;
-    const int dl = (int)dm->depth - 1, lim = 1 << dl;
-    for (int k = 0; k < 3; ++k)
-        if (!(fabsf(lo3[k] / res) < 1073741824.0f))   // false for NaN and inf
-            return dm_fail(dm, LA3DM_ERR_ARG, w + ": lo must be finite with |lo / resolution| < 2^30");
+    la3dm_region::Anchor an;
+    const std::string refusal = la3dm_region::resolve(q, lo3, dims3, dm->ctx->p.resolution, dm->block_size, dm->depth, has_out,
+                                                      has_mandatory, "->", an);
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
     for (int k = 0; k < 3; ++k) {
-        if (dims3[k] == 0) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims must be >= 1 on every axis");
+        g.g0[k] = an.g0[k];
         g.dims[k] = dims3[k];
+        g.info.cell[k] = an.cell[k];
     }
-    const uint64_t ncol = (uint64_t)dims3[0] * dims3[1];
-    if (columns) {
-        if (ncol > (1ull << 30)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than 2^30 columns");
-        if (dims3[2] > LA3DM_COLUMNS_MAX_NZ) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)");
-        g.total = ncol;
-    } else if (kind == 2) {
-        if (ncol > LA3DM_DF_MAX_CELLS || ncol * dims3[2] > LA3DM_DF_MAX_CELLS)
-            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels");
-        g.total = ncol * dims3[2];
-    } else if (kind == 3) {
-        const uint64_t pcol = ((uint64_t)dims3[0] + 2) * ((uint64_t)dims3[1] + 2);
-        if (std::max(dims3[0], std::max(dims3[1], dims3[2])) > LA3DM_FR_MAX_CELLS || pcol > LA3DM_FR_MAX_CELLS || pcol * ((uint64_t)dims3[2] + 2) > LA3DM_FR_MAX_CELLS)
-            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region");
-        g.total = ncol * dims3[2];
-    } else {
-        if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS)
-            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
-        g.total = ncol * dims3[2];
-    }
-    long long key = 0;
-    uint32_t cell[3];
-    for (int k = 0; k < 3; ++k) {
-        const long long b = (long long)((double)lo3[k] / (double)bs + 524288.5);   // block_to_hash_key, one axis
-        if (b < 0 || b >= (1ll << 20)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": lo: the block field leaves [0, 2^20)");
-        const float center = (float)(b - 524288) * bs;                             // hash_key_to_block
-        const int t = (int)((lo3[k] - center) / res + (float)(lim / 2));           // Block::get_index: truncation, clamped
-        const int c = std::max(0, std::min(t, lim - 1));
-        const long long first = b * lim + c, last = first + (long long)dims3[k] - 1;
-        if (last / lim >= (1ll << 20)) return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: the region's block fields leave [0, 2^20)");
-        if (kind == 3 && (first == 0 || (last + 1) / lim >= (1ll << 20)))
-            return dm_fail(dm, LA3DM_ERR_ARG, w + ": dims: the block fields of the region padded by one voxel leave [0, 2^20)");
-        g.g0[k] = (uint32_t)first;
-        cell[k] = (uint32_t)c;
-        g.info.cell[k] = c;
-        g.info.origin[k] = center;
-        key = (key << 20) | b;
-    }
-    g.info.block_key = key;
-    if (!has_out) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out is NULL");
-    if (!has_mandatory)
-        return dm_fail(dm, LA3DM_ERR_ARG, w + (columns ? ": out->counts must not be NULL" : kind == 2 ? ": out: d2 or dist must not be NULL" : ": out->cls must not be NULL"));
+    g.total = an.total;
+    g.info.block_key = an.block_key;
     // origin = Block::get_point of the anchor cell: the LUT entry of its finest-layer node + the block centre
+    const int dl = (int)dm->depth - 1;
     uint32_t index = 0;
     for (int level = dl - 1; level >= 0; --level)
-        index = index * 8u + ((((cell[0] >> level) & 1u) << 2) | (((cell[1] >> level) & 1u) << 1) | ((cell[2] >> level) & 1u));
+        index = index * 8u + ((((an.cell[0] >> level) & 1u) << 2) | (((an.cell[1] >> level) & 1u) << 1) | ((an.cell[2] >> level) & 1u));
     const uint32_t entry = (0x249249u & ((1u << (3u * (uint32_t)dl)) - 1u)) + index;
     if (entry >= dm->ctx->lut_count) return dm_fail(dm, LA3DM_ERR_ARG, w + ": the context's voxel LUT does not reach the finest layer");
     float4 o;
     DM_TRY(hipSetDevice(dm->ctx->device));
     DM_TRY(hipMemcpyAsync(&o, dm->ctx->d_lut + entry, sizeof(o), hipMemcpyDeviceToHost, dm->ctx->stream));
     DM_TRY(hipStreamSynchronize(dm->ctx->stream));
-    g.info.origin[0] = o.x + g.info.origin[0];
-    g.info.origin[1] = o.y + g.info.origin[1];
-    g.info.origin[2] = o.z + g.info.origin[2];
+    g.info.origin[0] = o.x + an.center[0];
+    g.info.origin[1] = o.y + an.center[1];
+    g.info.origin[2] = o.z + an.center[2];
     return LA3DM_OK;
 }
 
@@ -2473,16 +2427,7 @@ static RegionArgs region_args(la3dm_devmap *dm, const RegionGeom &g) {
     a.ny = g.dims[1];
     a.nz = g.dims[2];
     a.total = (uint32_t)g.total;
-    a.tab_key = dm->tab_key;
-    a.tab_val = dm->tab_val;
-    a.mask = dm->tab_cap - 1;
-    a.A = dm->A;
-    a.B = dm->B;
-    a.S = dm->S;
-    a.npb = dm->npb;
-    a.depth = dm->depth;
-    a.a0 = dm->init_A;
-    a.b0 = dm->init_B;
+    a.pool = pool_view(dm);
     return a;
 }
 
@@ -2512,7 +2457,7 @@ static void columns_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_co
 int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *d_out,
                             la3dm_region_info *info) {
     RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, false, d_out != nullptr, d_out && d_out->cls, "la3dm_devmap_box_device", g);
+    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kBox, d_out != nullptr, d_out && d_out->cls, "la3dm_devmap_box_device", g);
     if (rc != LA3DM_OK) return rc;
     hipStream_t st = dm->ctx->stream;
     const la3dm_box_out &o = *d_out;
@@ -2537,7 +2482,7 @@ int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *
 int la3dm_devmap_box_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out,
                           la3dm_region_info *info) {
     RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, false, out != nullptr, out && out->cls, "la3dm_devmap_box_host", g);
+    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kBox, out != nullptr, out && out->cls, "la3dm_devmap_box_host", g);
     if (rc != LA3DM_OK) return rc;
     const la3dm_box_out &h = *out;
     const size_t n = (size_t)g.total;
@@ -2575,7 +2520,7 @@ int la3dm_devmap_box_host(la3dm_devmap *dm, const float *lo3, const uint32_t *di
 int la3dm_devmap_columns_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *d_out,
                                 la3dm_region_info *info) {
     RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, true, d_out != nullptr, d_out && d_out->counts, "la3dm_devmap_columns_device", g);
+    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kColumns, d_out != nullptr, d_out && d_out->counts, "la3dm_devmap_columns_device", g);
     if (rc != LA3DM_OK) return rc;
     hipStream_t st = dm->ctx->stream;
     const la3dm_columns_out &o = *d_out;
@@ -2599,7 +2544,7 @@ int la3dm_devmap_columns_device(la3dm_devmap *dm, const float *lo3, const uint32
 int la3dm_devmap_columns_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
                               la3dm_region_info *info) {
     RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, true, out != nullptr, out && out->counts, "la3dm_devmap_columns_host", g);
+    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kColumns, out != nullptr, out && out->counts, "la3dm_devmap_columns_host", g);
     if (rc != LA3DM_OK) return rc;
     const la3dm_columns_out &h = *out;
     const size_t n = (size_t)g.total;
@@ -2635,12 +2580,19 @@ int la3dm_devmap_columns_host(la3dm_devmap *dm, const float *lo3, const uint32_t
 static int distance_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
                             const la3dm_distance_out *out, const char *who, RegionGeom &g) {
     if (!dm) return LA3DM_ERR_ARG;
-    const std::string w(who);
-    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu))
-        return dm_fail(dm, LA3DM_ERR_ARG, w + ": obstacle_mask must hold at least one of the bits 0x1F and no other");
-    if (radius == 0 || radius > LA3DM_DF_MAX_RADIUS)
-        return dm_fail(dm, LA3DM_ERR_ARG, w + ": radius must lie in [1, LA3DM_DF_MAX_RADIUS (1024)]");
-    return region_resolve(dm, lo3, dims3, 2, out != nullptr, out && (out->d2 || out->dist), who, g);
+    const std::string refusal = la3dm_region::distance_check(obstacle_mask, radius);
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+    return region_resolve(dm, lo3, dims3, la3dm_region::kDistance, out != nullptr, out && (out->d2 || out->dist), who, g);
+}
+
+// a min-plus pass over 16-bit z distances or (wide) 32-bit partial sums: staged in LDS where the rows of a workgroup and
+// their halo fit, else straight from global memory
+static void df_pass_launch(hipStream_t st, bool wide, uint32_t grid, uint32_t rows, const DfPassArgs &p) {
+    const uint32_t lds = rows * 64u * (wide ? 4u : 2u);
+    const bool fits = lds <= kDfLdsBytes;
+    void (*pass)(DfPassArgs) = wide ? (fits ? dm_df_pass<uint32_t, true> : dm_df_pass<uint32_t, false>)
+                                    : (fits ? dm_df_pass<uint16_t, true> : dm_df_pass<uint16_t, false>);
+    hipLaunchKernelGGL(pass, dim3(grid), dim3(256), fits ? lds : 0, st, p);
 }
 
 // The four stages on the map's stream.  Two buffers take turns: `work` (4 bytes per voxel, the devmap's) and `spare` (an
@@ -2669,11 +2621,7 @@ static void distance_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t obst
         p.S = a.nz;
         p.n_lt = cdiv(p.L, kDfRows);
         p.n_ct = cdiv(p.S, 64);
-        const uint32_t grid = a.nx * p.n_lt * p.n_ct, lds = rows * 64u * 2u;
-        if (lds <= kDfLdsBytes)
-            hipLaunchKernelGGL((dm_df_pass<uint16_t, true>), dim3(grid), dim3(256), lds, st, p);
-        else
-            hipLaunchKernelGGL((dm_df_pass<uint16_t, false>), dim3(grid), dim3(256), 0, st, p);
+        df_pass_launch(st, false, a.nx * p.n_lt * p.n_ct, rows, p);
     }
     p.in = work;
     p.out = nullptr;
@@ -2684,17 +2632,7 @@ static void distance_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t obst
     p.S = a.ny * a.nz;
     p.n_lt = cdiv(p.L, kDfRows);
     p.n_ct = cdiv(p.S, 64);
-    const uint32_t grid = p.n_lt * p.n_ct, wide = y_pass ? 4u : 2u, lds = rows * 64u * wide;
-    if (y_pass) {
-        if (lds <= kDfLdsBytes)
-            hipLaunchKernelGGL((dm_df_pass<uint32_t, true>), dim3(grid), dim3(256), lds, st, p);
-        else
-            hipLaunchKernelGGL((dm_df_pass<uint32_t, false>), dim3(grid), dim3(256), 0, st, p);
-    } else if (lds <= kDfLdsBytes) {
-        hipLaunchKernelGGL((dm_df_pass<uint16_t, true>), dim3(grid), dim3(256), lds, st, p);
-    } else {
-        hipLaunchKernelGGL((dm_df_pass<uint16_t, false>), dim3(grid), dim3(256), 0, st, p);
-    }
+    df_pass_launch(st, y_pass, p.n_lt * p.n_ct, rows, p);
 }
 
 int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
@@ -2754,15 +2692,9 @@ static int frontier_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *
                             const uint64_t *n_found, const char *who, RegionGeom &g) {
     if (!dm) return LA3DM_ERR_ARG;
     const std::string w(who);
-    if (open_mask == 0 || (open_mask & ~0x1Fu))
-        return dm_fail(dm, LA3DM_ERR_ARG, w + ": open_mask must hold at least one of the bits 0x1F and no other");
-    if (unknown_mask == 0 || (unknown_mask & ~0x1Fu))
-        return dm_fail(dm, LA3DM_ERR_ARG, w + ": unknown_mask must hold at least one of the bits 0x1F and no other");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        return dm_fail(dm, LA3DM_ERR_ARG, w + ": connectivity must be 6, 18 or 26");
-    if (min_neighbours == 0 || min_neighbours > connectivity)
-        return dm_fail(dm, LA3DM_ERR_ARG, w + ": min_neighbours must lie in [1, connectivity]");
-    int rc = region_resolve(dm, lo3, dims3, 3, true, true, who, g);   // lo, dims, the limit and the range: before any buffer
+    const std::string refusal = la3dm_region::frontier_check(open_mask, unknown_mask, connectivity, min_neighbours);
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
+    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kFrontier, true, true, who, g);   // lo, dims, the limit and the range: before any buffer
     if (rc != LA3DM_OK) return rc;
     if (cap > 0 && !out) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out is NULL with cap > 0");
     if (cap > 0 && !out->index) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out->index must not be NULL with cap > 0");
@@ -2806,23 +2738,19 @@ static int frontier_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t open_
     if (o.score) DM_TRY(hipMemsetAsync(o.score, 0, (size_t)g.total, st));
     hipLaunchKernelGGL(dm_fr_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, open_mask, unknown_mask, f.open, base + stride);
     const dim3 wgrid(cdiv(n_words + 1, 256));
-    if (connectivity == 6)
-        hipLaunchKernelGGL(dm_fr_stencil<6>, wgrid, dim3(256), 0, st, f);
-    else if (connectivity == 18)
-        hipLaunchKernelGGL(dm_fr_stencil<18>, wgrid, dim3(256), 0, st, f);
-    else
-        hipLaunchKernelGGL(dm_fr_stencil<26>, wgrid, dim3(256), 0, st, f);
+    struct Kernels {
+        void (*stencil)(FrontierArgs), (*emit)(FrontierArgs);
+    };
+    const Kernels kn = connectivity == 6    ? Kernels{dm_fr_stencil<6>, dm_fr_emit<6>}
+                       : connectivity == 18 ? Kernels{dm_fr_stencil<18>, dm_fr_emit<18>}
+                                            : Kernels{dm_fr_stencil<26>, dm_fr_emit<26>};
+    hipLaunchKernelGGL(kn.stencil, wgrid, dim3(256), 0, st, f);
     DM_TRY(hipGetLastError());
     dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
     int rc = exclusive_scan(dm, f.count, base + 3 * stride, n_words + 1);
     if (rc != LA3DM_OK) return rc;
     if (cap) {
-        if (connectivity == 6)
-            hipLaunchKernelGGL(dm_fr_emit<6>, wgrid, dim3(256), 0, st, f);
-        else if (connectivity == 18)
-            hipLaunchKernelGGL(dm_fr_emit<18>, wgrid, dim3(256), 0, st, f);
-        else
-            hipLaunchKernelGGL(dm_fr_emit<26>, wgrid, dim3(256), 0, st, f);
+        hipLaunchKernelGGL(kn.emit, wgrid, dim3(256), 0, st, f);
         DM_TRY(hipGetLastError());
     }
     d_total = f.offset + n_words;

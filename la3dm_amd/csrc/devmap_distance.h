@@ -39,25 +39,12 @@ constexpr uint32_t kDfLdsBytes = 64u << 10;   // staging limit of dm_df_pass<..,
 // lanes beyond `total` vote 0, so the bits past the end of the last word are clear.
 __global__ __launch_bounds__(256) void dm_df_bits(RegionArgs a, uint32_t obstacle_mask, uint32_t *bits) {
     const uint32_t f = blockIdx.x * 256u + threadIdx.x;   // total <= 2^28: no overflow
-    uint32_t cls = kRegionMissing;
-    const bool in = f < a.total;
-    if (in) {
-        const uint32_t dl = a.depth - 1u, cm = (1u << dl) - 1u;
+    uint32_t cls = kClsMissing;
+    if (f < a.total) {
         const uint32_t k = f % a.nz, row = f / a.nz;
-        const uint32_t gx = a.g0[0] + row / a.ny, gy = a.g0[1] + row % a.ny, gz = a.g0[2] + k;
-        const long long key = ((long long)(gx >> dl) << 40) | ((long long)(gy >> dl) << 20) | (long long)(gz >> dl);
-        const uint32_t slot = region_find_block(a, key);
-        if (slot != kRegionNoSlot) {
-            const uint32_t cell = ray_cell_index((int)(gx & cm), (int)(gy & cm), (int)(gz & cm), (int)dl);
-            const uint8_t *Sb = a.S + (size_t)slot * a.npb;
-            uint32_t d, n;
-            covering_leaf(Sb, dl, cell, d, n);
-            cls = Sb[dm_layer_base(d) + n] & 7u;
-        }
+        cls = pool_class_at(a.pool, a.g0[0] + row / a.ny, a.g0[1] + row % a.ny, a.g0[2] + k);
     }
-    const unsigned long long vote = __ballot(in && ((obstacle_mask >> cls) & 1u));
-    const uint32_t lane = threadIdx.x & 63u;
-    if (in && (lane & 31u) == 0u) bits[f >> 5] = lane ? (uint32_t)(vote >> 32) : (uint32_t)vote;
+    pool_store_ballot(bits, f, a.total, f < a.total && ((obstacle_mask >> cls) & 1u));
 }
 
 // ---- stage 2: distance along z ---------------------------------------------------------------------------------

@@ -56,32 +56,17 @@ struct FrontierArgs {
 __global__ __launch_bounds__(256) void dm_fr_bits(RegionArgs a, uint32_t open_mask, uint32_t unknown_mask, uint32_t *open,
                                                   uint32_t *unknown) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;   // total <= 2^28: no overflow
-    uint32_t cls = kRegionMissing;
+    uint32_t cls = kClsMissing;
     const bool in = p < a.total;
     bool inner = false;
     if (in) {
-        const uint32_t dl = a.depth - 1u, cm = (1u << dl) - 1u;
         const uint32_t k = p % a.nz, row = p / a.nz;
         const uint32_t i = row / a.ny, j = row % a.ny;
         inner = k >= 1u && k + 1u < a.nz && j >= 1u && j + 1u < a.ny && i >= 1u && i + 1u < a.nx;
-        const uint32_t gx = a.g0[0] + i, gy = a.g0[1] + j, gz = a.g0[2] + k;
-        const long long key = ((long long)(gx >> dl) << 40) | ((long long)(gy >> dl) << 20) | (long long)(gz >> dl);
-        const uint32_t slot = region_find_block(a, key);
-        if (slot != kRegionNoSlot) {
-            const uint32_t cell = ray_cell_index((int)(gx & cm), (int)(gy & cm), (int)(gz & cm), (int)dl);
-            const uint8_t *Sb = a.S + (size_t)slot * a.npb;
-            uint32_t d, n;
-            covering_leaf(Sb, dl, cell, d, n);
-            cls = Sb[dm_layer_base(d) + n] & 7u;
-        }
+        cls = pool_class_at(a.pool, a.g0[0] + i, a.g0[1] + j, a.g0[2] + k);
     }
-    const unsigned long long vo = __ballot(inner && ((open_mask >> cls) & 1u));
-    const unsigned long long vu = __ballot(in && ((unknown_mask >> cls) & 1u));
-    const uint32_t lane = threadIdx.x & 63u;
-    if (in && (lane & 31u) == 0u) {
-        open[p >> 5] = lane ? (uint32_t)(vo >> 32) : (uint32_t)vo;
-        unknown[p >> 5] = lane ? (uint32_t)(vu >> 32) : (uint32_t)vu;
-    }
+    pool_store_ballot(open, p, a.total, inner && ((open_mask >> cls) & 1u));
+    pool_store_ballot(unknown, p, a.total, in && ((unknown_mask >> cls) & 1u));
 }
 
 // ---- the stencil of one word --------------------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 // twin: host/bgkoctomap.cpp RayCaster + BGKOctoMap::raycast_many, which is the definition this kernel reproduces bit for
 // bit): an integer DDA over the voxel indices of the two end points, the reference's case order, its diagonal double
 // step and its "no case applies" repeat, the fp32 block-centre re-hash when a face is crossed and dead reckoning inside
-// missing blocks.  What a row IS comes from the covering leaf of its voxel (covering_leaf, devmap_kernels.h).
+// missing blocks.  What a row IS comes from the covering leaf of its voxel (pool_leaf_class, devmap_pool.h).
 //
 // Memory traffic per step: one state byte (plus one per PRUNED level climbed); the block-table probe (8 B key and 4 B
 // slot per entry tried) only when a block face is crossed; the LUT entry (16 B) of the voxel; A / B once, for the last row.
@@ -12,23 +12,16 @@
 #ifndef LA3DM_DEVMAP_RAYCAST_H
 #define LA3DM_DEVMAP_RAYCAST_H
 
-#include "../../include/la3dm_hip.h"
-#include "devmap_kernels.h"
+#include "devmap_pool.h"
 
 namespace la3dm_dev {
 
 struct RaycastArgs {
     const float *rays;   // 6 per ray: start xyz, end xyz
     uint32_t n, stop_mask, max_steps;
-    // pool
-    const long long *tab_key;
-    const uint32_t *tab_val;
-    uint32_t mask;       // table size - 1
-    const float *A, *B;
-    const uint8_t *S;
     const float4 *lut;   // voxel offsets, depth-major (the context's LUT)
-    uint32_t npb, depth;
-    float block_size, resolution, a0, b0;
+    float block_size, resolution;
+    PoolView pool;
     // outputs (all but steps / flags may be null)
     uint32_t *steps;
     uint8_t *flags;
@@ -40,29 +33,8 @@ struct RaycastArgs {
     uint32_t *counts;
 };
 
-constexpr uint32_t kRayHit = 1u, kRayTruncated = 2u, kRayInvalid = 4u, kRayMissing = 3u, kRayNoSlot = 0xFFFFFFFFu;
+constexpr uint32_t kRayHit = 1u, kRayTruncated = 2u, kRayInvalid = 4u;
 static_assert(LA3DM_RAY_MAX_STEPS <= (1u << 20), "dm_raycast packs its per-class row counts in 21-bit fields");
-
-// pool slot of a block key, kRayNoSlot when the map has no such block; at most one trip round the table
-__device__ __forceinline__ uint32_t ray_find_block(const RaycastArgs &a, long long key) {
-    uint32_t h = hash_key64(key, a.mask);
-    for (uint32_t probe = 0; probe <= a.mask; ++probe) {
-        const long long cur = a.tab_key[h];
-        const uint32_t val = a.tab_val[h];   // asked for together with the key: one round trip per probe, not two
-        if (cur == key) return val;
-        if (cur == kEmptyKey) break;
-        h = (h + 1) & a.mask;
-    }
-    return kRayNoSlot;
-}
-
-// Block::get_node: finest-layer index of cell (x, y, z); child bit 4 = +x, 2 = +y, 1 = +z per level
-__device__ __forceinline__ uint32_t ray_cell_index(int x, int y, int z, int levels) {
-    uint32_t index = 0;
-    for (int level = levels - 1; level >= 0; --level)
-        index = index * 8u + (uint32_t)((((x >> level) & 1) << 2) | (((y >> level) & 1) << 1) | ((z >> level) & 1));
-    return index;
-}
 
 // element `k` (runtime) of a 3-array that lives in registers: selects, never a runtime-indexed array (scratch)
 #define RAY_SEL3(v, k) ((k) == 0 ? (v)[0] : ((k) == 1 ? (v)[1] : (v)[2]))
@@ -85,22 +57,22 @@ __global__ __launch_bounds__(256, 8) void dm_raycast(RaycastArgs a) {
         q[k] = a.rays[6 * (size_t)r + k];
         ok &= fabsf(q[k] / res) < 1073741824.0f;   // false for NaN and inf
     }
-    const int dl = (int)a.depth - 1, lim = 1 << dl;
+    const int dl = (int)a.pool.depth - 1, lim = 1 << dl;
     const uint32_t fine_base = dm_layer_base((uint32_t)dl);
     uint32_t steps = 0, flags = ok ? 0u : kRayInvalid;
     unsigned long long cnt = 0;   // rows of class 0, 1, 2 in 21-bit fields (a ray has at most 2^20 rows); class 3 = the rest
     // block of the start point
     int bi[3] = {0, 0, 0};
     long long key = 0;
-    uint32_t slot = kRayNoSlot;
+    uint32_t slot = kNoSlot;
     if (ok) {
         const long long i0 = axis_index(q[0], bs), i1 = axis_index(q[1], bs), i2 = axis_index(q[2], bs);
         key = (i0 << 40) | (i1 << 20) | i2;
-        slot = ray_find_block(a, key);
+        slot = pool_find_block(a.pool, key);
     }
     float cur[3] = {0.f, 0.f, 0.f};   // current_p
     uint32_t idx = 0;                 // voxel index inside the block, 8 bits per axis (x lowest)
-    if (slot != kRayNoSlot) {
+    if (slot != kNoSlot) {
         // centre of the block as the host block holds it (hash_key_to_block of its key); recomputed from the key where
         // a row needs it, which is cheaper than three registers carried round the loop
         const float pc[3] = {axis_center(key >> 40, bs), axis_center((key >> 20) & 0xFFFFF, bs), axis_center(key & 0xFFFFF, bs)};
@@ -126,21 +98,15 @@ __global__ __launch_bounds__(256, 8) void dm_raycast(RaycastArgs a) {
         int err_xy = dd[0] - dd[1], err_xz = dd[0] - dd[2], err_yz = dd[1] - dd[2];
         for (;;) {   // n > 0 here; every trip is one row, and a.max_steps rows end the loop whatever the map holds
             // ---- the row (RayCaster::next up to `p = current_p`): its class is all the loop needs
-            uint32_t cls = kRayMissing;
-            if (slot != kRayNoSlot) {
-                const uint32_t cell = ray_cell_index(idx & 0xFF, (idx >> 8) & 0xFF, (idx >> 16) & 0xFF, dl);
+            uint32_t cls = kClsMissing;
+            if (slot != kNoSlot) {
+                const uint32_t cell = pool_cell_index(idx & 0xFF, (idx >> 8) & 0xFF, (idx >> 16) & 0xFF, dl);
                 const float4 o = a.lut[fine_base + cell];
                 cur[0] = o.x + axis_center(key >> 40, bs);
                 cur[1] = o.y + axis_center((key >> 20) & 0xFFFFF, bs);
                 cur[2] = o.z + axis_center(key & 0xFFFFF, bs);
-                const uint8_t *Sb = a.S + (size_t)slot * a.npb;
-                uint32_t d = (uint32_t)dl, i = cell, st = Sb[fine_base + cell] & 7u;
-                while (d > 0 && st == kStatePruned) {   // covering_leaf, the state kept
-                    --d;
-                    i >>= 3;
-                    st = Sb[dm_layer_base(d) + i] & 7u;
-                }
-                cls = st;
+                uint32_t d, i;
+                cls = pool_leaf_class(a.pool.S + (size_t)slot * a.pool.npb, (uint32_t)dl, cell, d, i);
             }
             ++steps;
             const uint32_t field = cls > 3u ? 2u : cls;   // (a BGK-LV map's UNCERTAIN leaves count with UNKNOWN)
@@ -190,28 +156,27 @@ __global__ __launch_bounds__(256, 8) void dm_raycast(RaycastArgs a) {
                     RAY_PUT3(wc, ax, w);
                     RAY_PUT3(bi, ax, (int)axis_index(w, bs));
                     key = ((long long)bi[0] << 40) | ((long long)bi[1] << 20) | (long long)bi[2];
-                    slot = ray_find_block(a, key);
+                    slot = pool_find_block(a.pool, key);
                 }
             }
         }
     }
     // ---- the last row again, in full: key, covering leaf and its node (the loop kept only the position and the counts)
-    uint32_t cls = kRayMissing, leaf_d = 255u, node_key = 0;
-    float A = a.a0, B = a.b0;
+    uint32_t cls = kClsMissing, leaf_d = 255u, node_key = 0;
+    float A = a.pool.a0, B = a.pool.b0;
     if (steps == 0) {
         key = 0;   // never started (or refused)
     } else {
-        const uint32_t cell = ray_cell_index(idx & 0xFF, (idx >> 8) & 0xFF, (idx >> 16) & 0xFF, dl);
+        const uint32_t cell = pool_cell_index(idx & 0xFF, (idx >> 8) & 0xFF, (idx >> 16) & 0xFF, dl);
         node_key = ((uint32_t)dl << 16) + cell;
-        if (slot != kRayNoSlot) {
-            const uint8_t *Sb = a.S + (size_t)slot * a.npb;
+        if (slot != kNoSlot) {
             uint32_t d, i;
-            covering_leaf(Sb, (uint32_t)dl, cell, d, i);
-            const size_t node = dm_layer_base(d) + i;
-            cls = Sb[node] & 7u;
+            covering_leaf(a.pool.S + (size_t)slot * a.pool.npb, (uint32_t)dl, cell, d, i);
+            const size_t node = (size_t)slot * a.pool.npb + dm_layer_base(d) + i;
+            cls = a.pool.S[node] & 7u;
             leaf_d = d;
-            if (a.oA) A = a.A[(size_t)slot * a.npb + node];
-            if (a.oB) B = a.B[(size_t)slot * a.npb + node];
+            if (a.oA) A = a.pool.A[node];
+            if (a.oB) B = a.pool.B[node];
         }
     }
     a.steps[r] = steps;

@@ -20,9 +20,7 @@
 #ifndef LA3DM_DEVMAP_REGION_H
 #define LA3DM_DEVMAP_REGION_H
 
-#include "../../include/la3dm_hip.h"
-#include "devmap_kernels.h"
-#include "devmap_raycast.h"
+#include "devmap_pool.h"
 
 namespace la3dm_dev {
 
@@ -30,14 +28,7 @@ struct RegionArgs {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0)
     uint32_t nx, ny, nz;
     uint32_t total;      // box: nx ny nz; columns: nx ny
-    // pool
-    const long long *tab_key;
-    const uint32_t *tab_val;
-    uint32_t mask;       // table size - 1
-    const float *A, *B;
-    const uint8_t *S;
-    uint32_t npb, depth;
-    float a0, b0;
+    PoolView pool;
     // box outputs (all but cls may be null)
     uint8_t *cls, *leaf_depth;
     float *oA, *oB;
@@ -47,57 +38,42 @@ struct RegionArgs {
     uint32_t counts_vec;   // counts is 16-byte aligned: one uint4 store per column
 };
 
-constexpr uint32_t kRegionNoSlot = 0xFFFFFFFFu, kRegionMissing = LA3DM_RAY_MISSING;
 constexpr uint32_t kRegionFree = 0u, kRegionOccupied = 1u;   // State::FREE, State::OCCUPIED
-
-// pool slot of a block key, kRegionNoSlot when the map has no such block; at most one trip round the table
-__device__ __forceinline__ uint32_t region_find_block(const RegionArgs &a, long long key) {
-    uint32_t h = hash_key64(key, a.mask);
-    for (uint32_t probe = 0; probe <= a.mask; ++probe) {
-        const long long cur = a.tab_key[h];
-        const uint32_t val = a.tab_val[h];   // asked for together with the key: one round trip per probe, not two
-        if (cur == key) return val;
-        if (cur == kEmptyKey) break;
-        h = (h + 1) & a.mask;
-    }
-    return kRegionNoSlot;
-}
 
 template <int V>
 __global__ __launch_bounds__(256) void dm_box(RegionArgs a) {
     const uint32_t first = (blockIdx.x * 256u + threadIdx.x) * (uint32_t)V;   // total <= 2^30: no overflow
     if (first >= a.total) return;
-    const uint32_t dl = a.depth - 1u, cm = (1u << dl) - 1u;
+    const uint32_t dl = a.pool.depth - 1u, cm = (1u << dl) - 1u;
     uint32_t k = first % a.nz;
     const uint32_t row = first / a.nz;
     uint32_t j = row % a.ny, i = row / a.ny;
     uint32_t cls[V], dep[V];
     float vA[V], vB[V];
     long long last_key = -2;   // (no key: keys are >= 0, the table's empty mark is -1)
-    uint32_t slot = kRegionNoSlot;
+    uint32_t slot = kNoSlot;
 #pragma unroll
     for (int v = 0; v < V; ++v) {   // V is a template argument: the four arrays are registers
-        cls[v] = kRegionMissing;
+        cls[v] = kClsMissing;
         dep[v] = 255u;
-        vA[v] = a.a0;
-        vB[v] = a.b0;
+        vA[v] = a.pool.a0;
+        vB[v] = a.pool.b0;
         if (first + (uint32_t)v < a.total) {
             const uint32_t gx = a.g0[0] + i, gy = a.g0[1] + j, gz = a.g0[2] + k;
-            const long long key = ((long long)(gx >> dl) << 40) | ((long long)(gy >> dl) << 20) | (long long)(gz >> dl);
+            const long long key = pool_block_key(gx, gy, gz, dl);
             if (key != last_key) {
-                slot = region_find_block(a, key);
+                slot = pool_find_block(a.pool, key);
                 last_key = key;
             }
-            if (slot != kRegionNoSlot) {
-                const uint32_t cell = ray_cell_index((int)(gx & cm), (int)(gy & cm), (int)(gz & cm), (int)dl);
-                const uint8_t *Sb = a.S + (size_t)slot * a.npb;
+            if (slot != kNoSlot) {
+                const uint32_t cell = pool_cell_index((int)(gx & cm), (int)(gy & cm), (int)(gz & cm), (int)dl);
                 uint32_t d, n;
-                covering_leaf(Sb, dl, cell, d, n);
-                const size_t node = dm_layer_base(d) + n;
-                cls[v] = Sb[node] & 7u;
+                covering_leaf(a.pool.S + (size_t)slot * a.pool.npb, dl, cell, d, n);
+                const size_t node = (size_t)slot * a.pool.npb + dm_layer_base(d) + n;
+                cls[v] = a.pool.S[node] & 7u;
                 dep[v] = d;
-                if (a.oA) vA[v] = a.A[(size_t)slot * a.npb + node];
-                if (a.oB) vB[v] = a.B[(size_t)slot * a.npb + node];
+                if (a.oA) vA[v] = a.pool.A[node];
+                if (a.oB) vB[v] = a.pool.B[node];
             }
             if (++k == a.nz) {
                 k = 0;
@@ -131,29 +107,22 @@ __global__ __launch_bounds__(256) void dm_box(RegionArgs a) {
 __global__ __launch_bounds__(256) void dm_columns(RegionArgs a) {
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;
     if (c >= a.total) return;
-    const uint32_t dl = a.depth - 1u, lim = 1u << dl, cm = lim - 1u;
-    const uint32_t fine_base = dm_layer_base(dl);
+    const uint32_t dl = a.pool.depth - 1u, lim = 1u << dl, cm = lim - 1u;
     const uint32_t j = c % a.ny, i = c / a.ny;
     const uint32_t gx = a.g0[0] + i, gy = a.g0[1] + j;
-    const long long key_xy = ((long long)(gx >> dl) << 40) | ((long long)(gy >> dl) << 20);
-    const uint32_t cell_xy = ray_cell_index((int)(gx & cm), (int)(gy & cm), 0, (int)dl);
+    const uint32_t cell_xy = pool_cell_index((int)(gx & cm), (int)(gy & cm), 0, (int)dl);
     uint32_t n_free = 0, n_occ = 0, n_unk = 0;
     int32_t low = -1, top = -1;
     uint32_t k = 0;
     while (k < a.nz) {   // one trip per block of the column: at most nz / lim + 2
         const uint32_t gz = a.g0[2] + k, cz0 = gz & cm;
         const uint32_t run = min(lim - cz0, a.nz - k);
-        const uint32_t slot = region_find_block(a, key_xy | (long long)(gz >> dl));
-        if (slot != kRegionNoSlot) {   // (a missing block is counted by what is left of nz at the end)
-            const uint8_t *Sb = a.S + (size_t)slot * a.npb;
+        const uint32_t slot = pool_find_block(a.pool, pool_block_key(gx, gy, gz, dl));
+        if (slot != kNoSlot) {   // (a missing block is counted by what is left of nz at the end)
+            const uint8_t *Sb = a.pool.S + (size_t)slot * a.pool.npb;
             for (uint32_t u = 0; u < run; ++u) {
-                uint32_t n = cell_xy | ray_cell_index(0, 0, (int)(cz0 + u), (int)dl), d = dl;
-                uint32_t st = Sb[fine_base + n] & 7u;
-                while (d > 0 && st == kStatePruned) {   // covering_leaf, the state kept
-                    --d;
-                    n >>= 3;
-                    st = Sb[dm_layer_base(d) + n] & 7u;
-                }
+                uint32_t d, n;
+                const uint32_t st = pool_leaf_class(Sb, dl, cell_xy | pool_cell_index(0, 0, (int)(cz0 + u), (int)dl), d, n);
                 n_free += st == kRegionFree ? 1u : 0u;
                 n_occ += st == kRegionOccupied ? 1u : 0u;
                 n_unk += (st != kRegionFree && st != kRegionOccupied) ? 1u : 0u;   // UNKNOWN, and a BGK-LV map's UNCERTAIN

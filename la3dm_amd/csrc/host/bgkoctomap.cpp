@@ -12,6 +12,7 @@
 //   OcTree leaves / prune              src/bgkoctomap/bgkoctree.cpp:72-148, include/bgkoctomap/bgkoctree.h:62-147
 //   Occupancy                          src/bgkoctomap/bgkoctree_node.cpp:15-44
 #include "bgkoctomap.h"
+#include "region_contract.h"
 
 #include <algorithm>
 #include <parallel/algorithm>
@@ -775,56 +776,36 @@ void BGKOctoMap::raycast_many(const float *rays6, size_t n, uint32_t stop_mask, 
 
 // ---- dense region reads: box / columns.  The host forms below are the definition; the device kernels
 // (csrc/devmap_region.h) reproduce them bit for bit.
-void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, int kind, bool has_mandatory, const char *who,
-                               uint32_t g0[3], la3dm_region_info &info) const {
-    const bool columns = kind == 1;
-    const std::string w = std::string("BGKOctoMap::") + who;
-    if (lo3 == nullptr) throw std::invalid_argument(w + ": lo is NULL");
-    if (dims3 == nullptr) throw std::invalid_argument(w + ": dims is NULL");
-    for (int k = 0; k < 3; ++k)   // refused before any (int) conversion; false for NaN and inf
-        if (!(std::fabs(lo3[k] / resolution) < 1073741824.0f))
-            throw std::invalid_argument(w + ": lo must be finite with |lo / resolution| < 2^30");
-    for (int k = 0; k < 3; ++k)
-        if (dims3[k] == 0) throw std::invalid_argument(w + ": dims must be >= 1 on every axis");
-    const uint64_t ncol = (uint64_t)dims3[0] * dims3[1];
-    if (columns) {
-        if (ncol > (1ull << 30)) throw std::invalid_argument(w + ": dims: more than 2^30 columns");
-        if (dims3[2] > LA3DM_COLUMNS_MAX_NZ) throw std::invalid_argument(w + ": dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)");
-    } else if (kind == 2) {
-        if (ncol > LA3DM_DF_MAX_CELLS || ncol * dims3[2] > LA3DM_DF_MAX_CELLS)
-            throw std::invalid_argument(w + ": dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels");
-    } else if (kind == 3) {
-        const uint64_t pcol = ((uint64_t)dims3[0] + 2) * ((uint64_t)dims3[1] + 2);
-        if (std::max(dims3[0], std::max(dims3[1], dims3[2])) > LA3DM_FR_MAX_CELLS || pcol > LA3DM_FR_MAX_CELLS || pcol * ((uint64_t)dims3[2] + 2) > LA3DM_FR_MAX_CELLS)
-            throw std::invalid_argument(w + ": dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region");
-    } else if (ncol > LA3DM_BOX_MAX_CELLS || ncol * dims3[2] > LA3DM_BOX_MAX_CELLS) {
-        throw std::invalid_argument(w + ": dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels");
-    }
-    for (int k = 0; k < 3; ++k) {   // (a key only holds fields that fit it: test them before one is built)
-        const long long f = (long long)(lo3[k] / (double)block_size + 524288.5);
-        if (f < 0 || f >= (1ll << 20)) throw std::invalid_argument(w + ": lo: the block field leaves [0, 2^20)");
-    }
-    const BlockHashKey key = block_to_hash_key(lo3[0], lo3[1], lo3[2]);
-    const long long lim = 1ll << (block_depth - 1);
-    const long long b[3] = {(long long)(key >> 40), (long long)((key >> 20) & 0xFFFFF), (long long)(key & 0xFFFFF)};
-    const Block anchor(hash_key_to_block(key));
-    unsigned short c[3];
-    anchor.get_index(point3f(lo3[0], lo3[1], lo3[2]), c[0], c[1], c[2]);
+void BGKOctoMap::region_anchor(const float *lo3, const uint32_t *dims3, const la3dm_region::Query &q, bool has_mandatory,
+                               const char *who, uint32_t g0[3], la3dm_region_info &info) const {
+    la3dm_region::Anchor an;
+    const std::string refusal = la3dm_region::resolve(q, lo3, dims3, resolution, block_size, block_depth, true, has_mandatory, ".", an);
+    if (!refusal.empty()) throw std::invalid_argument(std::string("BGKOctoMap::") + who + ": " + refusal);
+    const Block anchor(hash_key_to_block(an.block_key));
+    const point3f o = anchor.get_point((unsigned short)an.cell[0], (unsigned short)an.cell[1], (unsigned short)an.cell[2]);
     for (int k = 0; k < 3; ++k) {
-        const long long first = b[k] * lim + c[k], last = first + (long long)dims3[k] - 1;
-        if (last / lim >= (1ll << 20)) throw std::invalid_argument(w + ": dims: the region's block fields leave [0, 2^20)");
-        if (kind == 3 && (first == 0 || (last + 1) / lim >= (1ll << 20)))
-            throw std::invalid_argument(w + ": dims: the block fields of the region padded by one voxel leave [0, 2^20)");
-        g0[k] = (uint32_t)first;
-        info.cell[k] = c[k];
+        g0[k] = an.g0[k];
+        info.cell[k] = an.cell[k];
+        info.origin[k] = o(k);
     }
-    info.block_key = key;
-    const point3f o = anchor.get_point(c[0], c[1], c[2]);
-    info.origin[0] = o.x();
-    info.origin[1] = o.y();
-    info.origin[2] = o.z();
-    if (!has_mandatory)
-        throw std::invalid_argument(w + (columns ? ": out.counts must not be NULL" : kind == 2 ? ": out: d2 or dist must not be NULL" : ": out.cls must not be NULL"));
+    info.block_key = an.block_key;
+}
+
+// (have, b) is the caller's cache of the last block looked up (have = -1 before the first call): a run along z asks the
+// block table once per block.  d = the leaf's layer, untouched where the block is missing.
+const OcTreeNode *BGKOctoMap::covering_leaf_at(uint32_t gx, uint32_t gy, uint32_t gz, BlockHashKey &have, const Block *&b, unsigned &d) const {
+    const unsigned dl = block_depth - 1u;
+    const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
+    if (key != have) {
+        auto it = block_arr.find(key);
+        b = it == block_arr.end() ? nullptr : it->second;
+        have = key;
+    }
+    if (b == nullptr) return nullptr;
+    const uint32_t cm = (1u << dl) - 1u;
+    unsigned n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
+    for (d = dl; d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED; --d) n >>= 3;
+    return &b->slab[layer_base(d) + n];
 }
 
 void BGKOctoMap::box(const float *lo3, const uint32_t *dims3, const la3dm_box_out &out, la3dm_region_info *info) const {
@@ -836,43 +817,22 @@ void BGKOctoMap::box(const float *lo3, const uint32_t *dims3, const la3dm_box_ou
     }
     uint32_t g0[3];
     la3dm_region_info inf;
-    region_anchor(lo3, dims3, false, out.cls != nullptr, "box", g0, inf);
+    region_anchor(lo3, dims3, la3dm_region::kBox, out.cls != nullptr, "box", g0, inf);
     if (info) *info = inf;
     const OcTreeNode dflt;
-    const unsigned dl = block_depth - 1u;
-    const uint32_t cm = (1u << dl) - 1u;
     const size_t ny = dims3[1], nz = dims3[2];
     for (uint32_t i = 0; i < dims3[0]; ++i)
         for (uint32_t j = 0; j < dims3[1]; ++j) {
-            const uint32_t gx = g0[0] + i, gy = g0[1] + j;
             const Block *b = nullptr;
             BlockHashKey have = -1;
             for (uint32_t k = 0; k < dims3[2]; ++k) {
-                const uint32_t gz = g0[2] + k;
-                const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
-                if (key != have) {
-                    auto it = block_arr.find(key);
-                    b = it == block_arr.end() ? nullptr : it->second;
-                    have = key;
-                }
+                unsigned d = 255;
+                const OcTreeNode *leaf = covering_leaf_at(g0[0] + i, g0[1] + j, g0[2] + k, have, b, d);
                 const size_t o = ((size_t)i * ny + j) * nz + k;
-                if (b == nullptr) {
-                    out.cls[o] = LA3DM_RAY_MISSING;
-                    if (out.leaf_depth) out.leaf_depth[o] = 255;
-                    if (out.A) out.A[o] = dflt.m_A;
-                    if (out.B) out.B[o] = dflt.m_B;
-                    continue;
-                }
-                unsigned d = dl, n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
-                while (d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED) {
-                    --d;
-                    n >>= 3;
-                }
-                const OcTreeNode &leaf = b->slab[layer_base(d) + n];
-                out.cls[o] = (uint8_t)leaf.state;
+                out.cls[o] = leaf ? (uint8_t)leaf->state : (uint8_t)LA3DM_RAY_MISSING;
                 if (out.leaf_depth) out.leaf_depth[o] = (uint8_t)d;
-                if (out.A) out.A[o] = leaf.m_A;
-                if (out.B) out.B[o] = leaf.m_B;
+                if (out.A) out.A[o] = (leaf ? leaf : &dflt)->m_A;
+                if (out.B) out.B[o] = (leaf ? leaf : &dflt)->m_B;
             }
         }
 }
@@ -886,34 +846,18 @@ void BGKOctoMap::columns(const float *lo3, const uint32_t *dims3, const la3dm_co
     }
     uint32_t g0[3];
     la3dm_region_info inf;
-    region_anchor(lo3, dims3, true, out.counts != nullptr, "columns", g0, inf);
+    region_anchor(lo3, dims3, la3dm_region::kColumns, out.counts != nullptr, "columns", g0, inf);
     if (info) *info = inf;
-    const unsigned dl = block_depth - 1u;
-    const uint32_t cm = (1u << dl) - 1u;
     for (uint32_t i = 0; i < dims3[0]; ++i)
         for (uint32_t j = 0; j < dims3[1]; ++j) {
-            const uint32_t gx = g0[0] + i, gy = g0[1] + j;
             uint32_t counts[4] = {0, 0, 0, 0};
             int32_t low = -1, top = -1;
             const Block *b = nullptr;
             BlockHashKey have = -1;
             for (uint32_t k = 0; k < dims3[2]; ++k) {
-                const uint32_t gz = g0[2] + k;
-                const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
-                if (key != have) {
-                    auto it = block_arr.find(key);
-                    b = it == block_arr.end() ? nullptr : it->second;
-                    have = key;
-                }
-                unsigned cls = LA3DM_RAY_MISSING;
-                if (b != nullptr) {
-                    unsigned d = dl, n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
-                    while (d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED) {
-                        --d;
-                        n >>= 3;
-                    }
-                    cls = (unsigned)b->slab[layer_base(d) + n].state;
-                }
+                unsigned d;
+                const OcTreeNode *leaf = covering_leaf_at(g0[0] + i, g0[1] + j, g0[2] + k, have, b, d);
+                const unsigned cls = leaf ? (unsigned)leaf->state : (unsigned)LA3DM_RAY_MISSING;
                 ++counts[cls < 4 ? cls : 2];   // (a BGK-LV map's UNCERTAIN leaves count with UNKNOWN)
                 if (cls == (unsigned)State::OCCUPIED) {
                     if (low < 0) low = (int32_t)k;
@@ -958,14 +902,11 @@ void BGKOctoMap::distance_field(const float *lo3, const uint32_t *dims3, uint32_
             throw std::runtime_error(std::string("BGKOctoMap::distance_field: ") + la3dm_last_error(ctx));
         return;
     }
-    const std::string w = "BGKOctoMap::distance_field";
-    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu))
-        throw std::invalid_argument(w + ": obstacle_mask must hold at least one of the bits 0x1F and no other");
-    if (radius == 0 || radius > LA3DM_DF_MAX_RADIUS)
-        throw std::invalid_argument(w + ": radius must lie in [1, LA3DM_DF_MAX_RADIUS (1024)]");
+    const std::string refusal = la3dm_region::distance_check(obstacle_mask, radius);
+    if (!refusal.empty()) throw std::invalid_argument("BGKOctoMap::distance_field: " + refusal);
     uint32_t g0[3];
     la3dm_region_info inf;
-    region_anchor(lo3, dims3, 2, out.d2 != nullptr || out.dist != nullptr, "distance_field", g0, inf);
+    region_anchor(lo3, dims3, la3dm_region::kDistance, out.d2 != nullptr || out.dist != nullptr, "distance_field", g0, inf);
     if (info) *info = inf;
     const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2], n = nx * ny * nz;
     std::vector<uint8_t> cls(n);
@@ -1017,17 +958,11 @@ void BGKOctoMap::frontier(const float *lo3, const uint32_t *dims3, uint32_t open
         return;
     }
     const std::string w = "BGKOctoMap::frontier";
-    if (open_mask == 0 || (open_mask & ~0x1Fu))
-        throw std::invalid_argument(w + ": open_mask must hold at least one of the bits 0x1F and no other");
-    if (unknown_mask == 0 || (unknown_mask & ~0x1Fu))
-        throw std::invalid_argument(w + ": unknown_mask must hold at least one of the bits 0x1F and no other");
-    if (connectivity != 6 && connectivity != 18 && connectivity != 26)
-        throw std::invalid_argument(w + ": connectivity must be 6, 18 or 26");
-    if (min_neighbours == 0 || min_neighbours > connectivity)
-        throw std::invalid_argument(w + ": min_neighbours must lie in [1, connectivity]");
+    const std::string refusal = la3dm_region::frontier_check(open_mask, unknown_mask, connectivity, min_neighbours);
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
     uint32_t g0[3];
     la3dm_region_info inf;
-    region_anchor(lo3, dims3, 3, true, "frontier", g0, inf);
+    region_anchor(lo3, dims3, la3dm_region::kFrontier, true, "frontier", g0, inf);
     if (cap > 0 && out.index == nullptr) throw std::invalid_argument(w + ": out.index must not be NULL with cap > 0");
     if (n_found == nullptr) throw std::invalid_argument(w + ": n_found is NULL");
     if (info) *info = inf;
@@ -1035,31 +970,15 @@ void BGKOctoMap::frontier(const float *lo3, const uint32_t *dims3, uint32_t open
     const size_t PY = ny + 2, PZ = nz + 2, P = (nx + 2) * PY * PZ;
     // classes of the padded box: box's loop at the lattice positions g0 - 1 + (i, j, k)
     std::vector<uint8_t> cls(P);
-    const unsigned dl = block_depth - 1u;
-    const uint32_t cm = (1u << dl) - 1u;
 #pragma omp parallel for schedule(static)
     for (size_t row = 0; row < (nx + 2) * PY; ++row) {
         const uint32_t gx = g0[0] - 1u + (uint32_t)(row / PY), gy = g0[1] - 1u + (uint32_t)(row % PY);
         const Block *b = nullptr;
         BlockHashKey have = -1;
         for (size_t k = 0; k < PZ; ++k) {
-            const uint32_t gz = g0[2] - 1u + (uint32_t)k;
-            const BlockHashKey key = ((BlockHashKey)(gx >> dl) << 40) | ((BlockHashKey)(gy >> dl) << 20) | (BlockHashKey)(gz >> dl);
-            if (key != have) {
-                auto it = block_arr.find(key);
-                b = it == block_arr.end() ? nullptr : it->second;
-                have = key;
-            }
-            uint8_t c = LA3DM_RAY_MISSING;
-            if (b != nullptr) {
-                unsigned d = dl, n = (unsigned)(Block::get_node((unsigned short)(gx & cm), (unsigned short)(gy & cm), (unsigned short)(gz & cm)) & 0xFFFF);
-                while (d > 0 && b->slab[layer_base(d) + n].state == State::PRUNED) {
-                    --d;
-                    n >>= 3;
-                }
-                c = (uint8_t)b->slab[layer_base(d) + n].state;
-            }
-            cls[row * PZ + k] = c;
+            unsigned d;
+            const OcTreeNode *leaf = covering_leaf_at(gx, gy, g0[2] - 1u + (uint32_t)k, have, b, d);
+            cls[row * PZ + k] = leaf ? (uint8_t)leaf->state : (uint8_t)LA3DM_RAY_MISSING;
         }
     }
     std::vector<ptrdiff_t> offs;

@@ -30,6 +30,10 @@
 
 #include "../../../include/la3dm_hip.h"
 
+namespace la3dm_region {
+struct Query;   // region_contract.h
+}
+
 extern "C" void la3dm_node_ab(const void *node, float *A, float *B);  // (m_A, m_B) of an Occupancy
 
 namespace la3dm {
@@ -515,10 +519,12 @@ protected:
     la3dm_devmap *dmap = nullptr;
     mutable bool mirror_dirty = false;
     mutable uint64_t mirror_sync_count = 0;
-    /// checks of a region query in the contract's order + its anchor: global voxel index g0 of voxel (0, 0, 0), info
-    /// (kind: 0 box, 1 columns, 2 distance field, 3 frontier)
-    void region_anchor(const float *lo3, const uint32_t *dims3, int kind, bool has_mandatory, const char *who,
+    /// checks of a region query in the contract's order (region_contract.h) + its anchor: global voxel index g0 of voxel
+    /// (0, 0, 0), info
+    void region_anchor(const float *lo3, const uint32_t *dims3, const la3dm_region::Query &q, bool has_mandatory, const char *who,
                        uint32_t g0[3], la3dm_region_info &info) const;
+    /// leaf that covers global voxel (gx, gy, gz), null where the map has no block there
+    const OcTreeNode *covering_leaf_at(uint32_t gx, uint32_t gy, uint32_t gz, BlockHashKey &have, const Block *&b, unsigned &d) const;
     la3dm_params create_params;   // what the context was created with (lut_xyz is re-pointed on use)
     void create_context();        // la3dm_create + the device-resident pool from create_params and the current statics
     void reconfigure(float resolution, unsigned short depth);

@@ -1,0 +1,102 @@
+// region_contract.h — what a valid region query is (include/la3dm_hip.h "Region"), once for the device library
+// (devmap.hip) and the host map (bgkoctomap.cpp): the limits of each query, their order, their texts and the anchor
+// arithmetic.  Host code only.  A check answers with the text of the refusal, without the caller's prefix, or with an
+// empty string; how a refusal is reported (an error code and a stored text, an exception) is the caller's business.
+#ifndef LA3DM_REGION_CONTRACT_H
+#define LA3DM_REGION_CONTRACT_H
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "../../../include/la3dm_hip.h"
+
+namespace la3dm_region {
+
+struct Query {
+    uint64_t max_cells;       // limit on the number of voxels (columns: of columns)
+    const char *limit_text;
+    bool columns;             // the limit counts columns, and nz has LA3DM_COLUMNS_MAX_NZ as a limit of its own
+    bool padded;              // limit and block-field range are taken on the region padded by one voxel on every side
+    const char *mandatory;    // refusal when the mandatory output is missing ("->" stands for the caller's member access)
+};
+
+constexpr Query kBox = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, false, "out->cls must not be NULL"};
+constexpr Query kColumns = {1ull << 30, "dims: more than 2^30 columns", true, false, "out->counts must not be NULL"};
+constexpr Query kDistance = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, "out: d2 or dist must not be NULL"};
+constexpr Query kFrontier = {LA3DM_FR_MAX_CELLS, "dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
+
+struct Anchor {
+    uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
+    int32_t cell[3];     // cell of lo in its block
+    float center[3];     // centre of that block
+    int64_t block_key;
+    uint64_t total;      // voxels of the region (columns: columns)
+};
+
+// Every check of a region in the contract's order — lo, dims, the limits and the block-field range before any buffer is
+// looked at — and the anchor, the only floating-point work of a query.  `member` is "->" or ".": how the caller's texts
+// name a member of out.
+inline std::string resolve(const Query &q, const float *lo, const uint32_t *dims, float resolution, float block_size,
+                           unsigned block_depth, bool has_out, bool has_mandatory, const char *member, Anchor &a) {
+    if (!lo) return "lo is NULL";
+    if (!dims) return "dims is NULL";
+    for (int k = 0; k < 3; ++k)   // refused before any (int) conversion; false for NaN and inf
+        if (!(std::fabs(lo[k] / resolution) < 1073741824.0f)) return "lo must be finite with |lo / resolution| < 2^30";
+    for (int k = 0; k < 3; ++k)
+        if (dims[k] == 0) return "dims must be >= 1 on every axis";
+    const uint64_t pad = q.padded ? 2 : 0, ncol = (uint64_t)dims[0] * dims[1], pcol = (dims[0] + pad) * (dims[1] + pad);
+    if (q.columns) {
+        if (ncol > q.max_cells) return q.limit_text;
+        if (dims[2] > LA3DM_COLUMNS_MAX_NZ) return "dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)";
+    } else if (std::max(dims[0], std::max(dims[1], dims[2])) > q.max_cells || pcol > q.max_cells || pcol * (dims[2] + pad) > q.max_cells) {
+        return q.limit_text;   // (an axis is tested first: the products of three such axes need not fit 64 bits)
+    }
+    a.total = q.columns ? ncol : ncol * dims[2];
+    const long long lim = 1ll << (block_depth - 1), top = 1ll << 20;
+    long long b[3];
+    for (int k = 0; k < 3; ++k) {   // (a key only holds fields that fit it: test them before one is built)
+        b[k] = (long long)((double)lo[k] / (double)block_size + 524288.5);   // block_to_hash_key, one axis
+        if (b[k] < 0 || b[k] >= top) return "lo: the block field leaves [0, 2^20)";
+    }
+    a.block_key = 0;
+    for (int k = 0; k < 3; ++k) {
+        a.center[k] = (float)(b[k] - 524288) * block_size;                                  // hash_key_to_block
+        const int t = (int)((lo[k] - a.center[k]) / resolution + (float)(lim / 2));         // Block::get_index: truncation, clamped
+        a.cell[k] = std::max(0, std::min(t, (int)lim - 1));
+        const long long first = b[k] * lim + a.cell[k], last = first + (long long)dims[k] - 1;
+        if (last / lim >= top) return "dims: the region's block fields leave [0, 2^20)";
+        if (q.padded && (first == 0 || (last + 1) / lim >= top))
+            return "dims: the block fields of the region padded by one voxel leave [0, 2^20)";
+        a.g0[k] = (uint32_t)first;
+        a.block_key = (a.block_key << 20) | b[k];
+    }
+    if (!has_out) return "out is NULL";
+    if (!has_mandatory) {
+        std::string text(q.mandatory);
+        const size_t at = text.find("->");
+        return at == std::string::npos ? text : text.replace(at, 2, member);
+    }
+    return "";
+}
+
+// the checks of distance_field's own arguments, before the region's
+inline std::string distance_check(uint32_t obstacle_mask, uint32_t radius) {
+    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu)) return "obstacle_mask must hold at least one of the bits 0x1F and no other";
+    if (radius == 0 || radius > LA3DM_DF_MAX_RADIUS) return "radius must lie in [1, LA3DM_DF_MAX_RADIUS (1024)]";
+    return "";
+}
+
+// the checks of frontier's own arguments, before the region's
+inline std::string frontier_check(uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours) {
+    if (open_mask == 0 || (open_mask & ~0x1Fu)) return "open_mask must hold at least one of the bits 0x1F and no other";
+    if (unknown_mask == 0 || (unknown_mask & ~0x1Fu)) return "unknown_mask must hold at least one of the bits 0x1F and no other";
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) return "connectivity must be 6, 18 or 26";
+    if (min_neighbours == 0 || min_neighbours > connectivity) return "min_neighbours must lie in [1, connectivity]";
+    return "";
+}
+
+}  // namespace la3dm_region
+
+#endif

@@ -172,6 +172,40 @@ def test_arguments(built):
     assert empty.mirror_syncs() == 0
 
 
+def _anchor_coordinates(res, bs):
+    """coordinates at and next to every boundary of the anchor arithmetic (voxel and block faces and centres, each with
+    its two float32 neighbours), a seeded uniform sample and a few far values"""
+    vals = []
+    for k in range(-12, 13):
+        for v in (np.float32(k) * res, np.float32(k + 0.5) * res, np.float32(k) * bs, np.float32(k + 0.5) * bs):
+            v = np.float32(v)
+            vals += [v, np.nextafter(v, np.float32(np.inf)), np.nextafter(v, np.float32(-np.inf))]
+    vals += list(np.random.default_rng(7).uniform(-50.0, 50.0, 600).astype(np.float32))
+    vals += [1.0e5, -1.0e5, 52428.0, -52428.0]
+    return np.array(vals, np.float32)
+
+
+@pytest.mark.parametrize("depth", [3, 4])
+def test_anchor_equals_the_yardstick_at_every_boundary(built, depth):
+    """the anchor arithmetic (block field in float64, centre and cell in float32, the cell truncated and clamped) serves
+    every region query of the host map and of the device library from one place: origin (bits), block_key and cell of
+    columns(lo, (1, 1, 1)) against region_cases.anchor, every case accepted"""
+    import la3dm_amd
+    m = la3dm_amd.BGKOctoMap(**dict(R.YAML, block_depth=depth), device=-1)
+    res = np.float32(m.get_resolution())
+    bs = np.float32(np.float32(2.0 ** (depth - 1)) * res)
+    vals = _anchor_coordinates(res, bs)
+    rng = np.random.default_rng(13)
+    los = np.stack([vals, vals[rng.permutation(vals.size)], vals[rng.permutation(vals.size)]], 1)
+    assert los.shape == (904, 3)
+    for lo in los:
+        got = m.columns(lo, (1, 1, 1))
+        b, c, _, origin = R.anchor(lo, res, depth)
+        assert got["block_key"] == (b[0] << 40) | (b[1] << 20) | b[2], (lo, got["block_key"], b)
+        assert (np.asarray(got["cell"]) == np.array(c)).all(), (lo, got["cell"], c)
+        assert (np.asarray(got["origin"], np.float32).view(np.uint32) == origin.view(np.uint32)).all(), (lo, got["origin"], origin)
+
+
 def test_header_declares_and_library_exports_the_new_symbols(built):
     """item 5"""
     from la3dm_amd import _lib
