@@ -1,0 +1,280 @@
+// bgk_scan1_kernels.h — the BGK predict + fuse scan of full blocks in ONE launch (block_depth 3, bgk_sum 1, tables).
+//
+// bgk_predict_fuse_t1 is a COPY of bgk_predict_fuse_t<kTrig, false> (bgk_kernels.h) with the work of the bgk_prepare
+// launch folded in: it reads the caller's unscaled training points and divides them by ell as it stages them, and it
+// forms the descriptor of the 7 neighbour ranges from nbr / train_off in its own prologue.  It stands beside the
+// original, in a header of its own, for one reason only: bgk_kernels.h belongs to the source closure that the counter
+// files under profiles/ are stamped with (tests/test_profiles_stamps_cpu.py), so no line of it can change without
+// recording all three counter files again.  The pull request that records them again ("BGK scan: merge
+// bgk_predict_fuse_t1 into bgk_kernels.h and re-stamp the counter files") folds this kernel back into
+// bgk_predict_fuse_t and deletes this header.  Until then: a change to the table path of one kernel belongs in the other too.
+//
+// Everything else — device functions, the LA3DM_TP_* macros, WaveLdsT, the ablation flags — is bgk_kernels.h's, used
+// from here (include this header after it).  Same pairs, same fp32 terms in the same order: alpha, beta and state are
+// bit-identical to the two-launch path (tests/test_bgk_one_launch_gpu.py).
+#pragma once
+#include "bgk_kernels.h"
+
+namespace la3dm_dev {
+
+// BgkArgs as bgk_predict_fuse_t takes them, except: pts = the caller's UNSCALED points (x, y, z, label); blk_desc,
+// nbr_range and label_seq are not read.  Full blocks only (the host verifies it from the leaf count), tpb_shift 0 or more,
+// one descriptor per block (desc_shift is not read: the host takes this path at block_depth 3 only).
+template <int kTrig>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) void bgk_predict_fuse_t1(BgkArgs a) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_lds[5120];
+    const uint32_t task = bgk_task_of_workgroup(a);
+    if (task >= a.n_tasks) return;
+    const uint32_t blk = task >> a.tpb_shift;
+    // the block's scalar inputs — leaf range, the 7 neighbour indices, centre — in one round trip.  The row of a block is
+    // 7 words at a 4-byte-aligned address and the last block's row ends the array: 4 + 2 + 1 words, never word 7.
+    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+    typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+    u32x4 n03;
+    u32x2 n45, lbr;
+    uint32_t n6;
+    float cx, cy, cz;
+    asm("s_load_dwordx2 %[lb], %[lop], 0x0\n"
+        "s_load_dwordx4 %[n03], %[nr], 0x0\n"
+        "s_load_dwordx2 %[n45], %[nr], 0x10\n"
+        "s_load_dword %[n6], %[nr], 0x18\n"
+        "s_load_dword %[cx], %[ctr], 0x0\n"
+        "s_load_dword %[cy], %[ctr], 0x4\n"
+        "s_load_dword %[cz], %[ctr], 0x8\n"
+        "s_waitcnt lgkmcnt(0)\n"
+        : [lb] "=&s"(lbr), [n03] "=&s"(n03), [n45] "=&s"(n45), [n6] "=&s"(n6), [cx] "=&s"(cx), [cy] "=&s"(cy), [cz] "=&s"(cz)
+        : [lop] "s"(a.leaf_off + blk), [nr] "s"(a.nbr + 7 * (size_t)blk), [ctr] "s"(a.blk_center + 3 * (size_t)blk));
+    const uint32_t lb0 = lbr[0];
+    if (lbr[1] - lb0 != 1u << (3u * (a.depth - 1u))) return;  // (the host vouched for full blocks: a tile that is not is left untouched)
+    // second round trip: train_off[tb], train_off[tb + 1] of every neighbour that exists (tb < 0: the block's leaf range is
+    // read instead — two words that are always there, train_off may hold a single one — and dropped), then bgk_prepare's
+    // thirteen words at shift 0 in scalar registers: adj[b] = first point of neighbour b minus the flat index where b starts, pend[b] = flat index where b ends, M = pend[6]
+    uint32_t adj[7], pend[7];
+    {
+        const int32_t tb[7] = {(int32_t)n03[0], (int32_t)n03[1], (int32_t)n03[2], (int32_t)n03[3], (int32_t)n45[0], (int32_t)n45[1], (int32_t)n6};
+        u32x2 r[7];
+        auto pair = [&](int b) { return tb[b] >= 0 ? a.train_off + tb[b] : a.leaf_off + blk; };
+        asm("s_load_dwordx2 %0, %7, 0x0\n"
+            "s_load_dwordx2 %1, %8, 0x0\n"
+            "s_load_dwordx2 %2, %9, 0x0\n"
+            "s_load_dwordx2 %3, %10, 0x0\n"
+            "s_load_dwordx2 %4, %11, 0x0\n"
+            "s_load_dwordx2 %5, %12, 0x0\n"
+            "s_load_dwordx2 %6, %13, 0x0\n"
+            "s_waitcnt lgkmcnt(0)\n"
+            : "=&s"(r[0]), "=&s"(r[1]), "=&s"(r[2]), "=&s"(r[3]), "=&s"(r[4]), "=&s"(r[5]), "=&s"(r[6])
+            : "s"(pair(0)), "s"(pair(1)), "s"(pair(2)), "s"(pair(3)), "s"(pair(4)), "s"(pair(5)), "s"(pair(6)));
+        uint32_t pre = 0;
+#pragma unroll
+        for (int b = 0; b < 7; ++b) {
+            const uint32_t first = tb[b] >= 0 ? r[b][0] : 0u, cnt = tb[b] >= 0 ? r[b][1] - r[b][0] : 0u;
+            adj[b] = first - pre;
+            pre += cnt;
+            pend[b] = pre;
+        }
+    }
+    const uint32_t M = pend[6];
+    WaveLdsT &L = *reinterpret_cast<WaveLdsT *>(s_lds);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t tile = task & ((1u << a.tpb_shift) - 1u);
+    const uint32_t li = lb0 + tile * kWave + lane;
+    // LeafIterator order is descending: the leaf at list position j of a full block has the finest-level index
+    // 8^(depth-1) - 1 - j, so the key needs no load
+    const uint32_t n_fine = 1u << (3u * (a.depth - 1u));
+    const uint32_t lut_idx = lut_layer_base(a.depth - 1u) + (n_fine - 1u - tile * kWave) - lane;
+
+    // the UNSCALED points of flat indices cb + lane (chunk() divides them by ell); a lane past the end reads the range's
+    // last point (the caller masks it).  The descriptor stays in scalar registers for the whole tile; its offsets are
+    // copied to VGPRs per call (a v_cndmask reads one scalar operand, and its mask is one).
+    auto gather = [&](uint32_t cb) {
+        uint32_t adjv[7];
+#pragma unroll
+        for (int b = 0; b < 7; ++b) {
+            adjv[b] = adj[b];
+            asm volatile("" : "+v"(adjv[b]));
+        }
+        const uint32_t f = min(cb + lane, M - 1u);
+        uint32_t ad;
+        unsigned long long m1, m2, m3, m4, m5, m6;
+        asm("v_cmp_le_u32 %[m1], %[e0], %[f]\n"
+            "v_cmp_le_u32 %[m2], %[e1], %[f]\n"
+            "v_cmp_le_u32 %[m3], %[e2], %[f]\n"
+            "v_cmp_le_u32 %[m4], %[e3], %[f]\n"
+            "v_cmp_le_u32 %[m5], %[e4], %[f]\n"
+            "v_cmp_le_u32 %[m6], %[e5], %[f]\n"
+            "v_cndmask_b32 %[ad], %[a0], %[a1], %[m1]\n"
+            "v_cndmask_b32 %[ad], %[ad], %[a2], %[m2]\n"
+            "v_cndmask_b32 %[ad], %[ad], %[a3], %[m3]\n"
+            "v_cndmask_b32 %[ad], %[ad], %[a4], %[m4]\n"
+            "v_cndmask_b32 %[ad], %[ad], %[a5], %[m5]\n"
+            "v_cndmask_b32 %[ad], %[ad], %[a6], %[m6]\n"
+            : [ad] "=&v"(ad), [m1] "=&s"(m1), [m2] "=&s"(m2), [m3] "=&s"(m3), [m4] "=&s"(m4), [m5] "=&s"(m5), [m6] "=&s"(m6)
+            : [f] "v"(f), [e0] "s"(pend[0]), [e1] "s"(pend[1]), [e2] "s"(pend[2]), [e3] "s"(pend[3]), [e4] "s"(pend[4]),
+              [e5] "s"(pend[5]), [a0] "v"(adjv[0]), [a1] "v"(adjv[1]), [a2] "v"(adjv[2]), [a3] "v"(adjv[3]), [a4] "v"(adjv[4]),
+              [a5] "v"(adjv[5]), [a6] "v"(adjv[6]));
+        return a.pts[f + ad];
+    };
+#if LA3DM_T_EARLY_AB
+    const float A0 = a.alpha[li], B0 = a.beta[li];  // needed by the epilogue only: loaded here, a round trip off the tile's tail
+#endif
+    if (M == 0u) {  // no training point in the 7 blocks: nothing reaches the tile
+        if (!(a.flags & 1u)) a.state[li] = 0;
+        else {  // insert_training_data: update() runs with (0, 0)
+            const float A = a.alpha[li], B = a.beta[li];
+            a.state[li] = (uint8_t)(classify(A, B, a) | 0x80u);
+        }
+        return;
+    }
+    float4 pc = gather(0), pn = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (M > (uint32_t)kWave) pn = gather(kWave);
+
+    const float4 off4 = a.lut[lut_idx];
+    const float xs0 = div_by_ell(off4.x + cx, a.ell, a.inv_ell), ys0 = div_by_ell(off4.y + cy, a.ell, a.inv_ell),
+                zs0 = div_by_ell(off4.z + cz, a.ell, a.inv_ell);
+    L.acc0[lane] = 0.0;
+    L.acc1[lane] = 0.0;
+
+    // the four coordinates per axis.  Lane l holds leaf index c = 63 - l of the cube; c = (i1 j1 k1 i0 j0 k0) in binary:
+    // child number i*4 + j*2 + k at the parent level (bits 5-3) and at the leaf level (bits 2-0).
+    // Axis value r = 2 * (high bit) + (low bit); the lanes read below have the other two axes' bits clear.
+    auto rl = [](float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); };
+    const la3dm_v2f X01 = {rl(xs0, 63), rl(xs0, 59)}, X23 = {rl(xs0, 31), rl(xs0, 27)};
+    const la3dm_v2f Y01 = {rl(ys0, 63), rl(ys0, 61)}, Y23 = {rl(ys0, 47), rl(ys0, 45)};
+    const la3dm_v2f Z01 = {rl(zs0, 63), rl(zs0, 62)}, Z23 = {rl(zs0, 55), rl(zs0, 54)};
+    const uint32_t c6 = lane ^ 63u;
+    const uint32_t ix = ((c6 >> 4) & 2u) | ((c6 >> 2) & 1u), iy = ((c6 >> 3) & 2u) | ((c6 >> 1) & 1u), iz = ((c6 >> 2) & 2u) | (c6 & 1u);
+    const uint32_t tab_base = (uint32_t)(uintptr_t)&L.tab[0][0][0];
+    constexpr uint32_t kRowB = 4u * 16u, kHalfB = 12u * kRowB;
+    static_assert(kTabSlots == 32, "the B loop below walks two halves of 16 slots");
+    const uint32_t ax0 = tab_base + ix * kRowB, ay0 = tab_base + (4u + iy) * kRowB, az0 = tab_base + (8u + iz) * kRowB;
+    const uint32_t ring_base = (uint32_t)(uintptr_t)&L.ring[0];
+    const uint32_t w0 = (uint32_t)(uintptr_t)&L.acc0[0] + 8u * lane;
+    if (w0 & 0x200u) __builtin_trap();   // (s_lds is the kernel's only static LDS object: it starts at LDS address 0)
+    static_assert(offsetof(WaveLdsT, acc1) - offsetof(WaveLdsT, acc0) == 512, "c_eval adds 512 to the address of acc0[leaf] for a label-1 pair");
+    const float hit_t = __uint_as_float(kHitTBits);
+    const uint32_t tail_cap = ring_base + 8u * (uint32_t)(kRingT - 4 * kWave);
+    uint32_t tailb = ring_base;  // LDS byte address of the ring's first free entry
+
+    // C: lane evaluates ring entry i and adds k to the leaf's accumulator 0 or 1 (the sign of d2 is the label)
+    auto c_eval = [&](uint32_t i) {
+        const uint2 e = L.ring[i];
+        const float kv = cov_sparse_fast<kTrig, true, true>(sqrt_cr(__builtin_fabsf(__uint_as_float(e.x))), a.sf2);
+        const double kd = (double)kv;
+        const uint32_t ad = e.y | ((e.x >> 22) & 0x200u);  // label 1 (negative d2): acc1[leaf], 512 bytes up
+        asm volatile("ds_add_f64 %0, %1\n" : : "v"(ad), "v"(kd) : "memory");
+    };
+    // C round: the full 64-entry batches, taken from the ring's END so that the remainder (< 64 entries) stays at the front
+    auto c_flush = [&]() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t tail = (tailb - ring_base) >> 3;
+        const uint32_t rem = tail & 63u;
+        if (!(a.flags & 0x100u))  // 0x100: profiling ablation
+            for (uint32_t p = rem; p < tail; p += kWave) c_eval(p + lane);
+        tailb = ring_base + 8u * rem;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    };
+
+    // A + B for one chunk of 64 training points (lane = point)
+    auto chunk = [&](const float4 &pu, const uint32_t cb) {
+        // x / ell, y / ell, z / ell as bgk_prepare's IEEE divisions leave them (div_by_ell is the correctly rounded quotient;
+        // a zero may come out with the other sign, which the squares below remove); the label is untouched
+        const float px = div_by_ell(pu.x, a.ell, a.inv_ell), py = div_by_ell(pu.y, a.ell, a.inv_ell), pz = div_by_ell(pu.z, a.ell, a.inv_ell);
+        const la3dm_v2f bx = {px, px}, by = {py, py}, bz = {pz, pz};
+        la3dm_v2f x01 = bx - X01, x23 = bx - X23, y01 = by - Y01, y23 = by - Y23, z01 = bz - Z01, z23 = bz - Z23;
+        x01 *= x01, x23 *= x23, y01 *= y01, y23 *= y23, z01 *= z01, z23 *= z23;
+        const float mx = fminf(fminf(x01.x, x01.y), fminf(x23.x, x23.y));
+        const float my = fminf(fminf(y01.x, y01.y), fminf(y23.x, y23.y));
+        const float mz = fminf(fminf(z01.x, z01.y), fminf(z23.x, z23.y));
+        // min over the 64 leaves of d2 (+ and * are monotone): staged iff some leaf hits (lanes past the end hold a
+        // copy of the last point: masked)
+        const bool keep = mx + (my + mz) < hit_t && cb + lane < M;
+        const unsigned long long m = __ballot(keep);
+        if (m == 0ull) return;
+        const float sg = 1.0f - (pu.w + pu.w);  // label 0 -> +1, label 1 -> -1 (exact)
+        const la3dm_v2f s2 = {sg, sg};
+        x01 *= s2, x23 *= s2, y01 *= s2, y23 *= s2, z01 *= s2, z23 *= s2;
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+        const uint32_t n = (uint32_t)__popcll(m);
+        for (uint32_t base = 0; base < n; base += kTabSlots) {
+            const uint32_t nr = min(n - base, (uint32_t)kTabSlots), ngroup = (nr + 3u) >> 2;
+            // pad the last column group with entries no leaf can reach (an X row suffices: the sum stays huge or NaN)
+            if (lane < 4u && nr + lane < 4u * ngroup) {
+                float big;
+                asm volatile("v_mov_b32 %0, 0x5e268890" : "=v"(big));
+#pragma unroll
+                for (int r = 0; r < 4; ++r) L.tab[(nr + lane) >> 4][r][(nr + lane) & 15u] = big;
+            }
+            const uint32_t slot = rank - base;
+            if (keep && slot < (uint32_t)kTabSlots) {
+                float(&T)[12][16] = L.tab[slot >> 4];
+                const uint32_t c = slot & 15u;
+                T[0][c] = x01.x, T[1][c] = x01.y, T[2][c] = x23.x, T[3][c] = x23.y;
+                T[4][c] = y01.x, T[5][c] = y01.y, T[6][c] = y23.x, T[7][c] = y23.y;
+                T[8][c] = z01.x, T[9][c] = z01.y, T[10][c] = z23.x, T[11][c] = z23.y;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            if (a.flags & 0x200u) continue;  // 0x200: profiling ablation
+            uint32_t aX = ax0, aY = ay0, aZ = az0;
+            for (uint32_t g = 0; g < ngroup; g += 2u) {  // two column groups per trip: the three row addresses move once
+                uint32_t st;
+                float tr;
+                unsigned long long hm0, hm1, hm2, hm3;
+                LA3DM_TP_TRIP("0");
+                if (tailb > tail_cap) c_flush();
+                if (g + 1u < ngroup) {
+                    LA3DM_TP_TRIP("16");
+                    if (tailb > tail_cap) c_flush();
+                }
+                const uint32_t step = g == 2u ? kHalfB - 32u : 32u;   // column groups 0-3 sit in the first half, 4-7 in the second
+                aX += step, aY += step, aZ += step;
+            }
+            // (the next sub-round overwrites the table: LDS operations of a wave complete in order)
+        }
+    };
+
+    for (uint32_t cb = 0;;) {
+        chunk(pc, cb);
+        cb += kWave;
+        if (cb >= M) break;
+        pc = pn;
+        if (cb + kWave < M) pn = gather(cb + kWave);
+    }
+
+    // the tile's last, partly filled batch(es)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    {
+        const uint32_t tail = (tailb - ring_base) >> 3;
+        if (!(a.flags & 0x100u))
+            for (uint32_t p = 0; p < tail; p += kWave)
+                if (p + lane < tail) c_eval(p + lane);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+
+    {
+        const double s0 = L.acc0[lane], s1 = L.acc1[lane];
+        const double K = s0 + s1, Y = s1;
+        uint32_t lw = li;
+        asm volatile("" : "+v"(lw));
+        if (K > 0.0 || (a.flags & 1u) != 0u) {  // flag 1: insert_training_data, update() runs unconditionally
+#if LA3DM_T_EARLY_AB
+            const float A = (float)((double)A0 + Y);
+            const float B = (float)((double)B0 + (K - Y));
+#else
+            const float A = (float)((double)a.alpha[lw] + Y);
+            const float B = (float)((double)a.beta[lw] + (K - Y));
+#endif
+            a.alpha[lw] = A;
+            a.beta[lw] = B;
+            a.state[lw] = (uint8_t)(classify_fast(A, B, a) | 0x80u);
+        } else {
+            a.state[lw] = 0;
+        }
+    }
+}
+
+}  // namespace la3dm_dev

@@ -26,6 +26,8 @@ struct la3dm_ctx {
                            // (bgk_predict_fuse_v5, bit-identical to the CPU restatement); env LA3DM_BGK_SUM sets the default
     int opt_bgk_tables = 1;  // bgk_sum = 1 only: 1 (default) = bgk_predict_fuse_t (per-axis distance tables for aligned 4x4x4 tiles, the
                              // other tiles through the general path in the same launch), 0 = bgk_predict_fuse_r for every tile
+    int opt_bgk_one_launch = 1;  // bgk_sum = 1, tables, block_depth 3, a scan of full blocks only: 1 (default) = one launch, bgk_predict_fuse_t1 on the caller's
+                                 // unscaled points (bgk_scan1_kernels.h), 0 = bgk_prepare + bgk_predict_fuse_t<.., false>; env LA3DM_BGK_ONE_LAUNCH sets the default
     float inv_ell = 0.0f;   // RN(1 / ell), or 0 when x / ell must stay an IEEE division (bgk_kernels.h div_by_ell)
     int opt_fast_trig = 0;  // 0 correctly rounded (f64 kernels), 1 f32 polynomial, 2 OCML, 3 Eigen 3.3.7 psin / pcos without FMA (the likely reference build)
     int opt_gp_mode = 0;    // GPOctoMap: 0 = FMA chains in ascending order (VALU and matrix cores alike: the parity configuration), 1 = the order of an

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "bgk_kernels.h"
+#include "bgk_scan1_kernels.h"
 #include "gp_kernels.h"
 #include "gp_eigen_kernels.h"
 #include "lv_kernels.h"
@@ -233,6 +234,9 @@ int la3dm_create(const la3dm_params *params, la3dm_ctx **out) {
     if (const char *ev = getenv("LA3DM_BGK_TABLES")) {  // bgk_sum = 1: 0 = bgk_predict_fuse_r for every tile
         if (ev[0] == '0' || ev[0] == '1') ctx->opt_bgk_tables = ev[0] - '0';
     }
+    if (const char *ev = getenv("LA3DM_BGK_ONE_LAUNCH")) {  // full-block table scans at block_depth 3: 0 = bgk_prepare + bgk_predict_fuse_t
+        if (ev[0] == '0' || ev[0] == '1') ctx->opt_bgk_one_launch = ev[0] - '0';
+    }
     if (const char *ev = getenv("LA3DM_BGKL_SPLIT_ROWS")) {   // default of "bgkl_split_rows": an integer (< 0: never split); anything else is ignored
         char *end = nullptr;
         const long v = strtol(ev, &end, 10);
@@ -300,6 +304,11 @@ int la3dm_set_option(la3dm_ctx *ctx, const char *name, int value) {
         ctx->opt_bgk_tables = value;
         return LA3DM_OK;
     }
+    if (!strcmp(name, "bgk_one_launch")) {  // 1 = full-block table scans at block_depth 3 in one launch (bgk_predict_fuse_t1), 0 = bgk_prepare + bgk_predict_fuse_t
+        if (value < 0 || value > 1) return bad_value("0 or 1");
+        ctx->opt_bgk_one_launch = value;
+        return LA3DM_OK;
+    }
     if (!strcmp(name, "fast_trig")) {  // 0 correctly rounded (default, the parity configuration), 1 f32 polynomial, 2 OCML, 3 = Eigen 3.3.7's psin / pcos
         // without FMA, the likely reference build (BGK, BGK-L and BGK-LV kernels; 1 and 2: the BGK kernels only)
         if (value < 0 || value > 3) return bad_value("0, 1, 2 or 3");
@@ -364,6 +373,7 @@ int la3dm_get_option(const la3dm_ctx *ctx, const char *name, int *value) {
     if (!ctx || !name || !value) return LA3DM_ERR_ARG;
     if (!strcmp(name, "bgk_sum")) *value = ctx->opt_bgk_sum;
     else if (!strcmp(name, "bgk_tables")) *value = ctx->opt_bgk_tables;
+    else if (!strcmp(name, "bgk_one_launch")) *value = ctx->opt_bgk_one_launch;
     else if (!strcmp(name, "fast_trig")) *value = ctx->opt_fast_trig;
     else if (!strcmp(name, "gp_mode")) *value = ctx->opt_gp_mode;
     else if (!strcmp(name, "grid_order")) *value = ctx->opt_grid_order;
@@ -397,12 +407,25 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     hipStream_t stream = (hipStream_t)stream_;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-    // 1. x / ell once per training point
-    rc = arena_reserve(ctx, ctx->pts_scaled, sizeof(float4) * (size_t)(s->n_train_pts ? s->n_train_pts : 1));
-    if (rc != LA3DM_OK) return rc;
-    rc = arena_reserve(ctx, ctx->nbr_range, sizeof(uint2) * 7 * (size_t)s->n_test_blk);
-    if (rc != LA3DM_OK) return rc;
     const bool sum_f64 = ctx->opt_bgk_sum == 1;
+    // the table kernels: tiles of full (un-pruned) blocks through the distance tables, the others through the general
+    // path of the same launch; they need every label to be 0 or 1
+    const bool use_tables = sum_f64 && ctx->opt_bgk_tables && ctx->p.block_depth >= 3 && (s->flags & LA3DM_SCAN_LABELS_01) != 0u;
+    // the instance without the general path only when the caller's LA3DM_SCAN_FULL_BLOCKS can be verified here: a block
+    // holds at most 8^(depth-1) leaves, so the total says whether every block is full (ADVICE r04: a tile of a block that is
+    // not would be skipped silently)
+    const bool full_blocks = (s->flags & LA3DM_SCAN_FULL_BLOCKS) != 0u && (uint64_t)s->n_leaf == ((uint64_t)s->n_test_blk << (3 * (ctx->p.block_depth - 1)));
+    // full-block table scans at block_depth 3 (the first scan into an empty map): ONE launch — bgk_predict_fuse_t1 scales the
+    // caller's points and resolves the neighbour ranges itself (bgk_scan1_kernels.h); option "bgk_one_launch" 0 = the two launches below
+    const bool one_launch = use_tables && full_blocks && ctx->p.block_depth == 3 && ctx->opt_bgk_one_launch == 1;
+
+    // 1. x / ell once per training point
+    if (!one_launch) {
+        rc = arena_reserve(ctx, ctx->pts_scaled, sizeof(float4) * (size_t)(s->n_train_pts ? s->n_train_pts : 1));
+        if (rc != LA3DM_OK) return rc;
+        rc = arena_reserve(ctx, ctx->nbr_range, sizeof(uint2) * 7 * (size_t)s->n_test_blk);
+        if (rc != LA3DM_OK) return rc;
+    }
     uint32_t max_leaves = 1u << (3 * (ctx->p.block_depth - 1));
     uint32_t tpb = (max_leaves + kWave - 1) / kWave;  // power of two
     uint32_t tpb_shift = 0;
@@ -413,7 +436,7 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     const bool tile_desc = sum_f64 && tpb_shift >= 3 && ctx->opt_bgk_tile_desc && !(s->flags & LA3DM_SCAN_UPDATE_UNGATED) &&
                            ctx->p.ell <= 4.0f * ctx->p.resolution;
     const uint32_t desc_shift = tile_desc ? tpb_shift : 0u;
-    if (sum_f64) {
+    if (sum_f64 && !one_launch) {
         rc = arena_reserve(ctx, ctx->blk_desc, sizeof(uint32_t) * 16 * ((size_t)s->n_test_blk << desc_shift));
         if (rc != LA3DM_OK) return rc;
         if (!ctx->label_seq.ptr) {
@@ -424,14 +447,7 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
         }
         if (++ctx->scan_seq == 0u) ctx->scan_seq = 1u;  // 0 is the cleared state
     }
-    // the table kernels: tiles of full (un-pruned) blocks through the distance tables, the others through the general
-    // path of the same launch; they need every label to be 0 or 1
-    const bool use_tables = sum_f64 && ctx->opt_bgk_tables && ctx->p.block_depth >= 3 && (s->flags & LA3DM_SCAN_LABELS_01) != 0u;
-    // the instance without the general path only when the caller's LA3DM_SCAN_FULL_BLOCKS can be verified here: a block
-    // holds at most 8^(depth-1) leaves, so the total says whether every block is full (ADVICE r04: a tile of a block that is
-    // not would be skipped silently)
-    const bool full_blocks = (s->flags & LA3DM_SCAN_FULL_BLOCKS) != 0u && (uint64_t)s->n_leaf == ((uint64_t)s->n_test_blk << (3 * (ctx->p.block_depth - 1)));
-    {
+    if (!one_launch) {
         const uint32_t n_nbr = 7u * s->n_test_blk;
         uint32_t n_thr = s->n_train_pts > n_nbr ? s->n_train_pts : n_nbr;
         BgkDescArgs da;
@@ -452,7 +468,7 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
 
     // 2. predict + fuse
     BgkArgs a;
-    a.pts = (const float4 *)ctx->pts_scaled.ptr;
+    a.pts = one_launch ? (const float4 *)s->train_xyzy : (const float4 *)ctx->pts_scaled.ptr;  // (one launch: the caller's unscaled points)
     a.train_off = s->train_off;
     a.nbr = s->nbr;
     a.blk_center = s->blk_center;
@@ -501,7 +517,9 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     if (sum_f64) {
         grid = dim3(a.n_tasks);
         block = dim3(kWave);
-        if (use_tables) {
+        if (one_launch) {
+            LAUNCH_BGK(bgk_predict_fuse_t1)
+        } else if (use_tables) {
             if (full_blocks) {  // no pruned block in this scan: the kernel without the general path
                 LAUNCH_BGK(bgk_predict_fuse_t, , false)
             } else {
@@ -527,7 +545,7 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     HIP_TRY(ctx, hipGetLastError());
     if (out) {
         out->n_tiles = a.n_tasks;
-        out->scratch_bytes = sizeof(float4) * (size_t)s->n_train_pts;
+        out->scratch_bytes = one_launch ? 0 : sizeof(float4) * (size_t)s->n_train_pts;
     }
     return LA3DM_OK;
 }

@@ -8,32 +8,41 @@
 cd $GRAFT_REPO_ROOT; export TMPDIR=/tmp
 ROUND=${ROUND:-r06}   # output directory under gpurun_out/ and profiles/; the entries' "round" field
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$ROUND/prof; rm -rf $OUT; mkdir -p $OUT
+# every profiler run under a time limit of its own (RUN_LIMIT seconds); the first run that fails, faults or runs out of time ends the
+# script — nothing more is started on the device after it, and no counter file is written from a partial set
+RUN_LIMIT=${RUN_LIMIT:-180}
+run() {   # run <log name> <command ...>
+  local name=$1; shift
+  timeout -k 10 $RUN_LIMIT "$@" > $OUT/bench_$name.log 2>&1
+  local rc=$?
+  if [ $rc -ne 0 ]; then echo "update_traffic.sh: run $name ended with status $rc (log: $OUT/bench_$name.log): stopping" >&2; tail -5 $OUT/bench_$name.log >&2; exit $rc; fi
+}
 for SUM in 1 0; do
   BENCH="python bench.py --steps 20 --warmup 3 --no-cpu --no-e2e --no-big --no-side --no-other-mode --sum $SUM"
-  rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace$SUM -o t -- $BENCH > $OUT/bench_trace$SUM.log 2>&1
+  run trace$SUM rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace$SUM -o t -- $BENCH
   for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD" \
              "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_VMEM_RD SQ_WAIT_INST_LDS" \
              "GRBM_GUI_ACTIVE SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VMEM_WR" \
              "FETCH_SIZE" "WRITE_SIZE"; do
     n=$(echo $set | tr ' ' '_' | cut -c1-40)
-    rocprofv3 --output-format csv --pmc $set -d $OUT/pmc${SUM}_$n -o p -- $BENCH > $OUT/bench_pmc${SUM}_$n.log 2>&1
+    run pmc${SUM}_$n rocprofv3 --output-format csv --pmc $set -d $OUT/pmc${SUM}_$n -o p -- $BENCH
   done
   # per-phase instruction counts: ablate 1 = no kernel evaluation (C), 2 = no candidate tests (B and C), 4 = no ordered fuse (D, sum 0)
   for AB in 1 2 4 5; do
     if [ $SUM = 1 ] && [ $AB -ge 4 ]; then continue; fi
-    rocprofv3 --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU -d $OUT/ab${SUM}_$AB -o p -- $BENCH --ablate $AB > $OUT/bench_ab${SUM}_$AB.log 2>&1
+    run ab${SUM}_$AB rocprofv3 --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU -d $OUT/ab${SUM}_$AB -o p -- $BENCH --ablate $AB
   done
 done
 # block_depth 4 (the reference constructor's default): kernel trace + the counters the bench's roofline.depth4 leg quotes
 BENCH4="python bench.py --steps 20 --warmup 3 --no-cpu --no-e2e --no-big --no-side --no-other-mode --sum 1 --depth 4"
-rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_d4 -o t -- $BENCH4 > $OUT/bench_trace_d4.log 2>&1
+run trace_d4 rocprofv3 --output-format csv --kernel-trace --stats -d $OUT/trace_d4 -o t -- $BENCH4
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_SMEM SQ_INSTS_VMEM_RD" \
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT" "FETCH_SIZE" "WRITE_SIZE"; do
   n=$(echo $set | tr ' ' '_' | cut -c1-40)
-  rocprofv3 --output-format csv --pmc $set -d $OUT/pmcd4_$n -o p -- $BENCH4 > $OUT/bench_pmcd4_$n.log 2>&1
+  run pmcd4_$n rocprofv3 --output-format csv --pmc $set -d $OUT/pmcd4_$n -o p -- $BENCH4
 done
 for AB in 1 2; do
-  rocprofv3 --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU -d $OUT/abd4_$AB -o p -- $BENCH4 --ablate $AB > $OUT/bench_abd4_$AB.log 2>&1
+  run abd4_$AB rocprofv3 --output-format csv --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU -d $OUT/abd4_$AB -o p -- $BENCH4 --ablate $AB
 done
 python - <<PY
 import csv, glob, collections, json, os, sys
