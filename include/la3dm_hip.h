@@ -562,6 +562,54 @@ int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_
 int la3dm_devmap_frontier_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
                                  uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
                                  const la3dm_frontier_out *d_out, uint64_t *n_found, la3dm_region_info *info);
+/* Gain of candidate viewpoints: per viewpoint the number of DISTINCT voxels of a region that a fan of rays from it walks
+ * over and whose class is in count_mask — the expected information gain of a next-best-view planner when count_mask
+ * selects the unobserved classes.  (Summing raycast_many's counts over the rays of a viewpoint counts a voxel once per
+ * ray that crosses it; the rays of a fan overlap near their origin.)
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's.
+ *   Rays.  n viewpoints origins3 (packed xyz) and m directions offsets3 (packed xyz, metres in the map frame, shared by
+ *     all viewpoints: the caller's sensor pattern) give n * m segments: start = origins[v], end[c] = origins[v][c] +
+ *     offsets[d][c], one fp32 add per coordinate — the only floating-point operation the query adds to raycast_many's.
+ *   Walk.  Every segment is walked exactly as raycast_many(start, end, stop_mask, max_steps) walks it: the same validity
+ *     test on the six coordinates (an invalid ray contributes nothing), the same never-starts rule, the same rows, the
+ *     same stopping row and the same truncation.
+ *   Marking.  Every row produced is a candidate, the stopping row included.  Its lattice position is, per axis, the
+ *     20-bit field of its block key times lim plus the cell of its node key, as RayCaster::next reports them (rows in
+ *     missing blocks included).  If that position lies in the region and count_mask & (1u << cls) is set — cls the class
+ *     of the row: FREE 0, OCCUPIED 1, UNKNOWN 2, MISSING 3, a BGK-LV map's UNCERTAIN 4; what box reports there — bit f
+ *     of the viewpoint's set is set.
+ *   Outputs.  gain[v] = the popcount of viewpoint v's set.  seen[v * W + f / 32] bit f % 32 = the set itself, W =
+ *     ceil(nx ny nz / 32); the bits at f >= nx ny nz are 0.  started[v] / hits[v] = the rays of the viewpoint with
+ *     steps > 0 / that ended on a stop row (LA3DM_RAY_HIT).
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, no buffer touched, nothing reserved), in this
+ *     order: a count_mask of 0 or with bits above 0x1F; a stop_mask with bits above 0x1F (0 is legal: every ray walks to
+ *     its end); max_steps outside 1 ... LA3DM_RAY_MAX_STEPS; m = 0; n * m > LA3DM_GAIN_MAX_RAYS; what box refuses for
+ *     lo and dims; more than LA3DM_GAIN_MAX_CELLS voxels; n * W > LA3DM_GAIN_MAX_WORDS; with n > 0 a NULL origins3,
+ *     offsets3, out or out->gain.
+ *   n = 0 is served and writes nothing.  An empty map (no ray starts) answers all-zero without a launch.
+ *   Working storage: the sets, n * W words, in a grow-only arena of the devmap (released with it; a smaller request
+ *     after a larger one allocates nothing).  When out->seen is given to the device-pointer form it is the working
+ *     storage and the arena is not used.
+ *   Everything after the walk is integer arithmetic: the results equal the host form (BGKOctoMap::gain on a host-mode
+ *     map) exactly. */
+#define LA3DM_GAIN_MAX_CELLS (1u << 28)
+#define LA3DM_GAIN_MAX_RAYS  (1u << 28)
+#define LA3DM_GAIN_MAX_WORDS (1u << 28)
+typedef struct la3dm_gain_out {
+    uint32_t *gain;     /* [n]   mandatory: distinct marked voxels per viewpoint */
+    uint32_t *started;  /* [n]   or NULL: rays of the viewpoint with steps > 0 */
+    uint32_t *hits;     /* [n]   or NULL: rays that ended on a stop row (LA3DM_RAY_HIT) */
+    uint32_t *seen;     /* [n W] or NULL: the sets themselves, W = ceil(nx ny nz / 32) */
+} la3dm_gain_out;
+/* host pointers: upload of the origins and offsets, the launches, download, synchronise — on the map's stream */
+int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
+                           const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                           const la3dm_gain_out *out, la3dm_region_info *info);
+/* device pointers (origins3, offsets3 and out's arrays already in HBM on the map's device, 4-byte aligned; lo3, dims3 and
+ * info stay host-side); returns when the results are complete */
+int la3dm_devmap_gain_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_origins3, uint32_t n,
+                             const float *d_offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                             const la3dm_gain_out *d_out, la3dm_region_info *info);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

@@ -150,6 +150,16 @@ int la3dm_map_distance_field(const la3dm_map *m, const float *lo3, const uint32_
 int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask,
                        uint32_t connectivity, uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out *out,
                        uint64_t *n_found, la3dm_region_info *info);
+/* BGKOctoMap::gain: per viewpoint origins3[v] the number of DISTINCT voxels of box's region that the segments origins3[v] ->
+ * origins3[v] + offsets3[d], d < m, walk over — each exactly as raycast_many(stop_mask, max_steps) walks it — and whose class
+ * is in count_mask: the expected information gain of a next-best-view planner with count_mask = UNKNOWN | MISSING.
+ * out->gain (mandatory) [n]; out->started / out->hits [n] = the rays that produced a row / ended on a stop row; out->seen
+ * [n * ceil(nx ny nz / 32)] = the sets, bit f = (i * ny + j) * nz + k.  Contract, limits and refusals: include/la3dm_hip.h
+ * (la3dm_devmap_gain_host).  Device-resident maps run the query on the device pool without a mirror refresh, host-mode
+ * maps on the CPU; the results are identical. */
+int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
+                   const float *offsets3, uint32_t m_dirs, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                   const la3dm_gain_out *out, la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

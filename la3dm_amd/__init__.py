@@ -2,6 +2,7 @@
 hot path behind the reference's BGKOctoMap interface.  See DESIGN.md / INTEGRATION.md."""
 from .bgkoctomap import BGKOctoMap, GPOctoMap, BGKLVOctoMap, BGKLOctoMap, PackedScan, FREE, OCCUPIED, UNKNOWN, PRUNED  # noqa: F401
 from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR_MAX_CELLS  # noqa: F401
+from .bgkoctomap import GAIN_MAX_CELLS, GAIN_MAX_RAYS, GAIN_MAX_WORDS  # noqa: F401
 from .pcd import load_pcd  # noqa: F401
 from .synth import synthetic_scan  # noqa: F401
 

@@ -16,6 +16,7 @@ MISSING = 3
 RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
 DF_FAR = 0xFFFFFFFF                 # LA3DM_DF_FAR: beyond the radius of distance_field (dist: +inf)
 FR_MAX_CELLS = 1 << 28             # LA3DM_FR_MAX_CELLS: voxels of frontier's region padded by one on every side
+GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: voxels of gain's region, n * m rays, n * W set words
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
@@ -352,6 +353,48 @@ class BGKOctoMap:
         m = min(total, k)
         out["index"], out["nbrs"] = out["index"][:m], out["nbrs"][:m]
         out["n"] = total
+        out.update(self._region_info(info))
+        return out
+
+    def gain(self, lo, dims, origins, offsets, count=("unknown", "missing"), stop=("occupied",), max_steps=4096, fields=("gain",)):
+        """The information gain of n candidate viewpoints: per viewpoint origins[v] the number of DISTINCT voxels of the
+        region of box(lo, dims) that the m segments origins[v] -> origins[v] + offsets[d] walk over and whose class is in
+        `count`.  Every segment is walked exactly as raycast_many(stop=stop, max_steps=max_steps) walks it; every row it
+        produces, the stopping row included, marks its voxel if the voxel lies in the region and its class is in `count`.
+        offsets (m, 3) are metres in the map frame, shared by all viewpoints: the caller's sensor pattern.  count / stop:
+        names out of free / occupied / unknown / missing (/ uncertain on a BGK-LV map) or an integer bit mask, as
+        frontier takes them; stop=() walks every ray to its end.  Returns a dict: gain (n,) uint32 and, when named in
+        `fields`, started / hits (n,) = the rays of the viewpoint that produced a row / ended on a stop row, seen (n, W)
+        uint32 = the sets themselves, bit f % 32 of word f // 32 for the flat index f = (i * ny + j) * nz + k, W =
+        ceil(nx ny nz / 32); plus origin, block_key, cell as box() returns them.  At most 2^28 voxels, n * m <= 2^28 rays
+        and n * W <= 2^28 words.  A device-resident map runs the query on the device pool (no host mirror refresh); a
+        host-mode map runs it on the CPU, with identical results."""
+        lo3, d3, d, cells = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= GAIN_MAX_CELLS else 0)(d[0] * d[1] * d[2]))
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        f = np.ascontiguousarray(offsets, np.float32).reshape(-1, 3)
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - {"gain", "started", "hits", "seen"}
+        if bad:
+            raise ValueError(f"gain: unknown fields {sorted(bad)}")
+        masks = []
+        for m in (count, stop):
+            if isinstance(m, str):
+                m = (m,)
+            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
+        if not all(0 <= v < 2 ** 32 for v in masks + [int(max_steps), o.shape[0], f.shape[0]]):
+            raise ValueError("gain: count, stop, max_steps and the numbers of origins and offsets must fit 32 bits")
+        n, W = o.shape[0], (cells + 31) // 32
+        # (a request the call refuses gets one-element arrays: it is refused before a buffer is looked at)
+        served = cells > 0 and f.shape[0] > 0 and n * f.shape[0] <= GAIN_MAX_RAYS and n * W <= GAIN_MAX_WORDS
+        out = {k: np.empty(n if served else 1, np.uint32) for k in ("gain", "started", "hits") if k == "gain" or k in fields}
+        if "seen" in fields:
+            out["seen"] = np.empty((n, W) if served else (1,), np.uint32)
+        g = _lib.GainOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.GainOut._fields_])
+        info = _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_gain(self._h, lo3.ctypes.data, d3.ctypes.data, o.ctypes.data if n else None, n,
+                                         f.ctypes.data if f.shape[0] else None, f.shape[0], masks[0], masks[1], int(max_steps),
+                                         C.byref(g), C.byref(info)))
         out.update(self._region_info(info))
         return out
 

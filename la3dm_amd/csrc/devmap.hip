@@ -29,6 +29,7 @@
 #include "devmap_region.h"
 #include "devmap_distance.h"
 #include "devmap_frontier.h"
+#include "devmap_gain.h"
 
 using namespace la3dm_dev;
 
@@ -78,6 +79,7 @@ struct la3dm_devmap {
     Arena train, grid, axis_tab, m_code, q_out;
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
+    Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -673,7 +675,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -2837,6 +2839,134 @@ int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_
     }
     *n_found = total;
     if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+// ---- gain of candidate viewpoints (devmap_gain.h) ---------------------------------------------------------------
+static int gain_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
+                        const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                        const la3dm_gain_out *out, const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    const std::string w(who);
+    std::string refusal = la3dm_region::gain_check(count_mask, stop_mask, max_steps, n, m);
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
+    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kGain, true, true, who, g);   // lo, dims, the limit and the range: before any buffer
+    if (rc != LA3DM_OK) return rc;
+    refusal = la3dm_region::gain_buffers(g.total, n, origins3 != nullptr, offsets3 != nullptr, out != nullptr, out && out->gain, "->");
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
+    return LA3DM_OK;
+}
+
+// Zeroing, mark and count on the map's stream; every pointer is device memory.  o.seen null: the sets live in the arena;
+// `sets` returns where they are.
+static int gain_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_origins3, uint32_t n, const float *d_offsets3,
+                       uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, const la3dm_gain_out &o,
+                       const uint32_t *&sets) {
+    hipStream_t st = dm->ctx->stream;
+    const uint32_t W = la3dm_region::gain_words(g.total);
+    const size_t words = (size_t)n * W;   // <= LA3DM_GAIN_MAX_WORDS
+    uint32_t *seen = o.seen;
+    if (!seen) {
+        DM_RESERVE(dm->gain_work, 4ull * words);
+        seen = (uint32_t *)dm->gain_work.ptr;
+    }
+    GainArgs a;
+    memset(&a, 0, sizeof(a));
+    a.origins = d_origins3;
+    a.offsets = d_offsets3;
+    a.n = n;
+    a.m = m;
+    a.chunks = cdiv(m, 256);
+    a.count_mask = count_mask;
+    a.stop_mask = stop_mask;
+    a.max_steps = max_steps;
+    a.block_size = dm->block_size;
+    a.resolution = dm->ctx->p.resolution;
+    a.pool = pool_view(dm);
+    for (int k = 0; k < 3; ++k) a.g0[k] = g.g0[k];
+    a.nx = g.dims[0];
+    a.ny = g.dims[1];
+    a.nz = g.dims[2];
+    a.W = W;
+    a.seen = seen;
+    a.started = o.started;
+    a.hits = o.hits;
+    DM_TRY(hipMemsetAsync(seen, 0, 4ull * words, st));
+    DM_TRY(hipMemsetAsync(o.gain, 0, 4ull * n, st));
+    if (o.started) DM_TRY(hipMemsetAsync(o.started, 0, 4ull * n, st));
+    if (o.hits) DM_TRY(hipMemsetAsync(o.hits, 0, 4ull * n, st));
+    // (n chunks <= n m / 256 + n <= 2^20 + 2^28 workgroups, and n ceil(W / 256) <= 2^20 + 2^28: both fit the grid's x)
+    hipLaunchKernelGGL(dm_gain_mark, dim3(n * a.chunks), dim3(256), 0, st, a);
+    const uint32_t wchunks = cdiv(W, 256);
+    hipLaunchKernelGGL(dm_gain_count, dim3(n * wchunks), dim3(256), 0, st, (const uint32_t *)seen, W, wchunks, o.gain);
+    DM_TRY(hipGetLastError());
+    sets = seen;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_gain_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_origins3, uint32_t n,
+                             const float *d_offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                             const la3dm_gain_out *d_out, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = gain_resolve(dm, lo3, dims3, d_origins3, n, d_offsets3, m, count_mask, stop_mask, max_steps, d_out,
+                          "la3dm_devmap_gain_device", g);
+    if (rc != LA3DM_OK) return rc;
+    if (info) *info = g.info;
+    if (n == 0) return LA3DM_OK;
+    hipStream_t st = dm->ctx->stream;
+    const la3dm_gain_out &o = *d_out;
+    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched (the constant answer is written by memsets)
+        DM_TRY(hipMemsetAsync(o.gain, 0, 4ull * n, st));
+        if (o.started) DM_TRY(hipMemsetAsync(o.started, 0, 4ull * n, st));
+        if (o.hits) DM_TRY(hipMemsetAsync(o.hits, 0, 4ull * n, st));
+        if (o.seen) DM_TRY(hipMemsetAsync(o.seen, 0, 4ull * n * la3dm_region::gain_words(g.total), st));
+    } else {
+        const uint32_t *sets = nullptr;
+        rc = gain_launch(dm, g, d_origins3, n, d_offsets3, m, count_mask, stop_mask, max_steps, o, sets);
+        if (rc != LA3DM_OK) return rc;
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
+                           const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                           const la3dm_gain_out *out, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = gain_resolve(dm, lo3, dims3, origins3, n, offsets3, m, count_mask, stop_mask, max_steps, out,
+                          "la3dm_devmap_gain_host", g);
+    if (rc != LA3DM_OK) return rc;
+    if (info) *info = g.info;
+    if (n == 0) return LA3DM_OK;
+    const la3dm_gain_out &h = *out;
+    const size_t words = (size_t)n * la3dm_region::gain_words(g.total);
+    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched
+        memset(h.gain, 0, 4ull * n);
+        if (h.started) memset(h.started, 0, 4ull * n);
+        if (h.hits) memset(h.hits, 0, 4ull * n);
+        if (h.seen) memset(h.seen, 0, 4ull * words);
+        return LA3DM_OK;
+    }
+    hipStream_t st = dm->ctx->stream;
+    // origins and offsets in `cloud`; gain, started, hits in `q_out`; the sets in their own arena
+    DM_RESERVE(dm->cloud, 12ull * n + 12ull * m);
+    DM_RESERVE(dm->q_out, 12ull * n);
+    float *d_origins = (float *)dm->cloud.ptr, *d_offsets = d_origins + 3ull * n;
+    la3dm_gain_out d;
+    d.gain = (uint32_t *)dm->q_out.ptr;
+    d.started = h.started ? d.gain + n : nullptr;
+    d.hits = h.hits ? d.gain + 2ull * n : nullptr;
+    d.seen = nullptr;
+    DM_TRY(hipMemcpyAsync(d_origins, origins3, 12ull * n, hipMemcpyHostToDevice, st));
+    DM_TRY(hipMemcpyAsync(d_offsets, offsets3, 12ull * m, hipMemcpyHostToDevice, st));
+    const uint32_t *sets = nullptr;
+    rc = gain_launch(dm, g, d_origins, n, d_offsets, m, count_mask, stop_mask, max_steps, d, sets);
+    if (rc != LA3DM_OK) return rc;
+    DM_TRY(hipMemcpyAsync(h.gain, d.gain, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.started) DM_TRY(hipMemcpyAsync(h.started, d.started, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.hits) DM_TRY(hipMemcpyAsync(h.hits, d.hits, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (h.seen) DM_TRY(hipMemcpyAsync(h.seen, sets, 4ull * words, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
     return LA3DM_OK;
 }
 

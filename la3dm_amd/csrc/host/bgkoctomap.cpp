@@ -1026,6 +1026,103 @@ void BGKOctoMap::frontier(const float *lo3, const uint32_t *dims3, uint32_t open
     }
 }
 
+// ---- gain of candidate viewpoints.  The host form below is the definition; the device kernels (csrc/devmap_gain.h)
+// reproduce it bit for bit.  Per segment the loop is raycast_many's, row for row; what is added is the mark: the row's
+// lattice position (block-key fields * lim + the cell of its node key) against the region, and one bit per voxel and
+// viewpoint.
+void BGKOctoMap::gain(const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n, const float *offsets3, uint32_t m,
+                      uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, const la3dm_gain_out &out,
+                      la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_gain_host(dmap, lo3, dims3, origins3, n, offsets3, m, count_mask, stop_mask, max_steps, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::gain: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::gain";
+    std::string refusal = la3dm_region::gain_check(count_mask, stop_mask, max_steps, n, m);
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kGain, true, "gain", g0, inf);
+    const uint64_t total = (uint64_t)dims3[0] * dims3[1] * dims3[2];
+    refusal = la3dm_region::gain_buffers(total, n, origins3 != nullptr, offsets3 != nullptr, true, out.gain != nullptr, ".");
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    if (info) *info = inf;
+    if (n == 0) return;
+    const size_t W = la3dm_region::gain_words(total);
+    std::vector<uint32_t> own_sets;
+    uint32_t *sets = out.seen;
+    if (sets == nullptr) {
+        own_sets.resize((size_t)n * W);
+        sets = own_sets.data();
+    }
+    std::fill(sets, sets + (size_t)n * W, 0u);
+    const unsigned dl = block_depth - 1u;
+    const uint32_t lim = 1u << dl, nx = dims3[0], ny = dims3[1], nz = dims3[2];
+    for (uint32_t v = 0; v < n; ++v) {
+        uint32_t *set = sets + (size_t)v * W;
+        uint32_t started = 0, hits = 0;
+        const float *o = origins3 + 3 * (size_t)v;
+        for (uint32_t d = 0; d < m; ++d) {
+            const float *off = offsets3 + 3 * (size_t)d;
+            const float q[6] = {o[0], o[1], o[2], o[0] + off[0], o[1] + off[1], o[2] + off[2]};
+            bool ok = true;  // raycast_many's validity test
+            for (int a = 0; a < 6; ++a) ok &= std::fabs(q[a] / resolution) < 1073741824.0f;   // false for NaN and inf
+            if (!ok) continue;
+            uint32_t steps = 0;
+            RayCaster rc(this, point3f(q[0], q[1], q[2]), point3f(q[3], q[4], q[5]));
+            while (!rc.end()) {
+                if (steps == max_steps) break;   // truncated
+                point3f p;
+                OcTreeNode nd;
+                BlockHashKey bk = 0;
+                OcTreeHashKey nk = 0;
+                const bool valid = rc.next(p, nd, bk, nk);
+                ++steps;
+                uint32_t cls = LA3DM_RAY_MISSING;
+                if (valid) {   // the covering leaf, as raycast_many finds it
+                    const Block *b = block_arr.find(bk)->second;
+                    unsigned ld = dl, i = (unsigned)(nk & 0xFFFF);
+                    while (ld > 0 && b->slab[layer_base(ld) + i].state == State::PRUNED) {
+                        --ld;
+                        i >>= 3;
+                    }
+                    cls = (uint32_t)b->slab[layer_base(ld) + i].state;
+                }
+                if ((count_mask >> cls) & 1u) {
+                    // the cell of the node key: its digits base 8 (bit 4 = x, 2 = y, 1 = z), the coarsest level first
+                    uint32_t c[3] = {0, 0, 0};
+                    for (unsigned level = 0; level < dl; ++level) {
+                        const uint32_t digit = ((uint32_t)nk >> (3 * level)) & 7u;
+                        c[0] |= ((digit >> 2) & 1u) << level;
+                        c[1] |= ((digit >> 1) & 1u) << level;
+                        c[2] |= (digit & 1u) << level;
+                    }
+                    // (wrapping: a position below g0 becomes a huge index and fails the compare)
+                    const uint32_t i = ((uint32_t)(bk >> 40) & 0xFFFFFu) * lim + c[0] - g0[0];
+                    const uint32_t j = ((uint32_t)(bk >> 20) & 0xFFFFFu) * lim + c[1] - g0[1];
+                    const uint32_t k = ((uint32_t)bk & 0xFFFFFu) * lim + c[2] - g0[2];
+                    if (i < nx && j < ny && k < nz) {
+                        const uint32_t f = (i * ny + j) * nz + k;
+                        set[f >> 5] |= 1u << (f & 31u);
+                    }
+                }
+                if (stop_mask & (1u << cls)) {
+                    ++hits;
+                    break;
+                }
+            }
+            started += steps > 0 ? 1u : 0u;
+        }
+        uint32_t gain = 0;
+        for (size_t t = 0; t < W; ++t) gain += (uint32_t)__builtin_popcount(set[t]);
+        out.gain[v] = gain;
+        if (out.started) out.started[v] = started;
+        if (out.hits) out.hits[v] = hits;
+    }
+}
+
 namespace {
 // heightMapColor, include/common/markerarray_pub.h:21-76 (s = v = 1)
 void height_map_color(double h, float *rgba) {

@@ -456,6 +456,17 @@ public:
     void frontier(const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity,
                   uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out &out, uint64_t *n_found,
                   la3dm_region_info *info = nullptr) const;
+    /// Gain of candidate viewpoints over box's region (contract: include/la3dm_hip.h, la3dm_devmap_gain_host): the n * m
+    /// segments origins[v] -> origins[v] + offsets[d] are walked exactly as raycast_many(stop_mask, max_steps) walks them;
+    /// every row whose class is in `count_mask` and whose voxel lies in the region sets that voxel's bit in viewpoint v's
+    /// set.  out.gain[v] = the number of DISTINCT voxels marked — the expected information gain when count_mask selects the
+    /// unobserved classes — out.seen the sets, out.started / out.hits the rays per viewpoint that produced a row / ended on a
+    /// stop row.  Bad arguments throw std::invalid_argument.  A device-resident map runs the query on the device pool (no
+    /// mirror refresh); a host-mode map loops its own RayCaster: that form is the definition, and both give the same
+    /// integers.
+    void gain(const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n, const float *offsets3, uint32_t m,
+              uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, const la3dm_gain_out &out,
+              la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {

@@ -398,6 +398,19 @@ int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dim
         return 0;)
 }
 
+int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
+                   const float *offsets3, uint32_t mdirs, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                   const la3dm_gain_out *out, la3dm_region_info *info) {
+    GUARD(
+        la3dm_gain_out none;
+        none.gain = nullptr;
+        none.started = nullptr;
+        none.hits = nullptr;
+        none.seen = nullptr;
+        m->map->gain(lo3, dims3, origins3, n, offsets3, mdirs, count_mask, stop_mask, max_steps, out ? *out : none, info);
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);

@@ -26,6 +26,7 @@ constexpr Query kBox = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELL
 constexpr Query kColumns = {1ull << 30, "dims: more than 2^30 columns", true, false, "out->counts must not be NULL"};
 constexpr Query kDistance = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, "out: d2 or dist must not be NULL"};
 constexpr Query kFrontier = {LA3DM_FR_MAX_CELLS, "dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
+constexpr Query kGain = {LA3DM_GAIN_MAX_CELLS, "dims: more than LA3DM_GAIN_MAX_CELLS (2^28) voxels", false, false, ""};
 
 struct Anchor {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
@@ -94,6 +95,31 @@ inline std::string frontier_check(uint32_t open_mask, uint32_t unknown_mask, uin
     if (unknown_mask == 0 || (unknown_mask & ~0x1Fu)) return "unknown_mask must hold at least one of the bits 0x1F and no other";
     if (connectivity != 6 && connectivity != 18 && connectivity != 26) return "connectivity must be 6, 18 or 26";
     if (min_neighbours == 0 || min_neighbours > connectivity) return "min_neighbours must lie in [1, connectivity]";
+    return "";
+}
+
+// the checks of gain's own arguments, before the region's
+inline std::string gain_check(uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, uint32_t n, uint32_t m) {
+    if (count_mask == 0 || (count_mask & ~0x1Fu)) return "count_mask must hold at least one of the bits 0x1F and no other";
+    if (stop_mask & ~0x1Fu) return "stop_mask must hold no bit above 0x1F";
+    if (max_steps == 0 || max_steps > LA3DM_RAY_MAX_STEPS) return "max_steps must lie in [1, LA3DM_RAY_MAX_STEPS (2^20)]";
+    if (m == 0) return "m must be >= 1";
+    if ((uint64_t)n * m > LA3DM_GAIN_MAX_RAYS) return "n * m: more than LA3DM_GAIN_MAX_RAYS (2^28) rays";
+    return "";
+}
+
+// words of one viewpoint's set
+inline uint32_t gain_words(uint64_t total) { return (uint32_t)((total + 31) / 32); }
+
+// the checks that follow the region's: the size of the sets, then the buffers (`member` as in resolve)
+inline std::string gain_buffers(uint64_t total, uint32_t n, bool has_origins, bool has_offsets, bool has_out, bool has_gain,
+                                const char *member) {
+    if ((uint64_t)n * gain_words(total) > LA3DM_GAIN_MAX_WORDS) return "n * W: more than LA3DM_GAIN_MAX_WORDS (2^28) words of sets, W = ceil(nx ny nz / 32)";
+    if (n == 0) return "";
+    if (!has_origins) return "origins3 is NULL";
+    if (!has_offsets) return "offsets3 is NULL";
+    if (!has_out) return "out is NULL";
+    if (!has_gain) return std::string("out") + member + "gain must not be NULL";
     return "";
 }
 
