@@ -610,6 +610,70 @@ int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *d
 int la3dm_devmap_gain_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_origins3, uint32_t n,
                              const float *d_offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                              const la3dm_gain_out *d_out, la3dm_region_info *info);
+/* Reach: the hop distance from seed voxels through the passable voxels of a region — can a goal be got to, and in how
+ * many moves.  A breadth-first wave, one launch per level.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; cls(v)
+ *     is what box reports for voxel v (FREE 0, OCCUPIED 1, UNKNOWN 2, MISSING 3, a BGK-LV map's UNCERTAIN 4).
+ *   Passable.  v is passable iff pass_mask & (1u << cls(v)) is set and (clearance == 0 or distance_field(lo, dims,
+ *     obstacle_mask, radius = clearance) reports d2[v] == LA3DM_DF_FAR): distance_field's definition over the same region.
+ *     Obstacles outside the region are not seen; a caller pads the region where that matters.  obstacle_mask is ignored
+ *     when clearance is 0.
+ *   Seeds.  seeds[s] is a flat index.  A seed that is out of range (>= nx ny nz) or not passable is ignored; n_seeded =
+ *     the number of DISTINCT passable voxels among the seeds.  n_seeds = 0 is served: everything is unreachable.
+ *   Steps.  steps[v] = the least number of moves from any seeded voxel to v, each move to a neighbour under connectivity
+ *     (frontier's offset sets: 6 = |di| + |dj| + |dk| = 1, 18 = a sum <= 2, 26 = all of {-1, 0, 1}^3 without 0) that is
+ *     passable and inside the region.  A seeded voxel has steps 0.  steps[v] = LA3DM_REACH_NONE when v is not passable,
+ *     when no such walk exists, or when the walk needs more than max_steps moves.
+ *   Corner cutting.  A diagonal move (connectivity 18, 26) is NOT tested for the voxels it squeezes between: two passable
+ *     voxels that touch by an edge or a corner are neighbours even when the voxels they share faces with are not
+ *     passable.  A caller who minds that uses clearance >= 1 or connectivity 6.
+ *   Targets.  target_steps[t] = steps[targets[t]], and LA3DM_REACH_NONE for an index out of range (>= nx ny nz).
+ *   Stats (always a host struct, may be NULL): n_seeded; n_reached = the voxels with finite steps, seeds included;
+ *     levels = the largest finite step (0 without a reached voxel).  levels == max_steps tells the caller that the wave
+ *     may have been cut.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written), before the region's own
+ *     checks: a pass_mask of 0 or with bits above 0x1F; with clearance > 0 an obstacle_mask of 0, and in any case one
+ *     with bits above 0x1F; clearance > LA3DM_DF_MAX_RADIUS; a connectivity other than 6, 18, 26; max_steps outside
+ *     1 ... LA3DM_REACH_MAX_STEPS; n_seeds > LA3DM_REACH_MAX_SEEDS; n_targets > 2^28; a NULL seeds or targets with a
+ *     non-zero count; a NULL out, or an out with neither steps nor target_steps; target_steps set with n_targets = 0 or
+ *     unset with n_targets > 0.  Then what box refuses for lo and dims, and as for frontier (nx + 2)(ny + 2)(nz + 2) >
+ *     LA3DM_REACH_MAX_CELLS or a region that, padded by one voxel on every side, fails box's block-field range check.
+ *   An empty map (every voxel MISSING) is answered all the same: an open box when pass_mask holds bit 3 (no obstacle
+ *     unless obstacle_mask holds it too), nothing reached otherwise.
+ *   Integers throughout, and the answer is unique: the results equal the host form (BGKOctoMap::reach on a host-mode
+ *     map) exactly.
+ *   Working storage, in a grow-only arena of the devmap (released with it; re-initialised on every call; a second call
+ *     at the same or a smaller size allocates nothing): four bit streams over the padded box (passable, reached and two fronts that take
+ *     turns: 1/2 byte per padded voxel), max_steps + 1 level counts, and 4 bytes per voxel that hold d2 (clearance > 0) and then the steps (when
+ *     out->steps is not given to the device form).
+ *   The host queues LA3DM_REACH_BATCH level launches, reads that batch's counts and stops at the first level that
+ *     reached nothing; levels queued behind it see an empty front and write nothing. */
+#define LA3DM_REACH_NONE      0xFFFFFFFFu
+#define LA3DM_REACH_MAX_CELLS (1u << 28)
+#define LA3DM_REACH_MAX_STEPS (1u << 16)
+#define LA3DM_REACH_MAX_SEEDS (1u << 20)
+#define LA3DM_REACH_BATCH     32
+typedef struct la3dm_reach_out {
+    uint32_t *steps;         /* [nx ny nz] or NULL */
+    uint32_t *target_steps;  /* [n_targets] or NULL; at least one of the two */
+} la3dm_reach_out;
+typedef struct la3dm_reach_stats {
+    uint32_t n_seeded;   /* distinct passable voxels among the seeds */
+    uint32_t n_reached;  /* voxels with finite steps, seeds included */
+    uint32_t levels;     /* the largest finite step */
+} la3dm_reach_stats;
+/* host pointers: upload of the seeds and targets, the launches, download of what was asked for (with target_steps alone:
+ * n_targets words), synchronise — on the map's stream */
+int la3dm_devmap_reach_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                            uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
+                            uint32_t max_steps, const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out,
+                            la3dm_reach_stats *stats, la3dm_region_info *info);
+/* device pointers (seeds, targets and out's arrays already in HBM on the map's device, 4-byte aligned; lo3, dims3, stats
+ * and info stay host-side); returns when the results are complete */
+int la3dm_devmap_reach_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
+                              uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
+                              uint32_t max_steps, const uint32_t *d_targets, uint32_t n_targets, const la3dm_reach_out *d_out,
+                              la3dm_reach_stats *stats, la3dm_region_info *info);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

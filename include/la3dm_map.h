@@ -160,6 +160,18 @@ int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dim
 int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
                    const float *offsets3, uint32_t m_dirs, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                    const la3dm_gain_out *out, la3dm_region_info *info);
+/* BGKOctoMap::reach: steps[v] = the least number of moves (connectivity 6, 18 or 26) from any of the seed voxels to v
+ * through the passable voxels of box's region — class in pass_mask and, with clearance > 0, farther than clearance voxels
+ * from every voxel of the region whose class is in obstacle_mask (distance_field's d2 == LA3DM_DF_FAR) — LA3DM_REACH_NONE
+ * where no such walk of at most max_steps moves exists.  seeds and targets are flat indices (i * ny + j) * nz + k, e.g.
+ * frontier's index list; out->target_steps[t] = steps[targets[t]].  stats (optional): seeded voxels, reached voxels, the
+ * largest finite step.  Contract, limits and refusals: include/la3dm_hip.h (la3dm_devmap_reach_host).  Device-resident
+ * maps run the wave on the device pool without a mirror refresh, host-mode maps a queue BFS on the CPU; the results are
+ * identical. */
+int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                    uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
+                    const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,
+                    la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

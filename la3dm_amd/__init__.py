@@ -3,6 +3,7 @@ hot path behind the reference's BGKOctoMap interface.  See DESIGN.md / INTEGRATI
 from .bgkoctomap import BGKOctoMap, GPOctoMap, BGKLVOctoMap, BGKLOctoMap, PackedScan, FREE, OCCUPIED, UNKNOWN, PRUNED  # noqa: F401
 from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR_MAX_CELLS  # noqa: F401
 from .bgkoctomap import GAIN_MAX_CELLS, GAIN_MAX_RAYS, GAIN_MAX_WORDS  # noqa: F401
+from .bgkoctomap import REACH_NONE, REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS, REACH_BATCH  # noqa: F401
 from .pcd import load_pcd  # noqa: F401
 from .synth import synthetic_scan  # noqa: F401
 

@@ -17,6 +17,9 @@ RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
 DF_FAR = 0xFFFFFFFF                 # LA3DM_DF_FAR: beyond the radius of distance_field (dist: +inf)
 FR_MAX_CELLS = 1 << 28             # LA3DM_FR_MAX_CELLS: voxels of frontier's region padded by one on every side
 GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: voxels of gain's region, n * m rays, n * W set words
+REACH_NONE = 0xFFFFFFFF             # LA3DM_REACH_NONE: reach found no walk to the voxel
+REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS = 1 << 28, 1 << 16, 1 << 20   # LA3DM_REACH_MAX_*: padded voxels, max_steps, seeds
+REACH_BATCH = 32                    # LA3DM_REACH_BATCH: level launches queued between two reads of the level counts
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
@@ -395,6 +398,55 @@ class BGKOctoMap:
         self._chk(self._M.la3dm_map_gain(self._h, lo3.ctypes.data, d3.ctypes.data, o.ctypes.data if n else None, n,
                                          f.ctypes.data if f.shape[0] else None, f.shape[0], masks[0], masks[1], int(max_steps),
                                          C.byref(g), C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
+    def reach(self, lo, dims, seeds, passable=("free",), obstacles=("occupied",), clearance=0, connectivity=6, max_steps=None,
+              targets=None, fields=("steps",)):
+        """Hop distances from seed voxels through the passable voxels of the region of box(lo, dims): can a goal be got to,
+        and in how many moves.  A voxel is passable when its class (box's cls) is in `passable` and, with clearance > 0,
+        distance_field(lo, dims, obstacles, radius=clearance) reports it FAR (obstacles outside the region are not seen).
+        seeds: flat indices (i * ny + j) * nz + k; one that is out of range or not passable is ignored.  steps[v] = the
+        least number of moves from any seed to v, each to a passable neighbour inside the region under `connectivity` (6,
+        18 or 26; diagonal moves are not tested for corner cutting — use clearance >= 1 or connectivity 6 for that),
+        REACH_NONE where there is no walk of at most max_steps moves (None: REACH_MAX_STEPS).  targets: flat indices, e.g.
+        frontier's index; target_steps[t] = steps[targets[t]], REACH_NONE for one out of range.  passable / obstacles: names
+        out of free / occupied / unknown / missing (/ uncertain on a BGK-LV map) or an integer bit mask, as frontier takes
+        them.  Returns a dict: steps (uint32, shape dims) when named in `fields`, target_steps (uint32) when targets is given
+        — fields=() with targets fetches the targets' steps alone — n_seeded (distinct passable seeds), n_reached (voxels
+        with finite steps), levels (the largest finite step; == max_steps: the wave may have been cut); plus origin,
+        block_key, cell as box() returns them.  At most 2^28 voxels in the region padded by one.  A device-resident map runs
+        the wave on the device pool, one launch per level (no host mirror refresh); a host-mode map runs a queue BFS on the
+        CPU, with identical results."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and (d[0] + 2) * (d[1] + 2) * (d[2] + 2) <= REACH_MAX_CELLS else 1)(d[0] * d[1] * d[2]))
+        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - {"steps"}
+        if bad:
+            raise ValueError(f"reach: unknown fields {sorted(bad)}")
+        masks = []
+        for m in (passable, obstacles):
+            if isinstance(m, str):
+                m = (m,)
+            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
+        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        t = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        nt = 0 if t is None else t.size
+        max_steps = REACH_MAX_STEPS if max_steps is None else int(max_steps)
+        if not all(0 <= v < 2 ** 32 for v in masks + [int(clearance), int(connectivity), max_steps, s.size, nt]):
+            raise ValueError("reach: passable, obstacles, clearance, connectivity, max_steps and the numbers of seeds and targets must fit 32 bits")
+        out = {}
+        if "steps" in fields:
+            out["steps"] = np.empty(shape, np.uint32)
+        if t is not None:
+            out["target_steps"] = np.empty(nt, np.uint32)
+        o = _lib.ReachOut(out["steps"].ctypes.data if "steps" in out else None, out["target_steps"].ctypes.data if nt else None)
+        stats, info = _lib.ReachStats(), _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_reach(self._h, lo3.ctypes.data, d3.ctypes.data, s.ctypes.data if s.size else None, s.size, masks[0],
+                                          masks[1], int(clearance), int(connectivity), max_steps, t.ctypes.data if nt else None, nt,
+                                          C.byref(o), C.byref(stats), C.byref(info)))
+        out.update(n_seeded=int(stats.n_seeded), n_reached=int(stats.n_reached), levels=int(stats.levels))
         out.update(self._region_info(info))
         return out
 

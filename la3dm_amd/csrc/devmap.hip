@@ -30,6 +30,7 @@
 #include "devmap_distance.h"
 #include "devmap_frontier.h"
 #include "devmap_gain.h"
+#include "devmap_reach.h"
 
 using namespace la3dm_dev;
 
@@ -80,6 +81,7 @@ struct la3dm_devmap {
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
+    Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -675,7 +677,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -2967,6 +2969,157 @@ int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *d
     if (h.hits) DM_TRY(hipMemcpyAsync(h.hits, d.hits, 4ull * n, hipMemcpyDeviceToHost, st));
     if (h.seen) DM_TRY(hipMemcpyAsync(h.seen, sets, 4ull * words, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+// ---- reach: hop distance from seeds through the passable voxels of a region (devmap_reach.h) -------------------------
+static int reach_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                         uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
+                         const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    const std::string refusal = la3dm_region::reach_check(pass_mask, obstacle_mask, clearance, connectivity, max_steps, n_seeds, n_targets,
+                                                          seeds != nullptr, targets != nullptr, out != nullptr, out && out->steps,
+                                                          out && out->target_steps, "->");
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+    return region_resolve(dm, lo3, dims3, la3dm_region::kReach, true, true, who, g);
+}
+
+// The whole query on the map's stream; every pointer but `stats` is device memory.  The working storage is initialised
+// here on every call.  d_steps: where the dense steps are — o.steps, or the query's working storage when the caller gave
+// no array for them.  The level launches are queued LA3DM_REACH_BATCH at a time; the counts of a batch are then read, and
+// the first level that reached nothing ends the loop (the levels queued behind it saw an empty front).
+static int reach_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d_seeds, uint32_t n_seeds, uint32_t pass_mask,
+                        uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
+                        const uint32_t *d_targets, uint32_t n_targets, const la3dm_reach_out &o, la3dm_reach_stats &stats,
+                        const uint32_t *&d_steps) {
+    hipStream_t st = dm->ctx->stream;
+    const size_t n = (size_t)g.total;
+    ReachArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nx = g.dims[0];
+    a.ny = g.dims[1];
+    a.nz = g.dims[2];
+    a.PY = a.ny + 2u;
+    a.PZ = a.nz + 2u;
+    a.total = (a.nx + 2u) * a.PY * a.PZ;   // <= LA3DM_REACH_MAX_CELLS
+    a.n_words = cdiv(a.total, 32);
+    a.n_cells = (uint32_t)n;
+    const size_t stride = ((size_t)a.n_words + 3) & ~(size_t)3, n_count = ((size_t)max_steps + 1 + 3) & ~(size_t)3;
+    // layout: pass | reached | front 0 | front 1 | counts | cells.  `cells` (4 bytes per voxel) is d2 while dm_rc_bits reads
+    // it and the steps from the fill behind that launch on, where the caller gave no array for them: the order of the
+    // stream is what keeps the two uses apart.
+    DM_RESERVE(dm->reach_work, 4ull * (4 * stride + n_count + n));
+    uint32_t *base = (uint32_t *)dm->reach_work.ptr;
+    uint32_t *pass = base, *front[2] = {base + 2 * stride, base + 3 * stride}, *cells = base + 4 * stride + n_count;
+    a.pass = pass;
+    a.reached = base + stride;
+    a.count = base + 4 * stride;
+    const bool empty = dm->n_blocks == 0;   // every voxel MISSING: the pool is not read
+    const uint32_t *d2 = nullptr;
+    if (clearance > 0 && !empty) {
+        DM_RESERVE(dm->df_work, 4ull * n);
+        la3dm_distance_out dd;
+        dd.d2 = cells;
+        dd.dist = nullptr;
+        distance_launch(dm, g, obstacle_mask, clearance, dm->df_work.ptr, dd);
+        d2 = cells;
+    }
+    // (an empty map with a clearance: all voxels are obstacles, d2 = 0 everywhere, or none is)
+    const uint32_t mask = empty && clearance > 0 && ((obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : pass_mask;
+    DM_TRY(hipMemsetAsync(a.reached, 0, 4ull * (3 * stride + n_count), st));   // reached, both fronts, the counts
+    RegionArgs r = region_args(dm, g);
+    hipLaunchKernelGGL(dm_rc_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, r, a, mask, empty ? 0u : 1u, d2, pass);
+    DM_TRY(hipGetLastError());
+    a.steps = o.steps ? o.steps : cells;   // (cells held d2 until dm_rc_bits read it)
+    DM_TRY(hipMemsetAsync(a.steps, 0xFF, 4ull * n, st));
+    stats.n_seeded = stats.n_reached = stats.levels = 0;
+    if (n_seeds) {
+        hipLaunchKernelGGL(dm_rc_seed, dim3(cdiv(n_seeds, 256)), dim3(256), 0, st, a, d_seeds, n_seeds, front[0]);
+        DM_TRY(hipGetLastError());
+        void (*level_kernel)(ReachArgs, const uint32_t *, uint32_t *, uint32_t) =
+            connectivity == 6 ? dm_rc_level<6> : connectivity == 18 ? dm_rc_level<18> : dm_rc_level<26>;
+        const dim3 wgrid(cdiv(a.n_words, 256));
+        uint32_t h_count[LA3DM_REACH_BATCH + 1];
+        uint32_t level = 1, turn = 0;
+        bool ended = false;
+        while (!ended && level <= max_steps) {   // at most max_steps / LA3DM_REACH_BATCH + 1 trips
+            const uint32_t next = (uint32_t)std::min<uint64_t>((uint64_t)level + LA3DM_REACH_BATCH, (uint64_t)max_steps + 1);
+            for (uint32_t l = level; l < next; ++l, turn ^= 1u)
+                hipLaunchKernelGGL(level_kernel, wgrid, dim3(256), 0, st, a, (const uint32_t *)front[turn], front[turn ^ 1u], l);
+            DM_TRY(hipGetLastError());
+            const uint32_t from = level == 1 ? 0u : level;   // (the first batch brings n_seeded along)
+            DM_TRY(hipMemcpyAsync(h_count, a.count + from, 4ull * (next - from), hipMemcpyDeviceToHost, st));
+            DM_TRY(hipStreamSynchronize(st));
+            if (level == 1) stats.n_seeded = stats.n_reached = h_count[0];
+            for (uint32_t l = level; l < next && !ended; ++l) {
+                const uint32_t c = h_count[l - from];
+                if (c == 0) {
+                    ended = true;
+                } else {
+                    stats.n_reached += c;
+                    stats.levels = l;
+                }
+            }
+            level = next;
+        }
+    }
+    if (n_targets) {
+        hipLaunchKernelGGL(dm_rc_gather, dim3(cdiv(n_targets, 256)), dim3(256), 0, st, (const uint32_t *)a.steps, a.n_cells, d_targets,
+                           n_targets, o.target_steps);
+        DM_TRY(hipGetLastError());
+    }
+    d_steps = a.steps;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_reach_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
+                              uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
+                              uint32_t max_steps, const uint32_t *d_targets, uint32_t n_targets, const la3dm_reach_out *d_out,
+                              la3dm_reach_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = reach_resolve(dm, lo3, dims3, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, d_targets,
+                           n_targets, d_out, "la3dm_devmap_reach_device", g);
+    if (rc != LA3DM_OK) return rc;
+    la3dm_reach_stats s;
+    const uint32_t *d_steps = nullptr;
+    rc = reach_launch(dm, g, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, d_targets, n_targets,
+                      *d_out, s, d_steps);
+    if (rc != LA3DM_OK) return rc;
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    if (stats) *stats = s;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_reach_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                            uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
+                            uint32_t max_steps, const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out,
+                            la3dm_reach_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = reach_resolve(dm, lo3, dims3, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, targets,
+                           n_targets, out, "la3dm_devmap_reach_host", g);
+    if (rc != LA3DM_OK) return rc;
+    const la3dm_reach_out &h = *out;
+    hipStream_t st = dm->ctx->stream;
+    // seeds and targets in `cloud`, the steps at the targets in `q_out`; the dense steps stay in the working storage
+    DM_RESERVE(dm->cloud, 4ull * n_seeds + 4ull * n_targets);
+    DM_RESERVE(dm->q_out, 4ull * n_targets);
+    uint32_t *d_seeds = (uint32_t *)dm->cloud.ptr, *d_targets = d_seeds + n_seeds;
+    if (n_seeds) DM_TRY(hipMemcpyAsync(d_seeds, seeds, 4ull * n_seeds, hipMemcpyHostToDevice, st));
+    if (n_targets) DM_TRY(hipMemcpyAsync(d_targets, targets, 4ull * n_targets, hipMemcpyHostToDevice, st));
+    la3dm_reach_out d;
+    d.steps = nullptr;
+    d.target_steps = n_targets ? (uint32_t *)dm->q_out.ptr : nullptr;
+    la3dm_reach_stats s;
+    const uint32_t *d_steps = nullptr;
+    rc = reach_launch(dm, g, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, d_targets, n_targets, d, s,
+                      d_steps);
+    if (rc != LA3DM_OK) return rc;
+    if (h.steps) DM_TRY(hipMemcpyAsync(h.steps, d_steps, 4ull * (size_t)g.total, hipMemcpyDeviceToHost, st));
+    if (n_targets) DM_TRY(hipMemcpyAsync(h.target_steps, d.target_steps, 4ull * n_targets, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (stats) *stats = s;
+    if (info) *info = g.info;
     return LA3DM_OK;
 }
 

@@ -1026,6 +1026,95 @@ void BGKOctoMap::frontier(const float *lo3, const uint32_t *dims3, uint32_t open
     }
 }
 
+// ---- reach over a region.  The host form below is the definition; the device kernels (csrc/devmap_reach.h) reproduce
+// it bit for bit.  A queue BFS over the passable voxels of the box padded by one voxel that is never passable, so a
+// neighbour is an index offset with no test at the faces.
+void BGKOctoMap::reach(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, uint32_t pass_mask,
+                       uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps, const uint32_t *targets,
+                       uint32_t n_targets, const la3dm_reach_out &out, la3dm_reach_stats *stats, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_reach_host(dmap, lo3, dims3, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps,
+                                    targets, n_targets, &out, stats, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::reach: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string refusal = la3dm_region::reach_check(pass_mask, obstacle_mask, clearance, connectivity, max_steps, n_seeds, n_targets,
+                                                          seeds != nullptr, targets != nullptr, true, out.steps != nullptr,
+                                                          out.target_steps != nullptr, ".");
+    if (!refusal.empty()) throw std::invalid_argument("BGKOctoMap::reach: " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kReach, true, "reach", g0, inf);
+    if (info) *info = inf;
+    const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2], n = nx * ny * nz;
+    const size_t PY = ny + 2, PZ = nz + 2;
+    std::vector<uint8_t> cls(n);
+    la3dm_box_out bo;
+    bo.cls = cls.data();
+    bo.leaf_depth = nullptr;
+    bo.A = bo.B = nullptr;
+    box(lo3, dims3, bo, nullptr);
+    std::vector<uint32_t> d2;
+    if (clearance > 0) {
+        d2.resize(n);
+        la3dm_distance_out dd;
+        dd.d2 = d2.data();
+        dd.dist = nullptr;
+        distance_field(lo3, dims3, obstacle_mask, clearance, dd, nullptr);
+    }
+    // open[p] = 1: padded voxel p is passable and not reached yet
+    std::vector<uint8_t> open((nx + 2) * PY * PZ, 0);
+    const auto padded = [&](size_t f) { return ((f / (ny * nz) + 1) * PY + (f / nz) % ny + 1) * PZ + f % nz + 1; };
+    const auto unpadded = [&](size_t p) { return ((p / (PY * PZ) - 1) * ny + (p / PZ) % PY - 1) * nz + p % PZ - 1; };
+    for (size_t f = 0; f < n; ++f)
+        open[padded(f)] = ((pass_mask >> cls[f]) & 1u) && (clearance == 0 || d2[f] == LA3DM_DF_FAR) ? 1 : 0;
+    std::vector<ptrdiff_t> offs;
+    const unsigned far = connectivity == 6 ? 1u : connectivity == 18 ? 2u : 3u;
+    for (int di = -1; di <= 1; ++di)
+        for (int dj = -1; dj <= 1; ++dj)
+            for (int dk = -1; dk <= 1; ++dk) {
+                const unsigned s = (unsigned)(std::abs(di) + std::abs(dj) + std::abs(dk));
+                if (s >= 1 && s <= far) offs.push_back(((ptrdiff_t)di * (ptrdiff_t)PY + dj) * (ptrdiff_t)PZ + dk);
+            }
+    std::vector<uint32_t> own_steps;
+    uint32_t *steps = out.steps;
+    if (steps == nullptr) {
+        own_steps.resize(n);
+        steps = own_steps.data();
+    }
+    std::fill(steps, steps + n, LA3DM_REACH_NONE);
+    la3dm_reach_stats s = {0, 0, 0};
+    std::vector<size_t> wave, next;
+    for (uint32_t t = 0; t < n_seeds; ++t) {
+        if (seeds[t] >= n) continue;
+        const size_t p = padded(seeds[t]);
+        if (!open[p]) continue;   // not passable, or listed before
+        open[p] = 0;
+        steps[seeds[t]] = 0;
+        wave.push_back(p);
+    }
+    s.n_seeded = s.n_reached = (uint32_t)wave.size();
+    for (uint32_t level = 1; level <= max_steps && !wave.empty(); ++level) {
+        next.clear();
+        for (const size_t p : wave)
+            for (const ptrdiff_t o : offs) {
+                const size_t q = (size_t)((ptrdiff_t)p + o);
+                if (!open[q]) continue;
+                open[q] = 0;
+                steps[unpadded(q)] = level;
+                next.push_back(q);
+            }
+        if (!next.empty()) {
+            s.levels = level;
+            s.n_reached += (uint32_t)next.size();
+        }
+        wave.swap(next);
+    }
+    for (uint32_t t = 0; t < n_targets; ++t) out.target_steps[t] = targets[t] < n ? steps[targets[t]] : LA3DM_REACH_NONE;
+    if (stats) *stats = s;
+}
+
 // ---- gain of candidate viewpoints.  The host form below is the definition; the device kernels (csrc/devmap_gain.h)
 // reproduce it bit for bit.  Per segment the loop is raycast_many's, row for row; what is added is the mark: the row's
 // lattice position (block-key fields * lim + the cell of its node key) against the region, and one bit per voxel and

@@ -467,6 +467,18 @@ public:
     void gain(const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n, const float *offsets3, uint32_t m,
               uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, const la3dm_gain_out &out,
               la3dm_region_info *info = nullptr) const;
+    /// Reach over box's region (contract: include/la3dm_hip.h, la3dm_devmap_reach_host): steps[v] = the least number of
+    /// moves (connectivity 6, 18 or 26) from any seed to v through passable voxels of the region — class (box's cls) in
+    /// `pass_mask` and, with clearance > 0, distance_field(obstacle_mask, radius = clearance) FAR — LA3DM_REACH_NONE where
+    /// there is no such walk of at most max_steps moves.  seeds / targets are flat indices; out.target_steps = the steps at
+    /// the targets; stats (may be null) = seeded and reached voxels and the largest finite step.  Diagonal moves are not
+    /// tested for corner cutting.  Bad arguments throw std::invalid_argument.  A device-resident map runs a level-per-launch
+    /// wave on the device pool (no mirror refresh); a host-mode map runs a queue BFS over box's classes and its own distance
+    /// transform: that form is the definition, and both give the same integers.
+    void reach(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, uint32_t pass_mask,
+               uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps, const uint32_t *targets,
+               uint32_t n_targets, const la3dm_reach_out &out, la3dm_reach_stats *stats = nullptr,
+               la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {

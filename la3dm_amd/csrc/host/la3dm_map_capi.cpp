@@ -411,6 +411,17 @@ int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, 
         return 0;)
 }
 
+int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                    uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
+                    const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,
+                    la3dm_region_info *info) {
+    GUARD(
+        if (out == nullptr) throw std::invalid_argument("BGKOctoMap::reach: out is NULL");
+        m->map->reach(lo3, dims3, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, targets, n_targets, *out,
+                      stats, info);
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);

@@ -27,6 +27,7 @@ constexpr Query kColumns = {1ull << 30, "dims: more than 2^30 columns", true, fa
 constexpr Query kDistance = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, "out: d2 or dist must not be NULL"};
 constexpr Query kFrontier = {LA3DM_FR_MAX_CELLS, "dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
 constexpr Query kGain = {LA3DM_GAIN_MAX_CELLS, "dims: more than LA3DM_GAIN_MAX_CELLS (2^28) voxels", false, false, ""};
+constexpr Query kReach = {LA3DM_REACH_MAX_CELLS, "dims: more than LA3DM_REACH_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
 
 struct Anchor {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
@@ -120,6 +121,28 @@ inline std::string gain_buffers(uint64_t total, uint32_t n, bool has_origins, bo
     if (!has_offsets) return "offsets3 is NULL";
     if (!has_out) return "out is NULL";
     if (!has_gain) return std::string("out") + member + "gain must not be NULL";
+    return "";
+}
+
+// the checks of reach's own arguments and buffers, all before the region's (`member` as in resolve)
+inline std::string reach_check(uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
+                               uint32_t n_seeds, uint32_t n_targets, bool has_seeds, bool has_targets, bool has_out, bool has_steps,
+                               bool has_target_steps, const char *member) {
+    if (pass_mask == 0 || (pass_mask & ~0x1Fu)) return "pass_mask must hold at least one of the bits 0x1F and no other";
+    if (obstacle_mask & ~0x1Fu) return "obstacle_mask must hold no bit above 0x1F";
+    if (clearance > 0 && obstacle_mask == 0) return "obstacle_mask must hold at least one of the bits 0x1F with clearance > 0";
+    if (clearance > LA3DM_DF_MAX_RADIUS) return "clearance must not exceed LA3DM_DF_MAX_RADIUS (1024)";
+    if (connectivity != 6 && connectivity != 18 && connectivity != 26) return "connectivity must be 6, 18 or 26";
+    if (max_steps == 0 || max_steps > LA3DM_REACH_MAX_STEPS) return "max_steps must lie in [1, LA3DM_REACH_MAX_STEPS (2^16)]";
+    if (n_seeds > LA3DM_REACH_MAX_SEEDS) return "n_seeds: more than LA3DM_REACH_MAX_SEEDS (2^20) seeds";
+    if (n_targets > (1u << 28)) return "n_targets: more than 2^28 targets";
+    if (n_seeds > 0 && !has_seeds) return "seeds is NULL with n_seeds > 0";
+    if (n_targets > 0 && !has_targets) return "targets is NULL with n_targets > 0";
+    if (!has_out) return "out is NULL";
+    const std::string out = std::string("out") + member;
+    if (!has_steps && !has_target_steps) return out + "steps or " + out + "target_steps must not be NULL";
+    if (has_target_steps && n_targets == 0) return out + "target_steps is set with n_targets = 0";
+    if (!has_target_steps && n_targets > 0) return out + "target_steps must not be NULL with n_targets > 0";
     return "";
 }
 
