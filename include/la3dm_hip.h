@@ -238,9 +238,15 @@ int la3dm_bgklv_scan_host(la3dm_ctx *ctx, const la3dm_lv_scan *scan, la3dm_bgk_c
 int la3dm_bgklv_scan_device(la3dm_ctx *ctx, const la3dm_lv_scan *scan, void *stream, la3dm_bgk_counters *out);
 
 /* Kernel timing.  After la3dm_set_option(ctx, "time_kernel", 1) every *_scan_device call
- * brackets its dominant kernel (bgk_predict_fuse) with HIP events on the launch stream.
- * This call waits for them, writes the elapsed milliseconds of each launch since the
- * last call (oldest first, at most cap) and resets the list. */
+ * times its dominant kernel with a pair of HIP events on the launch stream.
+ * la3dm_bgk_scan_device (one launch: bgk_predict_fuse_*; bgk_prepare is not in the figure)
+ * hands the pair to the launch itself (hipExtLaunchKernelGGL): the stop event is bound to the
+ * kernel's own dispatch packet and costs nothing on the stream; the start event is, with the
+ * HIP 7.2 runtime, still one marker packet ahead of the kernel (measured: DESIGN section 5,
+ * profiles/step_gap).  The GP and BGK-LV scans, whose dominant step is several launches, record
+ * one event before and one after them (two marker packets on the stream).
+ * This call waits for the events, writes the elapsed milliseconds of each scan call since the
+ * last call (oldest first, at most cap; *n_out = how many there were) and resets the list. */
 int la3dm_kernel_times(la3dm_ctx *ctx, float *ms, uint32_t cap, uint32_t *n_out);
 
 /* Diagnostics used by the parity tests: evaluate one primitive of the device

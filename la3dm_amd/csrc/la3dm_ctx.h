@@ -42,7 +42,11 @@ struct la3dm_ctx {
     int opt_l_split_rows = 1024;  // BGK-L: tiles with more rows than this are split over waves (< 0: never); measured on the 200 k-ray scan, round 5 (order-free sums, row cull): 8192 1.67 ms, 4096 1.63, 2048 1.30, 1024 1.27, 512 1.27 (round 2, ordered: 2048 was the optimum)
     int opt_lds_pad = 0;  // profiling only: extra dynamic LDS bytes on the BGK predict launch (lowers the waves a CU holds)
     int opt_ablate = 0;  // profiling only: 1 skip kernel evaluation, 2 skip the candidate tests
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;  // events around the dominant kernel
+    struct EvPair {
+        hipEvent_t first = nullptr, second = nullptr;
+        unsigned flags = 0;  // what hipEventCreateWithFlags was given
+    };
+    std::vector<EvPair> ev_pool;  // start / stop events of the dominant kernel, one pair per *_scan_device call (KernelTimer below)
     size_t ev_used = 0;
     // scratch (device-pointer path)
     Arena pts_scaled, nbr_range, blk_desc, label_seq;
@@ -82,6 +86,56 @@ static inline int arena_reserve(la3dm_ctx *ctx, Arena &a, size_t bytes) {
         return LA3DM_ERR_OOM;
     }
     a.cap = want;
+    return LA3DM_OK;
+}
+
+// ---- kernel timing (option "time_kernel"): the start / stop events of one *_scan_device call's dominant kernel ----
+// Two forms.  Marker form (timer_begin / timer_end round any number of launches): each is a hipEventRecord, a packet of
+// its own on the stream.  Dispatch-bound form (one launch): timer_acquire(.., true), then start and stop are handed to
+// hipExtLaunchKernelGGL.  The stop event is then the completion of the kernel's own dispatch packet, no packet of its own;
+// the start event is still a marker ahead of the kernel with the HIP 7.2 runtime (profiles/step_gap: 3.9 us per step on
+// configs[1], against 7.5 us for the two markers; a launch with the stop event alone costs nothing, but hipEventElapsedTime
+// of that event with itself is 0, so it gives no kernel time).
+struct KernelTimer {
+    hipEvent_t start = nullptr, stop = nullptr;  // both null: "time_kernel" is 0, nothing to do
+    explicit operator bool() const { return start != nullptr; }
+};
+
+// the next pair of the context's pool (la3dm_kernel_times reads them oldest first and resets the pool); t stays empty when
+// "time_kernel" is 0
+static inline int timer_acquire(la3dm_ctx *ctx, KernelTimer &t, bool dispatch_bound) {
+    t = KernelTimer();
+    if (!ctx->opt_time_kernel) return LA3DM_OK;
+    // Dispatch-bound pairs are created with hipEventDisableSystemFence: the host reads nothing on the strength of these
+    // events — la3dm_kernel_times takes their timestamps only, and results reach the host through the stream synchronisation
+    // or copy that follows the scan anyway — so the kernel keeps the fence scope of a plain launch.
+    const unsigned flags = dispatch_bound ? hipEventDisableSystemFence : hipEventDefault;
+    if (ctx->ev_used == ctx->ev_pool.size()) ctx->ev_pool.emplace_back();
+    la3dm_ctx::EvPair &p = ctx->ev_pool[ctx->ev_used];
+    if (p.first && p.flags != flags) {  // a pair left by the other form
+        HIP_TRY(ctx, hipEventDestroy(p.first));
+        p.first = nullptr;
+    }
+    if (p.second && p.flags != flags) {
+        HIP_TRY(ctx, hipEventDestroy(p.second));
+        p.second = nullptr;
+    }
+    p.flags = flags;
+    if (!p.first) HIP_TRY(ctx, hipEventCreateWithFlags(&p.first, flags));
+    if (!p.second) HIP_TRY(ctx, hipEventCreateWithFlags(&p.second, flags));
+    ++ctx->ev_used;
+    t.start = p.first;
+    t.stop = p.second;
+    return LA3DM_OK;
+}
+static inline int timer_begin(la3dm_ctx *ctx, KernelTimer &t, hipStream_t stream) {
+    int rc = timer_acquire(ctx, t, false);
+    if (rc != LA3DM_OK) return rc;
+    if (t) HIP_TRY(ctx, hipEventRecord(t.start, stream));
+    return LA3DM_OK;
+}
+static inline int timer_end(la3dm_ctx *ctx, const KernelTimer &t, hipStream_t stream) {
+    if (t) HIP_TRY(ctx, hipEventRecord(t.stop, stream));
     return LA3DM_OK;
 }
 

@@ -3,6 +3,7 @@
 // There is no CPU fallback anywhere in this file.
 #include "../../include/la3dm_hip.h"
 
+#include <hip/hip_ext.h>
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,17 +104,8 @@ static int lv_run_planned(la3dm_ctx *ctx, LvArgs &a, const uint32_t totals[4], h
     a.sub_info = (unsigned long long *)ctx->lvp_sub_out.ptr;
     a.sub_nz = a.sub_info + n_subs;
     a.sub_y = a.sub_nz + kWords * n_subs;
-    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-    if (ctx->opt_time_kernel) {
-        if (ctx->ev_used == ctx->ev_pool.size()) {
-            std::pair<hipEvent_t, hipEvent_t> p;
-            HIP_TRY(ctx, hipEventCreate(&p.first));
-            HIP_TRY(ctx, hipEventCreate(&p.second));
-            ctx->ev_pool.push_back(p);
-        }
-        ev = &ctx->ev_pool[ctx->ev_used++];
-        HIP_TRY(ctx, hipEventRecord(ev->first, stream));
-    }
+    KernelTimer tm;
+    if ((rc = timer_begin(ctx, tm, stream)) != LA3DM_OK) return rc;
     if (ctx->opt_bgk_sum == 1) {
         // order-free accumulate mode (the default): double sums per voxel, a split cube's workgroups leave 1 KB of partial sums
         // (without the 16 KB tile four workgroups fit a CU: the 8-waves-per-SIMD build, 0.755 -> 0.661 ms on the 50 k-ray scan)
@@ -123,7 +115,7 @@ static int lv_run_planned(la3dm_ctx *ctx, LvArgs &a, const uint32_t totals[4], h
         hipLaunchKernelGGL(bgklv_voxel_kernel<false>, dim3(n_subs), dim3(kLvWaves * kWave), 0, stream, a);
         if (n_split) hipLaunchKernelGGL(bgklv_split_add_kernel, dim3(n_split), dim3(kLvWaves * kWave), 0, stream, a);
     }
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev->second, stream));
+    if ((rc = timer_end(ctx, tm, stream)) != LA3DM_OK) return rc;
     HIP_TRY(ctx, hipGetLastError());
     return LA3DM_OK;
 }
@@ -280,8 +272,8 @@ void la3dm_destroy(la3dm_ctx *ctx) {
     for (Arena *a : all)
         if (a->ptr) (void)hipFree(a->ptr);
     for (auto &p : ctx->ev_pool) {
-        (void)hipEventDestroy(p.first);
-        (void)hipEventDestroy(p.second);
+        if (p.first) (void)hipEventDestroy(p.first);
+        if (p.second) (void)hipEventDestroy(p.second);
     }
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -496,23 +488,19 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     a.occupied_thresh = ctx->p.occupied_thresh;
     a.var_thresh = ctx->p.var_thresh;
     dim3 grid((a.n_tasks + kWavesPerWG - 1) / kWavesPerWG), block(kWavesPerWG * kWave);
-    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-    if (ctx->opt_time_kernel) {
-        if (ctx->ev_used == ctx->ev_pool.size()) {
-            std::pair<hipEvent_t, hipEvent_t> p;
-            HIP_TRY(ctx, hipEventCreate(&p.first));
-            HIP_TRY(ctx, hipEventCreate(&p.second));
-            ctx->ev_pool.push_back(p);
-        }
-        ev = &ctx->ev_pool[ctx->ev_used++];
-        HIP_TRY(ctx, hipEventRecord(ev->first, stream));
-    }
-#define LAUNCH_BGK(KERNEL, ...)                                                                 \
-    switch (ctx->opt_fast_trig) {                                                              \
-    case 1: hipLaunchKernelGGL((KERNEL<1 __VA_ARGS__>), grid, block, (size_t)ctx->opt_lds_pad, stream, a); break;     \
-    case 2: hipLaunchKernelGGL((KERNEL<2 __VA_ARGS__>), grid, block, (size_t)ctx->opt_lds_pad, stream, a); break;     \
-    case 3: hipLaunchKernelGGL((KERNEL<3 __VA_ARGS__>), grid, block, (size_t)ctx->opt_lds_pad, stream, a); break;     \
-    default: hipLaunchKernelGGL((KERNEL<0 __VA_ARGS__>), grid, block, (size_t)ctx->opt_lds_pad, stream, a); break;    \
+    // "time_kernel" 1: the start / stop events go to the launch itself (hipExtLaunchKernelGGL, flags 0: in stream order, the next
+    // scan reads what this one wrote) — no marker packet after the kernel, see KernelTimer for the one before it; 0: the plain launch
+    KernelTimer tm;
+    if ((rc = timer_acquire(ctx, tm, true)) != LA3DM_OK) return rc;
+#define LAUNCH_BGK_AS(K)                                                                                               \
+    if (tm) hipExtLaunchKernelGGL((K), grid, block, (uint32_t)ctx->opt_lds_pad, stream, tm.start, tm.stop, 0u, a);     \
+    else hipLaunchKernelGGL((K), grid, block, (size_t)ctx->opt_lds_pad, stream, a);
+#define LAUNCH_BGK(KERNEL, ...)                                \
+    switch (ctx->opt_fast_trig) {                             \
+    case 1: LAUNCH_BGK_AS((KERNEL<1 __VA_ARGS__>)) break;     \
+    case 2: LAUNCH_BGK_AS((KERNEL<2 __VA_ARGS__>)) break;     \
+    case 3: LAUNCH_BGK_AS((KERNEL<3 __VA_ARGS__>)) break;     \
+    default: LAUNCH_BGK_AS((KERNEL<0 __VA_ARGS__>)) break;    \
     }
     if (sum_f64) {
         grid = dim3(a.n_tasks);
@@ -541,7 +529,7 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
         }
     }
 #undef LAUNCH_BGK
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev->second, stream));
+#undef LAUNCH_BGK_AS
     HIP_TRY(ctx, hipGetLastError());
     if (out) {
         out->n_tiles = a.n_tasks;
@@ -709,17 +697,8 @@ int la3dm_gp_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_,
         if (max_n > (uint32_t)kGpTrainLdsMaxN)
             hipLaunchKernelGGL(gp_train_kernel, dim3(s->n_train_blk), dim3(kWave), 0, stream, a);
     }
-    std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
-    if (ctx->opt_time_kernel) {
-        if (ctx->ev_used == ctx->ev_pool.size()) {
-            std::pair<hipEvent_t, hipEvent_t> p;
-            HIP_TRY(ctx, hipEventCreate(&p.first));
-            HIP_TRY(ctx, hipEventCreate(&p.second));
-            ctx->ev_pool.push_back(p);
-        }
-        ev = &ctx->ev_pool[ctx->ev_used++];
-        HIP_TRY(ctx, hipEventRecord(ev->first, stream));
-    }
+    KernelTimer tm;
+    if ((rc = timer_begin(ctx, tm, stream)) != LA3DM_OK) return rc;
     if (eigen_order) {
         hipLaunchKernelGGL(gp_predict_fuse_eigen_kernel, dim3(a.n_tasks), dim3(kWave), (size_t)(max_n ? max_n : 1u) * kWave * sizeof(float), stream, a);
     } else {
@@ -738,7 +717,7 @@ int la3dm_gp_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_,
             hipLaunchKernelGGL(gp_predict_fuse_kernel, dim3(a.n_tasks), dim3(kWave),
                                std::max<size_t>(lds, 3 * 32 * 36 * sizeof(float)) /* gp_solve_mfma's three tile buffers */, stream, a);
     }
-    if (ev) HIP_TRY(ctx, hipEventRecord(ev->second, stream));
+    if ((rc = timer_end(ctx, tm, stream)) != LA3DM_OK) return rc;
     HIP_TRY(ctx, hipGetLastError());
     if (out) {
         out->n_tiles = a.n_tasks;
