@@ -37,7 +37,8 @@ enum {
     LA3DM_ERR_HIP = -2,      /* a HIP runtime call failed */
     LA3DM_ERR_NODEVICE = -3, /* no usable HIP device */
     LA3DM_ERR_OOM = -4,      /* device arena allocation failed */
-    LA3DM_ERR_PEER = -5      /* block-sharded insert: another rank failed in its rank-local work; every rank gives the insert up */
+    LA3DM_ERR_PEER = -5,     /* block-sharded insert: another rank failed in its rank-local work; every rank gives the insert up */
+    LA3DM_ERR_LIMIT = -6     /* a bounded loop of a query ran out before its answer was complete (travel: LA3DM_TRAVEL_MAX_ROUNDS) */
 };
 
 /* Occupancy state codes, include/bgkoctomap/bgkoctree_node.h:10-12 */
@@ -680,6 +681,98 @@ int la3dm_devmap_reach_device(la3dm_devmap *dm, const float *lo3, const uint32_t
                               uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
                               uint32_t max_steps, const uint32_t *d_targets, uint32_t n_targets, const la3dm_reach_out *d_out,
                               la3dm_reach_stats *stats, la3dm_region_info *info);
+/* Travel: the least path cost from seed voxels through the passable voxels of a region, with weighted moves, a soft
+ * penalty near obstacles and a parent per voxel to drive along — reach with costs.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; cls(v)
+ *     is what box reports for voxel v (FREE 0, OCCUPIED 1, UNKNOWN 2, MISSING 3, a BGK-LV map's UNCERTAIN 4).
+ *   Distance.  Only when clearance > 0 or soft_radius > 0: R = max(clearance, soft_radius) and d2 = distance_field(lo,
+ *     dims, obstacle_mask, radius = R) over the same region.  Obstacles outside the region are not seen, as for reach.
+ *     obstacle_mask is ignored when R = 0.
+ *   Passable.  v is passable iff pass_mask & (1u << cls(v)) is set and (clearance == 0 or d2[v] == LA3DM_DF_FAR or
+ *     d2[v] > clearance^2).  With soft_radius = 0 this is reach's rule.
+ *   Penalty.  pen(v) = floor(penalty * (S2 - d2[v]) / S2) with S2 = soft_radius^2 where soft_radius > 0 and d2[v] <= S2,
+ *     and 0 elsewhere: a 64-bit product and a floor division; it falls linearly in the squared distance from just under
+ *     `penalty` next to an obstacle to 0 at soft_radius.
+ *   Moves.  connectivity is 6, 18 or 26 with frontier's offset sets.  A move along an offset with 1, 2 or 3 non-zero
+ *     components costs move_cost[0], move_cost[1] or move_cost[2]: 10 / 14 / 17 approximates metres x 10 / resolution,
+ *     1 / 1 / 1 makes cost equal reach's steps.  Diagonal moves are not tested for corner cutting, as for reach.
+ *   Cost.  Entering passable v from passable u costs the move + pen(v).  A seeded voxel costs 0: its own penalty is not
+ *     charged.  cost[v] = the minimum over all walks inside the region from any seeded voxel, LA3DM_TRAVEL_NONE where v
+ *     is not passable, where no walk exists, or where the least cost exceeds max_cost.  (Candidates above max_cost are
+ *     dropped while relaxing; every prefix of a least-cost walk is cheaper than the walk, so no cost <= max_cost changes.)
+ *   Seeds and targets.  As reach's: a seed that is out of range (>= nx ny nz) or not passable is ignored, n_seeded counts
+ *     the DISTINCT passable voxels among the seeds, n_seeds = 0 is served.  target_cost[t] = cost[targets[t]], and
+ *     LA3DM_TRAVEL_NONE for an index out of range.
+ *   Parent (optional, dense uint8).  An offset (di, dj, dk) has the code q = (di + 1) * 9 + (dj + 1) * 3 + (dk + 1).  A
+ *     seeded voxel gets 13, an unreached voxel 255, any other reached v the smallest q such that the connectivity allows
+ *     the offset, u = v + offset lies in the region, cost[u] is finite and cost[u] + move + pen(v) == cost[v].  Such a q
+ *     exists and is a function of `cost` alone; following parents strictly lowers the cost and ends at a seeded voxel.
+ *   Stats (always a host struct, may be NULL).  Contract: n_seeded, n_reached (voxels with a finite cost, seeds
+ *     included), max_cost (the largest finite cost, 0 when nothing is reached).  Diagnostics of the device form, all 0 in
+ *     the host form and no part of device == host: rounds (launches of the round kernel in which a voxel changed),
+ *     brick_runs (brick relaxations run), capped (those that stopped at LA3DM_TRAVEL_INNER iterations).
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written, nothing reserved), before the
+ *     region's own checks: a NULL params; a pass_mask of 0 or with bits above 0x1F; an obstacle_mask with bits above 0x1F,
+ *     or 0 with R > 0; clearance or soft_radius > LA3DM_DF_MAX_RADIUS; soft_radius > 0 with penalty 0; penalty >
+ *     LA3DM_TRAVEL_MAX_PENALTY; a move_cost of 0 or > LA3DM_TRAVEL_MAX_MOVE; a connectivity other than 6, 18, 26;
+ *     max_cost outside 1 ... LA3DM_TRAVEL_MAX_COST; n_seeds > LA3DM_TRAVEL_MAX_SEEDS; n_targets > 2^28; a NULL seeds or
+ *     targets with a non-zero count; a NULL out, or an out with neither cost nor target_cost (parent alone is not
+ *     enough); target_cost set with n_targets = 0 or unset with n_targets > 0.  Then what box refuses for lo and dims, and
+ *     a region whose axes, each rounded up to a multiple of LA3DM_TRAVEL_BRICK, hold more than LA3DM_TRAVEL_MAX_CELLS
+ *     voxels.  No sum overflows 32 bits: a candidate is at most 2^31 + 2^17.
+ *   Non-convergence.  A call that needs more than LA3DM_TRAVEL_MAX_ROUNDS rounds fails with LA3DM_ERR_LIMIT and a text
+ *     that says so; the outputs are then unspecified.
+ *   An empty map (every voxel MISSING) is answered from the definition without reading the pool, as reach does.
+ *   Integers throughout, and the answer is unique: the results equal the host form (BGKOctoMap::travel on a host-mode
+ *     map: box's classes, the host distance transform, Dijkstra with a binary heap, then the parent pass) exactly.
+ *   Device form (csrc/devmap_travel.h): min-plus relaxation to its fixed point, which is unique whatever the order of the
+ *     relaxations.  The cost lives in bricks of LA3DM_TRAVEL_BRICK^3 voxels; one workgroup relaxes one brick in LDS until
+ *     nothing changes (at most LA3DM_TRAVEL_INNER iterations) before anything is written back, so a round moves the wave
+ *     by a brick.  The host queues LA3DM_TRAVEL_BATCH rounds, reads that batch's counts and stops at the first round in
+ *     which no voxel changed.  Working storage, in a grow-only arena of the devmap (released with it, re-initialised on
+ *     every call; a second call at the same or a smaller size allocates nothing): 12 bytes per voxel of the region
+ *     rounded up to whole bricks (two cost buffers, the entry words), 16 bytes per brick and the round counts; with
+ *     R > 0 also 4 bytes per voxel for d2 and distance_field's own working storage. */
+#define LA3DM_TRAVEL_NONE        0xFFFFFFFFu
+#define LA3DM_TRAVEL_MAX_CELLS   (1u << 28)
+#define LA3DM_TRAVEL_MAX_COST    (1u << 31)
+#define LA3DM_TRAVEL_MAX_MOVE    (1u << 16)
+#define LA3DM_TRAVEL_MAX_PENALTY (1u << 16)
+#define LA3DM_TRAVEL_MAX_SEEDS   (1u << 20)
+#define LA3DM_TRAVEL_MAX_ROUNDS  (1u << 16)
+#define LA3DM_TRAVEL_BRICK       8
+#define LA3DM_TRAVEL_INNER       16
+#define LA3DM_TRAVEL_BATCH       8
+typedef struct la3dm_travel_params {
+    uint32_t pass_mask, obstacle_mask;
+    uint32_t clearance;      /* voxels; 0: none */
+    uint32_t soft_radius;    /* voxels; 0: no penalty */
+    uint32_t penalty;        /* cost units at distance 0 */
+    uint32_t move_cost[3];   /* moves with 1, 2, 3 non-zero components */
+    uint32_t connectivity;   /* 6, 18, 26 */
+    uint32_t max_cost;       /* 1 ... LA3DM_TRAVEL_MAX_COST */
+} la3dm_travel_params;
+typedef struct la3dm_travel_out {
+    uint32_t *cost;         /* [nx ny nz] or NULL */
+    uint32_t *target_cost;  /* [n_targets] or NULL; at least one of the two */
+    uint8_t *parent;        /* [nx ny nz] or NULL */
+} la3dm_travel_out;
+typedef struct la3dm_travel_stats {
+    uint32_t n_seeded;    /* distinct passable voxels among the seeds */
+    uint32_t n_reached;   /* voxels with a finite cost, seeds included */
+    uint32_t max_cost;    /* the largest finite cost */
+    uint32_t rounds, brick_runs, capped;   /* diagnostics of the device form */
+} la3dm_travel_stats;
+/* host pointers: upload of the seeds and targets, the launches, download of what was asked for, synchronise — on the
+ * map's stream */
+int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                             const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets,
+                             const la3dm_travel_out *out, la3dm_travel_stats *stats, la3dm_region_info *info);
+/* device pointers (seeds, targets and out's arrays already in HBM on the map's device, cost and target_cost 4-byte
+ * aligned; lo3, dims3, params, stats and info stay host-side); returns when the results are complete */
+int la3dm_devmap_travel_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
+                               const la3dm_travel_params *params, const uint32_t *d_targets, uint32_t n_targets,
+                               const la3dm_travel_out *d_out, la3dm_travel_stats *stats, la3dm_region_info *info);
 /* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

@@ -172,6 +172,17 @@ int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3,
                     uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
                     const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,
                     la3dm_region_info *info);
+/* BGKOctoMap::travel: cost[v] = the least path cost from any of the seed voxels to v through the passable voxels of box's
+ * region, with a cost per move by its number of non-zero components (params->move_cost), a penalty that falls from
+ * params->penalty next to an obstacle to 0 at params->soft_radius, and reach's clearance; LA3DM_TRAVEL_NONE where no walk
+ * of at most params->max_cost exists.  out->parent[v] = the code (di + 1) * 9 + (dj + 1) * 3 + (dk + 1) of the offset to the
+ * voxel a least-cost walk came from, 13 at a seeded voxel, 255 where unreached; out->target_cost[t] = cost[targets[t]].
+ * Contract, limits and refusals: include/la3dm_hip.h (la3dm_devmap_travel_host).  Device-resident maps relax bricks of
+ * the region on the device pool without a mirror refresh, host-mode maps run Dijkstra on the CPU; the results are
+ * identical. */
+int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                     const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
+                     la3dm_travel_stats *stats, la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

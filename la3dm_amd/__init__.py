@@ -4,6 +4,8 @@ from .bgkoctomap import BGKOctoMap, GPOctoMap, BGKLVOctoMap, BGKLOctoMap, Packed
 from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR_MAX_CELLS  # noqa: F401
 from .bgkoctomap import GAIN_MAX_CELLS, GAIN_MAX_RAYS, GAIN_MAX_WORDS  # noqa: F401
 from .bgkoctomap import REACH_NONE, REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS, REACH_BATCH  # noqa: F401
+from .bgkoctomap import TRAVEL_NONE, TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_MOVE, TRAVEL_MAX_PENALTY, TRAVEL_MAX_SEEDS  # noqa: F401
+from .bgkoctomap import TRAVEL_MAX_ROUNDS, TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH, follow_parents  # noqa: F401
 from .pcd import load_pcd  # noqa: F401
 from .synth import synthetic_scan  # noqa: F401
 

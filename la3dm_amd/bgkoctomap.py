@@ -20,6 +20,10 @@ GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: 
 REACH_NONE = 0xFFFFFFFF             # LA3DM_REACH_NONE: reach found no walk to the voxel
 REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS = 1 << 28, 1 << 16, 1 << 20   # LA3DM_REACH_MAX_*: padded voxels, max_steps, seeds
 REACH_BATCH = 32                    # LA3DM_REACH_BATCH: level launches queued between two reads of the level counts
+TRAVEL_NONE = 0xFFFFFFFF            # LA3DM_TRAVEL_NONE: travel found no walk to the voxel
+TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_SEEDS, TRAVEL_MAX_ROUNDS = 1 << 28, 1 << 31, 1 << 20, 1 << 16   # LA3DM_TRAVEL_MAX_*
+TRAVEL_MAX_MOVE = TRAVEL_MAX_PENALTY = 1 << 16
+TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH = 8, 16, 8   # LA3DM_TRAVEL_*: a brick's edge, iterations of one brick run, rounds queued between two reads of the counts
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
@@ -450,6 +454,63 @@ class BGKOctoMap:
         out.update(self._region_info(info))
         return out
 
+    def travel(self, lo, dims, seeds, passable=("free",), obstacles=("occupied",), clearance=0, soft_radius=0, penalty=0,
+               move_cost=(10, 14, 17), connectivity=26, max_cost=None, targets=None, fields=("cost",)):
+        """Least path costs from seed voxels through the passable voxels of the region of box(lo, dims), and the parents to
+        drive along.  A voxel is passable when its class (box's cls) is in `passable` and, with clearance > 0, it lies farther
+        than `clearance` voxels from every voxel of the region with a class in `obstacles`.  A move along an offset with 1, 2
+        or 3 non-zero components costs move_cost[0], [1] or [2] (10 / 14 / 17 is metres x 10 / resolution; 1 / 1 / 1 gives
+        reach's steps); entering a voxel at squared distance d2 <= soft_radius^2 from an obstacle costs
+        penalty * (soft_radius^2 - d2) // soft_radius^2 more.  seeds cost 0; one that is out of range or not passable is
+        ignored.  cost[v] = the least cost of a walk inside the region from any seed to v under `connectivity` (6, 18 or 26),
+        TRAVEL_NONE where there is none of at most max_cost (None: TRAVEL_MAX_COST).  parent[v] (uint8) = the code
+        (di + 1) * 9 + (dj + 1) * 3 + (dk + 1) of the offset to the voxel a least-cost walk came from — the smallest such code
+        — 13 at a seed and 255 where unreached: follow_parents(parent, dims, index) lists the path.  targets: flat indices,
+        e.g. frontier's index; target_cost[t] = cost[targets[t]].  passable / obstacles: names or an integer bit mask, as reach
+        takes them.  fields: any of "cost", "parent"; fields=() with targets fetches the targets' costs alone.  Returns a dict
+        with those arrays, n_seeded, n_reached, max_cost (the largest finite cost), the device form's diagnostics rounds,
+        brick_runs and capped (0 on a host-mode map), plus origin, block_key, cell as box() returns them.  A device-resident
+        map relaxes 8 x 8 x 8 bricks of the region on the device pool (no host mirror refresh); a host-mode map runs Dijkstra
+        on the CPU, with identical results."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= TRAVEL_MAX_CELLS else 1)(d[0] * d[1] * d[2]))
+        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - {"cost", "parent"}
+        if bad:
+            raise ValueError(f"travel: unknown fields {sorted(bad)}")
+        masks = []
+        for m in (passable, obstacles):
+            if isinstance(m, str):
+                m = (m,)
+            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
+        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        t = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+        nt = 0 if t is None else t.size
+        max_cost = TRAVEL_MAX_COST if max_cost is None else int(max_cost)
+        moves = [int(v) for v in move_cost]
+        if len(moves) != 3:
+            raise ValueError("travel: move_cost must hold three values")
+        words = masks + [int(clearance), int(soft_radius), int(penalty)] + moves + [int(connectivity), max_cost]
+        if not all(0 <= v < 2 ** 32 for v in words + [s.size, nt]):
+            raise ValueError("travel: the masks, clearance, soft_radius, penalty, move_cost, connectivity, max_cost and the numbers of seeds and targets must fit 32 bits")
+        p = _lib.TravelParams(words[0], words[1], words[2], words[3], words[4], (C.c_uint32 * 3)(*moves), words[8], words[9])
+        out = {}
+        if "cost" in fields:
+            out["cost"] = np.empty(shape, np.uint32)
+        if "parent" in fields:
+            out["parent"] = np.empty(shape, np.uint8)
+        if t is not None:
+            out["target_cost"] = np.empty(nt, np.uint32)
+        o = _lib.TravelOut(out["cost"].ctypes.data if "cost" in out else None, out["target_cost"].ctypes.data if nt else None,
+                           out["parent"].ctypes.data if "parent" in out else None)
+        stats, info = _lib.TravelStats(), _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_travel(self._h, lo3.ctypes.data, d3.ctypes.data, s.ctypes.data if s.size else None, s.size, C.byref(p),
+                                           t.ctypes.data if nt else None, nt, C.byref(o), C.byref(stats), C.byref(info)))
+        out.update({k: int(getattr(stats, k)) for k in ("n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")})
+        out.update(self._region_info(info))
+        return out
+
     def mirror_syncs(self):
         """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
         return int(self._M.la3dm_map_mirror_syncs(self._h))
@@ -668,3 +729,22 @@ class BGKLVOctoMap(BGKOctoMap):
 
     def lv_commit(self):
         self._chk(self._M.la3dm_map_lv_commit(self._h))
+
+
+def follow_parents(parent, dims, index):
+    """The path from flat index `index` back to its seed through travel's `parent` array (any shape of prod(dims) codes): the
+    flat indices, `index` first and the seed last.  Empty where `index` was not reached (code 255)."""
+    par = np.asarray(parent).reshape(-1)
+    ny, nz = int(dims[1]), int(dims[2])
+    f, path = int(index), []
+    while par[f] != 255:
+        path.append(f)
+        q = int(par[f])
+        if q == 13:
+            return np.array(path, np.int64)
+        if len(path) > par.size:
+            break
+        f += ((q // 9 - 1) * ny + ((q // 3) % 3 - 1)) * nz + (q % 3 - 1)
+    if path:
+        raise ValueError("follow_parents: the parents do not lead to a seed")
+    return np.zeros(0, np.int64)

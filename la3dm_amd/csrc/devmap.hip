@@ -31,6 +31,7 @@
 #include "devmap_frontier.h"
 #include "devmap_gain.h"
 #include "devmap_reach.h"
+#include "devmap_travel.h"
 
 using namespace la3dm_dev;
 
@@ -82,6 +83,7 @@ struct la3dm_devmap {
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
     Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
+    Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -677,7 +679,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->travel_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3117,6 +3119,169 @@ int la3dm_devmap_reach_host(la3dm_devmap *dm, const float *lo3, const uint32_t *
     if (rc != LA3DM_OK) return rc;
     if (h.steps) DM_TRY(hipMemcpyAsync(h.steps, d_steps, 4ull * (size_t)g.total, hipMemcpyDeviceToHost, st));
     if (n_targets) DM_TRY(hipMemcpyAsync(h.target_steps, d.target_steps, 4ull * n_targets, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (stats) *stats = s;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+// ---- travel: least path cost from seeds through the passable voxels of a region, with parents (devmap_travel.h) -------
+static int travel_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                          const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
+                          const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    const std::string refusal = la3dm_region::travel_check(params, n_seeds, n_targets, seeds != nullptr, targets != nullptr, out != nullptr,
+                                                           out && out->cost, out && out->target_cost, "->");
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+    return region_resolve(dm, lo3, dims3, la3dm_region::kTravel, true, true, who, g);
+}
+
+constexpr uint32_t kTravelCountRing = 1024;   // rounds whose counts the working storage holds before they are cleared again
+
+// The whole query on the map's stream; every pointer but `stats` is device memory.  The working storage is initialised
+// here on every call.  The rounds are queued LA3DM_TRAVEL_BATCH at a time; the counts of a batch are then read, and the
+// first round in which no voxel changed ends the loop (the rounds queued behind it found every brick inactive and only
+// copied `side`).  o.cost and o.parent may be null: dm_tv_finish then only accumulates the totals.
+static int travel_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d_seeds, uint32_t n_seeds, const la3dm_travel_params &p,
+                         const uint32_t *d_targets, uint32_t n_targets, const la3dm_travel_out &o, la3dm_travel_stats &stats) {
+    hipStream_t st = dm->ctx->stream;
+    const size_t n = (size_t)g.total;
+    TravelArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nx = g.dims[0];
+    a.ny = g.dims[1];
+    a.nz = g.dims[2];
+    a.BX = cdiv(a.nx, LA3DM_TRAVEL_BRICK);
+    a.BY = cdiv(a.ny, LA3DM_TRAVEL_BRICK);
+    a.BZ = cdiv(a.nz, LA3DM_TRAVEL_BRICK);
+    a.n_bricks = a.BX * a.BY * a.BZ;   // * 512 <= LA3DM_TRAVEL_MAX_CELLS
+    a.n_cells = (uint32_t)n;
+    for (int k = 0; k < 3; ++k) a.move[k] = p.move_cost[k];
+    a.max_cost = p.max_cost;
+    const size_t cells = (size_t)a.n_bricks * 512, per_brick = ((size_t)a.n_bricks + 3) & ~(size_t)3;
+    const size_t n_small = 4 * per_brick + (size_t)kTravelCountRing * kTvCountWords + 4;   // side x 2, active x 2, counts, totals
+    const uint32_t R = std::max(p.clearance, p.soft_radius);
+    const bool empty = dm->n_blocks == 0;   // every voxel MISSING: the pool is not read
+    const bool transform = R > 0 && !empty;
+    // layout: cost 0 | cost 1 | E | side 0 | side 1 | active 0 | active 1 | counts | totals | d2
+    DM_RESERVE(dm->travel_work, 4ull * (3 * cells + n_small + (transform ? n : 0)));
+    uint32_t *base = (uint32_t *)dm->travel_work.ptr, *small = base + 3 * cells;
+    a.cost[0] = base;
+    a.cost[1] = base + cells;
+    a.E = base + 2 * cells;
+    a.side[0] = small;
+    a.side[1] = small + per_brick;
+    a.active[0] = small + 2 * per_brick;
+    a.active[1] = small + 3 * per_brick;
+    a.count = small + 4 * per_brick;
+    a.totals = a.count + (size_t)kTravelCountRing * kTvCountWords;
+    const uint32_t *d2 = nullptr;
+    uint32_t d2_fill = LA3DM_DF_FAR;
+    if (transform) {
+        DM_RESERVE(dm->df_work, 4ull * n);
+        la3dm_distance_out dd;
+        dd.d2 = small + n_small;
+        dd.dist = nullptr;
+        distance_launch(dm, g, p.obstacle_mask, R, dm->df_work.ptr, dd);
+        d2 = dd.d2;
+    } else if (R > 0 && ((p.obstacle_mask >> LA3DM_RAY_MISSING) & 1u)) {
+        d2_fill = 0u;   // (the empty map with MISSING as an obstacle: every voxel is one)
+    }
+    DM_TRY(hipMemsetAsync(small, 0, 4ull * n_small, st));
+    RegionArgs r = region_args(dm, g);
+    hipLaunchKernelGGL(dm_tv_enter, dim3(a.n_bricks * 2u), dim3(256), 0, st, r, a, p.pass_mask, empty ? 0u : 1u, d2, d2_fill, p.clearance,
+                       p.soft_radius * p.soft_radius, p.penalty);
+    DM_TRY(hipGetLastError());
+    memset(&stats, 0, sizeof(stats));
+    uint32_t queued = 0;   // rounds launched: side[queued & 1] is the array the last of them wrote
+    if (n_seeds) {
+        hipLaunchKernelGGL(dm_tv_seed, dim3(cdiv(n_seeds, 256)), dim3(256), 0, st, a, d_seeds, n_seeds,
+                           p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3);
+        DM_TRY(hipGetLastError());
+        void (*round_kernel)(TravelArgs, uint32_t, uint32_t) =
+            p.connectivity == 6 ? dm_tv_round<6> : p.connectivity == 18 ? dm_tv_round<18> : dm_tv_round<26>;
+        uint32_t h_count[LA3DM_TRAVEL_BATCH * kTvCountWords];
+        bool ended = false;
+        while (!ended) {   // at most LA3DM_TRAVEL_MAX_ROUNDS / LA3DM_TRAVEL_BATCH trips
+            if (queued >= LA3DM_TRAVEL_MAX_ROUNDS)
+                return dm_fail(dm, LA3DM_ERR_LIMIT, "la3dm_devmap_travel: no fixed point after LA3DM_TRAVEL_MAX_ROUNDS (2^16) rounds; the outputs are unspecified");
+            const uint32_t slot = queued % kTravelCountRing;   // (a batch never straddles the ring's end: 1024 is a multiple of the batch)
+            if (slot == 0 && queued) DM_TRY(hipMemsetAsync(a.count, 0, 4ull * kTravelCountRing * kTvCountWords, st));
+            for (uint32_t q = 0; q < LA3DM_TRAVEL_BATCH; ++q)
+                hipLaunchKernelGGL(round_kernel, dim3(a.n_bricks), dim3(512), 0, st, a, (queued + q) & 1u, slot + q);
+            DM_TRY(hipGetLastError());
+            DM_TRY(hipMemcpyAsync(h_count, a.count + (size_t)slot * kTvCountWords, sizeof(h_count), hipMemcpyDeviceToHost, st));
+            DM_TRY(hipStreamSynchronize(st));
+            queued += LA3DM_TRAVEL_BATCH;
+            for (uint32_t q = 0; q < LA3DM_TRAVEL_BATCH && !ended; ++q) {
+                const uint32_t *c = h_count + q * kTvCountWords;
+                stats.brick_runs += c[1];
+                stats.capped += c[2];
+                if (c[0] == 0)
+                    ended = true;
+                else
+                    ++stats.rounds;
+            }
+        }
+    }
+    const uint32_t *side = a.side[queued & 1u];
+    void (*finish_kernel)(TravelArgs, const uint32_t *, uint32_t *, uint8_t *) =
+        p.connectivity == 6 ? dm_tv_finish<6> : p.connectivity == 18 ? dm_tv_finish<18> : dm_tv_finish<26>;
+    hipLaunchKernelGGL(finish_kernel, dim3(cdiv(a.n_cells, 256)), dim3(256), 0, st, a, side, o.cost, o.parent);
+    DM_TRY(hipGetLastError());
+    if (n_targets) {
+        hipLaunchKernelGGL(dm_tv_gather, dim3(cdiv(n_targets, 256)), dim3(256), 0, st, a, side, d_targets, n_targets, o.target_cost);
+        DM_TRY(hipGetLastError());
+    }
+    uint32_t totals[3];
+    DM_TRY(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    stats.n_seeded = totals[0];
+    stats.n_reached = totals[1];
+    stats.max_cost = totals[2];
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_travel_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
+                               const la3dm_travel_params *params, const uint32_t *d_targets, uint32_t n_targets,
+                               const la3dm_travel_out *d_out, la3dm_travel_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = travel_resolve(dm, lo3, dims3, d_seeds, n_seeds, params, d_targets, n_targets, d_out, "la3dm_devmap_travel_device", g);
+    if (rc != LA3DM_OK) return rc;
+    la3dm_travel_stats s;
+    rc = travel_launch(dm, g, d_seeds, n_seeds, *params, d_targets, n_targets, *d_out, s);   // (ends in a synchronise)
+    if (rc != LA3DM_OK) return rc;
+    if (stats) *stats = s;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                             const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
+                             la3dm_travel_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = travel_resolve(dm, lo3, dims3, seeds, n_seeds, params, targets, n_targets, out, "la3dm_devmap_travel_host", g);
+    if (rc != LA3DM_OK) return rc;
+    const la3dm_travel_out &h = *out;
+    hipStream_t st = dm->ctx->stream;
+    const size_t n = (size_t)g.total;
+    // seeds and targets in `cloud`; the dense cost, the costs at the targets and the parents in `q_out`
+    const size_t n_cost = h.cost ? n : 0, n_parent = h.parent ? n : 0;
+    DM_RESERVE(dm->cloud, 4ull * n_seeds + 4ull * n_targets);
+    DM_RESERVE(dm->q_out, 4ull * (n_cost + n_targets) + n_parent);
+    uint32_t *d_seeds = (uint32_t *)dm->cloud.ptr, *d_targets = d_seeds + n_seeds;
+    if (n_seeds) DM_TRY(hipMemcpyAsync(d_seeds, seeds, 4ull * n_seeds, hipMemcpyHostToDevice, st));
+    if (n_targets) DM_TRY(hipMemcpyAsync(d_targets, targets, 4ull * n_targets, hipMemcpyHostToDevice, st));
+    la3dm_travel_out d;
+    d.cost = h.cost ? (uint32_t *)dm->q_out.ptr : nullptr;
+    d.target_cost = n_targets ? (uint32_t *)dm->q_out.ptr + n_cost : nullptr;
+    d.parent = h.parent ? (uint8_t *)((uint32_t *)dm->q_out.ptr + n_cost + n_targets) : nullptr;
+    la3dm_travel_stats s;
+    rc = travel_launch(dm, g, d_seeds, n_seeds, *params, d_targets, n_targets, d, s);
+    if (rc != LA3DM_OK) return rc;
+    if (h.cost) DM_TRY(hipMemcpyAsync(h.cost, d.cost, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (n_targets) DM_TRY(hipMemcpyAsync(h.target_cost, d.target_cost, 4ull * n_targets, hipMemcpyDeviceToHost, st));
+    if (h.parent) DM_TRY(hipMemcpyAsync(h.parent, d.parent, n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
     if (stats) *stats = s;
     if (info) *info = g.info;

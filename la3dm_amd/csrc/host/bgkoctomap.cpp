@@ -21,8 +21,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <new>
+#include <queue>
 #include <stdexcept>
 #include <string>
 
@@ -1112,6 +1114,120 @@ void BGKOctoMap::reach(const float *lo3, const uint32_t *dims3, const uint32_t *
         wave.swap(next);
     }
     for (uint32_t t = 0; t < n_targets; ++t) out.target_steps[t] = targets[t] < n ? steps[targets[t]] : LA3DM_REACH_NONE;
+    if (stats) *stats = s;
+}
+
+// ---- travel over a region.  The host form below is the definition; the device kernels (csrc/devmap_travel.h) reproduce
+// it bit for bit.  box's classes and the host distance transform give every voxel its entry word (pen(v), or blocked);
+// Dijkstra with a binary heap gives the costs — a candidate above max_cost is dropped where it is made, which changes no
+// cost <= max_cost because every prefix of a least-cost walk is cheaper than the walk — and a pass over the voxels the
+// parents, which are a function of the costs alone.
+void BGKOctoMap::travel(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, const la3dm_travel_params &p,
+                        const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out &out, la3dm_travel_stats *stats,
+                        la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_travel_host(dmap, lo3, dims3, seeds, n_seeds, &p, targets, n_targets, &out, stats, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::travel: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string refusal = la3dm_region::travel_check(&p, n_seeds, n_targets, seeds != nullptr, targets != nullptr, true,
+                                                           out.cost != nullptr, out.target_cost != nullptr, ".");
+    if (!refusal.empty()) throw std::invalid_argument("BGKOctoMap::travel: " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kTravel, true, "travel", g0, inf);
+    if (info) *info = inf;
+    const uint32_t nx = dims3[0], ny = dims3[1], nz = dims3[2];
+    const size_t n = (size_t)nx * ny * nz;
+    std::vector<uint8_t> cls(n);
+    la3dm_box_out bo;
+    bo.cls = cls.data();
+    bo.leaf_depth = nullptr;
+    bo.A = bo.B = nullptr;
+    box(lo3, dims3, bo, nullptr);
+    const uint32_t R = std::max(p.clearance, p.soft_radius);
+    std::vector<uint32_t> d2;
+    if (R > 0) {
+        d2.resize(n);
+        la3dm_distance_out dd;
+        dd.d2 = d2.data();
+        dd.dist = nullptr;
+        distance_field(lo3, dims3, p.obstacle_mask, R, dd, nullptr);
+    }
+    std::vector<uint32_t> entry(n);   // pen(v), or blocked
+    for (size_t f = 0; f < n; ++f)
+        entry[f] = ((p.pass_mask >> cls[f]) & 1u) ? la3dm_region::travel_entry(p, R > 0 ? d2[f] : LA3DM_DF_FAR) : la3dm_region::kTravelBlocked;
+    struct Move {
+        int d[3];
+        uint32_t cost, code;
+    };
+    std::vector<Move> moves;   // in the order of the code q
+    const int far = p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3;
+    for (int di = -1; di <= 1; ++di)
+        for (int dj = -1; dj <= 1; ++dj)
+            for (int dk = -1; dk <= 1; ++dk) {
+                const int s = std::abs(di) + std::abs(dj) + std::abs(dk);
+                if (s >= 1 && s <= far) moves.push_back(Move{{di, dj, dk}, p.move_cost[s - 1], (uint32_t)((di + 1) * 9 + (dj + 1) * 3 + (dk + 1))});
+            }
+    std::vector<uint32_t> own_cost;
+    uint32_t *cost = out.cost;
+    if (cost == nullptr) {
+        own_cost.resize(n);
+        cost = own_cost.data();
+    }
+    std::fill(cost, cost + n, LA3DM_TRAVEL_NONE);
+    la3dm_travel_stats s;
+    std::memset(&s, 0, sizeof(s));
+    typedef std::pair<uint32_t, uint32_t> Item;   // (cost, flat index)
+    std::priority_queue<Item, std::vector<Item>, std::greater<Item>> heap;
+    for (uint32_t t = 0; t < n_seeds; ++t) {
+        const uint32_t f = seeds[t];
+        if (f >= n || entry[f] == la3dm_region::kTravelBlocked || cost[f] == 0) continue;   // out of range, not passable, listed before
+        cost[f] = 0;
+        ++s.n_seeded;
+        heap.push(Item(0u, f));
+    }
+    // neighbour u of voxel (i, j, k) along m, or n where it leaves the region
+    const auto neighbour = [&](uint32_t i, uint32_t j, uint32_t k, const Move &m) -> size_t {
+        const uint32_t ui = i + (uint32_t)m.d[0], uj = j + (uint32_t)m.d[1], uk = k + (uint32_t)m.d[2];   // (0 - 1 wraps above nx)
+        return ui < nx && uj < ny && uk < nz ? ((size_t)ui * ny + uj) * nz + uk : n;
+    };
+    while (!heap.empty()) {
+        const Item top = heap.top();
+        heap.pop();
+        const uint32_t f = top.second;
+        if (top.first != cost[f]) continue;   // a stale entry
+        const uint32_t k = f % nz, j = (f / nz) % ny, i = f / (nz * ny);
+        for (const Move &m : moves) {
+            const size_t v = neighbour(i, j, k, m);
+            if (v == n || entry[v] == la3dm_region::kTravelBlocked) continue;
+            const uint32_t cand = top.first + m.cost + entry[v];   // <= 2^31 + 2^17
+            if (cand > p.max_cost || cand >= cost[v]) continue;
+            cost[v] = cand;
+            heap.push(Item(cand, (uint32_t)v));
+        }
+    }
+    for (size_t f = 0; f < n; ++f) {
+        if (cost[f] != LA3DM_TRAVEL_NONE) {
+            ++s.n_reached;
+            s.max_cost = std::max(s.max_cost, cost[f]);
+        }
+        if (out.parent == nullptr) continue;
+        uint8_t code = cost[f] == LA3DM_TRAVEL_NONE ? 255 : 13;
+        if (cost[f] != LA3DM_TRAVEL_NONE && cost[f] != 0) {
+            const uint32_t k = (uint32_t)(f % nz), j = (uint32_t)((f / nz) % ny), i = (uint32_t)(f / ((size_t)nz * ny));
+            for (const Move &m : moves) {
+                const size_t u = neighbour(i, j, k, m);
+                if (u != n && cost[u] != LA3DM_TRAVEL_NONE && cost[u] + m.cost + entry[f] == cost[f]) {
+                    code = (uint8_t)m.code;
+                    break;
+                }
+            }
+        }
+        out.parent[f] = code;
+    }
+    for (uint32_t t = 0; t < n_targets; ++t) out.target_cost[t] = targets[t] < n ? cost[targets[t]] : LA3DM_TRAVEL_NONE;
     if (stats) *stats = s;
 }
 

@@ -479,6 +479,19 @@ public:
                uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps, const uint32_t *targets,
                uint32_t n_targets, const la3dm_reach_out &out, la3dm_reach_stats *stats = nullptr,
                la3dm_region_info *info = nullptr) const;
+    /// Travel over box's region (contract: include/la3dm_hip.h, la3dm_devmap_travel_host): cost[v] = the least path cost
+    /// from any seed to v through passable voxels — class in p.pass_mask and farther than p.clearance voxels from every
+    /// voxel with a class in p.obstacle_mask — where a move costs p.move_cost by its number of non-zero components plus the
+    /// entered voxel's penalty, which falls from p.penalty next to an obstacle to 0 at p.soft_radius; LA3DM_TRAVEL_NONE
+    /// where no walk of at most p.max_cost exists.  out.parent (may be null) = the code of the offset to the voxel a
+    /// least-cost walk came from, 13 at a seed, 255 where unreached; out.target_cost = the costs at the targets; stats (may
+    /// be null) = seeded and reached voxels, the largest finite cost, and the device form's diagnostics.  Bad arguments
+    /// throw std::invalid_argument.  A device-resident map relaxes bricks of the region on the device pool (no mirror
+    /// refresh); a host-mode map runs Dijkstra over box's classes and its own distance transform: that form is the
+    /// definition, and both give the same integers.
+    void travel(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, const la3dm_travel_params &p,
+                const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out &out, la3dm_travel_stats *stats = nullptr,
+                la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {

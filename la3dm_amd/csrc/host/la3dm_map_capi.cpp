@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "bgkoctomap.h"
+#include "region_contract.h"
 
 using la3dm::BGKOctoMap;
 using la3dm::point3f;
@@ -419,6 +420,19 @@ int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3,
         if (out == nullptr) throw std::invalid_argument("BGKOctoMap::reach: out is NULL");
         m->map->reach(lo3, dims3, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, targets, n_targets, *out,
                       stats, info);
+        return 0;)
+}
+
+int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                     const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
+                     la3dm_travel_stats *stats, la3dm_region_info *info) {
+    GUARD(
+        if (params == nullptr) throw std::invalid_argument("BGKOctoMap::travel: params is NULL");
+        if (out == nullptr) {   // (the query's own checks come first: a bad mask answers before a missing out)
+            const std::string refusal = la3dm_region::travel_check(params, n_seeds, n_targets, seeds != nullptr, targets != nullptr, false, false, false, ".");
+            throw std::invalid_argument("BGKOctoMap::travel: " + refusal);
+        }
+        m->map->travel(lo3, dims3, seeds, n_seeds, *params, targets, n_targets, *out, stats, info);
         return 0;)
 }
 

@@ -20,6 +20,7 @@ struct Query {
     bool columns;             // the limit counts columns, and nz has LA3DM_COLUMNS_MAX_NZ as a limit of its own
     bool padded;              // limit and block-field range are taken on the region padded by one voxel on every side
     const char *mandatory;    // refusal when the mandatory output is missing ("->" stands for the caller's member access)
+    uint32_t brick = 0;       // > 0: the limit is taken on the region with every axis rounded up to a multiple of `brick`
 };
 
 constexpr Query kBox = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, false, "out->cls must not be NULL"};
@@ -28,6 +29,8 @@ constexpr Query kDistance = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_C
 constexpr Query kFrontier = {LA3DM_FR_MAX_CELLS, "dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
 constexpr Query kGain = {LA3DM_GAIN_MAX_CELLS, "dims: more than LA3DM_GAIN_MAX_CELLS (2^28) voxels", false, false, ""};
 constexpr Query kReach = {LA3DM_REACH_MAX_CELLS, "dims: more than LA3DM_REACH_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
+constexpr Query kTravel = {LA3DM_TRAVEL_MAX_CELLS, "dims: more than LA3DM_TRAVEL_MAX_CELLS (2^28) voxels in the region rounded up to whole bricks", false, false, "",
+                           LA3DM_TRAVEL_BRICK};
 
 struct Anchor {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
@@ -48,11 +51,14 @@ inline std::string resolve(const Query &q, const float *lo, const uint32_t *dims
         if (!(std::fabs(lo[k] / resolution) < 1073741824.0f)) return "lo must be finite with |lo / resolution| < 2^30";
     for (int k = 0; k < 3; ++k)
         if (dims[k] == 0) return "dims must be >= 1 on every axis";
-    const uint64_t pad = q.padded ? 2 : 0, ncol = (uint64_t)dims[0] * dims[1], pcol = (dims[0] + pad) * (dims[1] + pad);
+    const uint64_t pad = q.padded ? 2 : 0, ncol = (uint64_t)dims[0] * dims[1];
+    uint64_t e[3];   // the extents the limit counts: padded, rounded up to whole bricks, or as they are
+    for (int k = 0; k < 3; ++k) e[k] = q.brick ? ((uint64_t)dims[k] + q.brick - 1) / q.brick * q.brick : dims[k] + pad;
+    const uint64_t pcol = e[0] * e[1];
     if (q.columns) {
         if (ncol > q.max_cells) return q.limit_text;
         if (dims[2] > LA3DM_COLUMNS_MAX_NZ) return "dims: nz exceeds LA3DM_COLUMNS_MAX_NZ (2^16)";
-    } else if (std::max(dims[0], std::max(dims[1], dims[2])) > q.max_cells || pcol > q.max_cells || pcol * (dims[2] + pad) > q.max_cells) {
+    } else if (std::max(dims[0], std::max(dims[1], dims[2])) > q.max_cells || pcol > q.max_cells || pcol * e[2] > q.max_cells) {
         return q.limit_text;   // (an axis is tested first: the products of three such axes need not fit 64 bits)
     }
     a.total = q.columns ? ncol : ncol * dims[2];
@@ -144,6 +150,44 @@ inline std::string reach_check(uint32_t pass_mask, uint32_t obstacle_mask, uint3
     if (has_target_steps && n_targets == 0) return out + "target_steps is set with n_targets = 0";
     if (!has_target_steps && n_targets > 0) return out + "target_steps must not be NULL with n_targets > 0";
     return "";
+}
+
+// the checks of travel's own arguments and buffers, all before the region's (`member` as in resolve)
+inline std::string travel_check(const la3dm_travel_params *p, uint32_t n_seeds, uint32_t n_targets, bool has_seeds, bool has_targets,
+                                bool has_out, bool has_cost, bool has_target_cost, const char *member) {
+    if (!p) return "params is NULL";
+    if (p->pass_mask == 0 || (p->pass_mask & ~0x1Fu)) return "pass_mask must hold at least one of the bits 0x1F and no other";
+    if (p->obstacle_mask & ~0x1Fu) return "obstacle_mask must hold no bit above 0x1F";
+    if ((p->clearance > 0 || p->soft_radius > 0) && p->obstacle_mask == 0)
+        return "obstacle_mask must hold at least one of the bits 0x1F with clearance > 0 or soft_radius > 0";
+    if (p->clearance > LA3DM_DF_MAX_RADIUS) return "clearance must not exceed LA3DM_DF_MAX_RADIUS (1024)";
+    if (p->soft_radius > LA3DM_DF_MAX_RADIUS) return "soft_radius must not exceed LA3DM_DF_MAX_RADIUS (1024)";
+    if (p->soft_radius > 0 && p->penalty == 0) return "penalty must be >= 1 with soft_radius > 0";
+    if (p->penalty > LA3DM_TRAVEL_MAX_PENALTY) return "penalty must not exceed LA3DM_TRAVEL_MAX_PENALTY (2^16)";
+    for (int k = 0; k < 3; ++k)
+        if (p->move_cost[k] == 0 || p->move_cost[k] > LA3DM_TRAVEL_MAX_MOVE) return "move_cost: every entry must lie in [1, LA3DM_TRAVEL_MAX_MOVE (2^16)]";
+    if (p->connectivity != 6 && p->connectivity != 18 && p->connectivity != 26) return "connectivity must be 6, 18 or 26";
+    if (p->max_cost == 0 || p->max_cost > LA3DM_TRAVEL_MAX_COST) return "max_cost must lie in [1, LA3DM_TRAVEL_MAX_COST (2^31)]";
+    if (n_seeds > LA3DM_TRAVEL_MAX_SEEDS) return "n_seeds: more than LA3DM_TRAVEL_MAX_SEEDS (2^20) seeds";
+    if (n_targets > (1u << 28)) return "n_targets: more than 2^28 targets";
+    if (n_seeds > 0 && !has_seeds) return "seeds is NULL with n_seeds > 0";
+    if (n_targets > 0 && !has_targets) return "targets is NULL with n_targets > 0";
+    if (!has_out) return "out is NULL";
+    const std::string out = std::string("out") + member;
+    if (!has_cost && !has_target_cost) return out + "cost or " + out + "target_cost must not be NULL";
+    if (has_target_cost && n_targets == 0) return out + "target_cost is set with n_targets = 0";
+    if (!has_target_cost && n_targets > 0) return out + "target_cost must not be NULL with n_targets > 0";
+    return "";
+}
+
+// travel's entry word of a voxel whose class is in pass_mask: pen(v), or kTravelBlocked where the clearance closes it.
+// d2 = distance_field's word (LA3DM_DF_FAR without a distance transform).  One definition for the host form; the device
+// kernel (csrc/devmap_travel.h, tv_entry) is its twin.
+constexpr uint32_t kTravelBlocked = 0xFFFFFFFFu;
+inline uint32_t travel_entry(const la3dm_travel_params &p, uint32_t d2) {
+    if (p.clearance > 0 && d2 != LA3DM_DF_FAR && d2 <= p.clearance * p.clearance) return kTravelBlocked;
+    const uint32_t s2 = p.soft_radius * p.soft_radius;
+    return s2 > 0 && d2 <= s2 ? (uint32_t)((uint64_t)p.penalty * (s2 - d2) / s2) : 0u;
 }
 
 }  // namespace la3dm_region
