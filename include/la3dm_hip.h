@@ -38,7 +38,7 @@ enum {
     LA3DM_ERR_NODEVICE = -3, /* no usable HIP device */
     LA3DM_ERR_OOM = -4,      /* device arena allocation failed */
     LA3DM_ERR_PEER = -5,     /* block-sharded insert: another rank failed in its rank-local work; every rank gives the insert up */
-    LA3DM_ERR_LIMIT = -6     /* a bounded loop of a query ran out before its answer was complete (travel: LA3DM_TRAVEL_MAX_ROUNDS) */
+    LA3DM_ERR_LIMIT = -6     /* a bounded loop of a query ran out before its answer was complete (travel: LA3DM_TRAVEL_MAX_ROUNDS; clusters: LA3DM_CLUSTERS_MAX_ROUNDS) */
 };
 
 /* Occupancy state codes, include/bgkoctomap/bgkoctree_node.h:10-12 */
@@ -773,7 +773,105 @@ int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t 
 int la3dm_devmap_travel_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
                                const la3dm_travel_params *params, const uint32_t *d_targets, uint32_t n_targets,
                                const la3dm_travel_out *d_out, la3dm_travel_stats *stats, la3dm_region_info *info);
-/* Leaf export = the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
+/* Clusters: the connected groups of a region's member voxels, optionally confined to tiles and cut at a minimum size —
+ * a dense label and one record per cluster (first voxel, size, bounding box, coordinate sums, a representative member).
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; cls(v)
+ *     is what box reports for voxel v.
+ *   Members.  member_mask holds the bits of stop_mask: non-zero, no bit above 0x1F.  from_list = 0: every voxel v of the
+ *     region with member_mask & (1u << cls(v)) set is a member; members and n_members are then only checked, not used.
+ *     from_list = 1: only the voxels listed in members[n_members] (flat indices, e.g. frontier's index) whose class is in
+ *     member_mask are members; an index >= nx ny nz is ignored, a voxel listed twice counts once, n_members = 0 is served
+ *     and gives no clusters.
+ *   Adjacency.  connectivity is 6, 18 or 26 with frontier's offset sets, inside the region.  tile = 0: no tiling.
+ *     Otherwise tile is a multiple of LA3DM_CLUSTERS_BRICK and at most LA3DM_CLUSTERS_MAX_TILE, and two voxels are
+ *     adjacent only if i / tile, j / tile and k / tile agree (tiles are anchored at voxel (0, 0, 0) of the region).  A
+ *     cluster is a maximal set of members connected through adjacent members.
+ *   Minimum size.  min_size >= 1; a cluster with fewer members is dropped.
+ *   Numbering.  The kept clusters are numbered 0 ... n - 1 in ascending order of `first`, their smallest flat index.
+ *     *n_found = n whatever cap is (n_found may be NULL).
+ *   Outputs (out may be NULL, and so may each array).  label[nx ny nz]: the number of the voxel's cluster,
+ *     LA3DM_CLUSTERS_NONE for a non-member or a member of a dropped cluster.  of_member[n_members] (from_list = 1 only):
+ *     the same per list entry, NONE for an ignored entry.  Records for c < min(n, cap): first[c], size[c]; lo[3c ...],
+ *     hi[3c ...]: the bounding box in voxels of the region, inclusive; sum[3c ...]: the 64-bit sums of i, j and k over
+ *     the members (the client divides); rep[c]: a member to drive to or look from — with c_a = (2 sum_a + size) /
+ *     (2 size) in integer division, the member of the cluster with the smallest (i - c_0)^2 + (j - c_1)^2 + (k - c_2)^2,
+ *     the smallest flat index among equals.  The rounded centroid need not be a member; rep always is.  cap = 0 with no
+ *     record array counts, as frontier does.
+ *   Stats (always a host struct, may be NULL).  Contract: n_members (distinct members), n_clusters (= n), n_dropped
+ *     (clusters below min_size), largest (the largest size of a kept cluster, 0 when there is none).  Diagnostics of the
+ *     device form, all 0 in the host form and no part of device == host: rounds (launches of the round kernel in which
+ *     a voxel changed), brick_runs (brick relaxations run), capped (those that stopped at LA3DM_CLUSTERS_INNER
+ *     iterations).
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written, nothing reserved), in this
+ *     order: a NULL params; a member_mask of 0 or with bits above 0x1F; a connectivity other than 6, 18, 26; a tile that
+ *     is no multiple of LA3DM_CLUSTERS_BRICK or exceeds LA3DM_CLUSTERS_MAX_TILE; min_size 0; from_list > 1; n_members >
+ *     LA3DM_CLUSTERS_MAX_MEMBERS; a NULL members with n_members > 0; of_member set with from_list = 0; cap > 0 with no
+ *     record array.  Then what box refuses for lo and dims; an axis longer than LA3DM_CLUSTERS_MAX_AXIS (the squared
+ *     distance of rep then fits 32 bits); a region whose axes, each rounded up to a multiple of LA3DM_CLUSTERS_BRICK,
+ *     hold more than LA3DM_CLUSTERS_MAX_CELLS voxels.
+ *   Non-convergence.  A call that needs more than LA3DM_CLUSTERS_MAX_ROUNDS rounds fails with LA3DM_ERR_LIMIT and a
+ *     text that says so; the outputs are then unspecified.
+ *   An empty map (every voxel MISSING) is served without reading the pool: member_mask = MISSING makes every voxel, or
+ *     every listed voxel, a member.
+ *   Integers throughout, and the answer is unique: the results equal the host form (BGKOctoMap::clusters on a host-mode
+ *     map: box's classes, a flood fill from every unlabelled member in ascending flat order, the records in one pass,
+ *     rep in a second) exactly.
+ *   Device form (csrc/devmap_clusters.h): travel's scheme with min in place of min-plus.  The label of a member starts
+ *     as its own flat index; the fixed point of "take the smallest label among yourself and your adjacent members" is
+ *     the cluster's `first`, whatever the order of the relaxations.  The labels live in bricks of LA3DM_CLUSTERS_BRICK^3
+ *     voxels; one workgroup relaxes one brick in LDS until nothing changes (at most LA3DM_CLUSTERS_INNER iterations);
+ *     the host queues LA3DM_CLUSTERS_BATCH rounds, reads that batch's counts and stops at the first round in which no
+ *     voxel changed.  Sizes, the kept flags, the map's one-launch scan over them for the numbering, the labels and the
+ *     records follow; sizes, boxes, sums and rep are reduced per wave and cluster before one atomic per group is issued.
+ *     Working storage, in two grow-only arenas of the devmap (released with it, re-initialised on every call; a second
+ *     call at the same or a smaller size allocates nothing): 8 bytes per voxel of the region rounded up to whole bricks
+ *     (two label buffers), 12 bytes per voxel of the region (sizes, flags, numbers), 16 bytes per brick, the round
+ *     counts, and 68 bytes per record written. */
+#define LA3DM_CLUSTERS_NONE        0xFFFFFFFFu
+#define LA3DM_CLUSTERS_MAX_CELLS   (1u << 28)
+#define LA3DM_CLUSTERS_MAX_AXIS    (1u << 15)
+#define LA3DM_CLUSTERS_MAX_TILE    (1u << 15)
+#define LA3DM_CLUSTERS_MAX_MEMBERS (1u << 28)
+#define LA3DM_CLUSTERS_MAX_ROUNDS  (1u << 16)
+#define LA3DM_CLUSTERS_BRICK       8
+#define LA3DM_CLUSTERS_INNER       16
+#define LA3DM_CLUSTERS_BATCH       8
+typedef struct la3dm_clusters_params {
+    uint32_t member_mask;
+    uint32_t from_list;       /* 0: every voxel of the region by its class; 1: the listed voxels only */
+    uint32_t connectivity;    /* 6, 18, 26 */
+    uint32_t tile;            /* 0: none; else a multiple of LA3DM_CLUSTERS_BRICK */
+    uint32_t min_size;        /* >= 1 */
+    uint32_t n_members;
+    const uint32_t *members;  /* [n_members] flat indices (host or device memory, as the entry point says) */
+    uint32_t cap;             /* records wanted at most */
+} la3dm_clusters_params;
+typedef struct la3dm_clusters_out {
+    uint32_t *label;       /* [nx ny nz] or NULL */
+    uint32_t *of_member;   /* [n_members] or NULL */
+    uint32_t *first;       /* [cap] or NULL */
+    uint32_t *size;        /* [cap] or NULL */
+    uint32_t *lo, *hi;     /* [3 cap] or NULL */
+    uint64_t *sum;         /* [3 cap] or NULL */
+    uint32_t *rep;         /* [cap] or NULL */
+} la3dm_clusters_out;
+typedef struct la3dm_clusters_stats {
+    uint32_t n_members;    /* distinct members */
+    uint32_t n_clusters;   /* kept clusters: n */
+    uint32_t n_dropped;    /* clusters below min_size */
+    uint32_t largest;      /* the largest size of a kept cluster */
+    uint32_t rounds, brick_runs, capped;   /* diagnostics of the device form */
+} la3dm_clusters_stats;
+/* host pointers (params->members included): upload of the list, the launches, download of what was asked for,
+ * synchronise — on the map's stream */
+int la3dm_devmap_clusters_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                               const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info);
+/* device pointers (params->members and out's arrays already in HBM on the map's device, sum 8-byte aligned, the others
+ * 4-byte; lo3, dims3, params, n_found, stats and info stay host-side); returns when the results are complete */
+int la3dm_devmap_clusters_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                                 const la3dm_clusters_out *d_out, uint32_t *n_found, la3dm_clusters_stats *stats,
+                                 la3dm_region_info *info);
+/* Leaf export =the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),
  * state 0 = FREE leaves coloured by probability.  original_size 0 expands a collapsed leaf into the

@@ -183,6 +183,16 @@ int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3,
 int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                      const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
                      la3dm_travel_stats *stats, la3dm_region_info *info);
+/* BGKOctoMap::clusters: the connected groups of the member voxels of box's region — every voxel with a class in
+ * params->member_mask, or those of the list params->members — under params->connectivity, confined to tiles of
+ * params->tile voxels (0: untiled) and kept from params->min_size members up; numbered in ascending order of their
+ * smallest flat index.  out->label = the number per voxel, out->of_member = per list entry (LA3DM_CLUSTERS_NONE elsewhere);
+ * for the first params->cap clusters first, size, the bounding box lo / hi, the coordinate sums and rep, the member
+ * nearest the rounded centroid.  *n_found = the number of kept clusters.  Contract, limits and refusals:
+ * include/la3dm_hip.h (la3dm_devmap_clusters_host).  Device-resident maps relax bricks of the region on the device pool
+ * without a mirror refresh, host-mode maps flood-fill on the CPU; the results are identical. */
+int la3dm_map_clusters(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                       const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

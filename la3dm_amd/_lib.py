@@ -118,6 +118,19 @@ class TravelStats(C.Structure):  # la3dm_travel_stats
     _fields_ = [(k, C.c_uint32) for k in ("n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")]
 
 
+class ClustersParams(C.Structure):  # la3dm_clusters_params
+    _fields_ = [(k, C.c_uint32) for k in ("member_mask", "from_list", "connectivity", "tile", "min_size", "n_members")] + \
+               [("members", C.c_void_p), ("cap", C.c_uint32)]
+
+
+class ClustersOut(C.Structure):    # la3dm_clusters_out
+    _fields_ = [(k, C.c_void_p) for k in ("label", "of_member", "first", "size", "lo", "hi", "sum", "rep")]
+
+
+class ClustersStats(C.Structure):  # la3dm_clusters_stats
+    _fields_ = [(k, C.c_uint32) for k in ("n_members", "n_clusters", "n_dropped", "largest", "rounds", "brick_runs", "capped")]
+
+
 class RegionInfo(C.Structure):   # la3dm_region_info
     _fields_ = [("block_key", C.c_int64), ("cell", C.c_int32 * 3), ("origin", C.c_float * 3)]
 
@@ -137,7 +150,8 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_columns_host", "la3dm_devmap_columns_device", "la3dm_devmap_distance_host",
                "la3dm_devmap_distance_device", "la3dm_devmap_frontier_host", "la3dm_devmap_frontier_device",
                "la3dm_devmap_gain_host", "la3dm_devmap_gain_device", "la3dm_devmap_reach_host",
-               "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device"]
+               "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device",
+               "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device"]
 MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
                "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
                "la3dm_map_insert_training_data", "la3dm_map_prepare", "la3dm_map_prepare_training_data",
@@ -151,7 +165,7 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth",
                "la3dm_map_raycast_many", "la3dm_map_mirror_syncs", "la3dm_map_box", "la3dm_map_columns",
                "la3dm_map_distance_field", "la3dm_map_frontier", "la3dm_map_gain", "la3dm_map_reach",
-               "la3dm_map_travel"]
+               "la3dm_map_travel", "la3dm_map_clusters"]
 
 _hip = None
 _map = None
@@ -254,6 +268,11 @@ def hip():
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TravelParams), C.c_void_p, C.c_uint32,
                           C.POINTER(TravelOut), C.POINTER(TravelStats), C.POINTER(RegionInfo)]
+        for form in ("host", "device"):
+            f = getattr(L, f"la3dm_devmap_clusters_{form}")
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClustersParams), C.POINTER(ClustersOut), C.POINTER(C.c_uint32),
+                          C.POINTER(ClustersStats), C.POINTER(RegionInfo)]
         L.la3dm_devmap_training_data.restype = C.c_int
         L.la3dm_devmap_training_data.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         _hip = L
@@ -315,6 +334,9 @@ def maplib():
         M.la3dm_map_travel.restype = C.c_int
         M.la3dm_map_travel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TravelParams), C.c_void_p,
                                        C.c_uint32, C.POINTER(TravelOut), C.POINTER(TravelStats), C.POINTER(RegionInfo)]
+        M.la3dm_map_clusters.restype = C.c_int
+        M.la3dm_map_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClustersParams), C.POINTER(ClustersOut),
+                                         C.POINTER(C.c_uint32), C.POINTER(ClustersStats), C.POINTER(RegionInfo)]
         M.la3dm_map_mirror_syncs.restype = C.c_uint64
         M.la3dm_map_mirror_syncs.argtypes = [C.c_void_p]
         M.la3dm_map_raycast.restype = C.c_uint64

@@ -24,6 +24,10 @@ TRAVEL_NONE = 0xFFFFFFFF            # LA3DM_TRAVEL_NONE: travel found no walk to
 TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_SEEDS, TRAVEL_MAX_ROUNDS = 1 << 28, 1 << 31, 1 << 20, 1 << 16   # LA3DM_TRAVEL_MAX_*
 TRAVEL_MAX_MOVE = TRAVEL_MAX_PENALTY = 1 << 16
 TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH = 8, 16, 8   # LA3DM_TRAVEL_*: a brick's edge, iterations of one brick run, rounds queued between two reads of the counts
+CLUSTERS_NONE = 0xFFFFFFFF          # LA3DM_CLUSTERS_NONE: a non-member, or a member of a dropped cluster
+CLUSTERS_MAX_CELLS, CLUSTERS_MAX_MEMBERS, CLUSTERS_MAX_ROUNDS = 1 << 28, 1 << 28, 1 << 16   # LA3DM_CLUSTERS_MAX_*
+CLUSTERS_MAX_AXIS = CLUSTERS_MAX_TILE = 1 << 15
+CLUSTERS_BRICK, CLUSTERS_INNER, CLUSTERS_BATCH = 8, 16, 8   # LA3DM_CLUSTERS_*: as travel's
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
@@ -508,6 +512,58 @@ class BGKOctoMap:
         self._chk(self._M.la3dm_map_travel(self._h, lo3.ctypes.data, d3.ctypes.data, s.ctypes.data if s.size else None, s.size, C.byref(p),
                                            t.ctypes.data if nt else None, nt, C.byref(o), C.byref(stats), C.byref(info)))
         out.update({k: int(getattr(stats, k)) for k in ("n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")})
+        out.update(self._region_info(info))
+        return out
+
+    def clusters(self, lo, dims, members=None, member=("free",), connectivity=26, tile=0, min_size=1, cap=None, fields=("label",)):
+        """The connected groups of the member voxels of the region of box(lo, dims).  A member is a voxel whose class (box's
+        cls) is in `member` (names or an integer bit mask, as travel takes them) — every such voxel of the region, or with
+        `members` (flat indices, e.g. frontier's index) only the listed ones; an index out of range is ignored and a voxel
+        listed twice counts once.  Two members are adjacent under `connectivity` (6, 18 or 26) and, with tile > 0 (a multiple
+        of 8), only inside the same tile of tile^3 voxels anchored at voxel (0, 0, 0).  Clusters with fewer than min_size
+        members are dropped; the others are numbered in ascending order of `first`, their smallest flat index.  fields: any
+        of "label" (uint32 per voxel, CLUSTERS_NONE for a non-member or a dropped cluster) and "of_member" (the same per
+        entry of `members`).  cap: records wanted at most (None: every cluster; 0: count only).  Returns a dict with those
+        arrays, the records of the first min(n, cap) clusters — first, size, lo and hi [., 3] (the bounding box, inclusive),
+        sum [., 3] (uint64 sums of i, j, k: the client divides) and rep (the member nearest the rounded centroid, the
+        smallest flat index among equals) — n (the number of kept clusters), n_members, n_clusters, n_dropped, largest, the
+        device form's diagnostics rounds, brick_runs and capped (0 on a host-mode map), plus origin, block_key, cell as
+        box() returns them.  A device-resident map relaxes 8 x 8 x 8 bricks of the region on the device pool (no host mirror
+        refresh); a host-mode map flood-fills on the CPU, with identical results."""
+        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and max(d) <= CLUSTERS_MAX_AXIS and ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= CLUSTERS_MAX_CELLS else 1)(d[0] * d[1] * d[2]))
+        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - {"label", "of_member"}
+        if bad:
+            raise ValueError(f"clusters: unknown fields {sorted(bad)}")
+        if isinstance(member, str):
+            member = (member,)
+        mask = int(member) if isinstance(member, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(member))
+        lst = None if members is None else np.ascontiguousarray(members, np.uint32).reshape(-1)
+        nm = 0 if lst is None else lst.size
+        room = (nm if lst is not None else n) if cap is None else int(cap)   # (no more clusters than members)
+        words = [mask, int(connectivity), int(tile), int(min_size), nm, room]
+        if not all(0 <= v < 2 ** 32 for v in words):
+            raise ValueError("clusters: the mask, connectivity, tile, min_size, cap and the number of members must fit 32 bits")
+        p = _lib.ClustersParams(mask, 0 if lst is None else 1, words[1], words[2], words[3], nm, lst.ctypes.data if nm else None, room)
+        out = {}
+        if "label" in fields:
+            out["label"] = np.empty(shape, np.uint32)
+        if "of_member" in fields:
+            out["of_member"] = np.empty(nm, np.uint32)
+        rec = dict(first=np.empty(room, np.uint32), size=np.empty(room, np.uint32), lo=np.empty((room, 3), np.uint32),
+                   hi=np.empty((room, 3), np.uint32), sum=np.empty((room, 3), np.uint64), rep=np.empty(room, np.uint32))
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None   # noqa: E731
+        o = _lib.ClustersOut(ptr(out.get("label")), out["of_member"].ctypes.data if "of_member" in out else None,
+                             *[ptr(rec[k]) for k in ("first", "size", "lo", "hi", "sum", "rep")])
+        found, stats, info = C.c_uint32(0), _lib.ClustersStats(), _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_clusters(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(p), C.byref(o), C.byref(found), C.byref(stats),
+                                             C.byref(info)))
+        m = min(int(found.value), room)
+        out.update({k: v[:m].copy() for k, v in rec.items()})   # (the unused tail of the room is never touched)
+        out["n"] = int(found.value)
+        out.update({k: int(getattr(stats, k)) for k in ("n_members", "n_clusters", "n_dropped", "largest", "rounds", "brick_runs", "capped")})
         out.update(self._region_info(info))
         return out
 

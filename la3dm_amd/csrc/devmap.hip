@@ -32,6 +32,7 @@
 #include "devmap_gain.h"
 #include "devmap_reach.h"
 #include "devmap_travel.h"
+#include "devmap_clusters.h"
 
 using namespace la3dm_dev;
 
@@ -84,6 +85,8 @@ struct la3dm_devmap {
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
     Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
     Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
+    Arena clusters_work;          // clusters: two brick-major label buffers, side / active per brick, the round counts, sizes, flags, numbers (devmap_clusters.h)
+    Arena clusters_rec;           // clusters: the records of the clusters written (sums, keys, boxes, first, size, rep)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -679,7 +682,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->travel_work, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3283,6 +3286,202 @@ int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t 
     if (n_targets) DM_TRY(hipMemcpyAsync(h.target_cost, d.target_cost, 4ull * n_targets, hipMemcpyDeviceToHost, st));
     if (h.parent) DM_TRY(hipMemcpyAsync(h.parent, d.parent, n, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
+    if (stats) *stats = s;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+// ---- clusters: connected groups of a region's member voxels, optionally tiled (devmap_clusters.h) ----------------------
+static int clusters_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                            const la3dm_clusters_out *out, const char *who, RegionGeom &g) {
+    if (!dm) return LA3DM_ERR_ARG;
+    std::string refusal = la3dm_region::clusters_check(params, out);
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+    const int rc = region_resolve(dm, lo3, dims3, la3dm_region::kClusters, true, true, who, g);
+    if (rc != LA3DM_OK) return rc;
+    refusal = la3dm_region::clusters_region_check(dims3);
+    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+    return LA3DM_OK;
+}
+
+constexpr uint32_t kClustersCountRing = 1024;   // rounds whose counts the working storage holds before they are cleared again
+
+// The whole query on the map's stream; every pointer of p and o is device memory.  The working storage is initialised
+// here on every call.  The rounds are queued LA3DM_CLUSTERS_BATCH at a time; the counts of a batch are then read, and the
+// first round in which no voxel changed ends the loop.  n and the totals are read before the records, whose storage is
+// sized by min(n, cap).  `rec` = where the records lie in the working storage (rec.m of them) for a caller that copies
+// them itself; o's record arrays may all be null.
+static int clusters_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_clusters_params &p, const la3dm_clusters_out &o,
+                           uint32_t &n_found, la3dm_clusters_stats &stats, ClustersRec &rec) {
+    hipStream_t st = dm->ctx->stream;
+    ClustersArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nx = g.dims[0];
+    a.ny = g.dims[1];
+    a.nz = g.dims[2];
+    a.BX = cdiv(a.nx, LA3DM_CLUSTERS_BRICK);
+    a.BY = cdiv(a.ny, LA3DM_CLUSTERS_BRICK);
+    a.BZ = cdiv(a.nz, LA3DM_CLUSTERS_BRICK);
+    a.n_bricks = a.BX * a.BY * a.BZ;   // * 512 <= LA3DM_CLUSTERS_MAX_CELLS
+    a.n_cells = (uint32_t)g.total;
+    a.tb = p.tile ? p.tile / LA3DM_CLUSTERS_BRICK : kClNoTile;
+    a.min_size = p.min_size;
+    const size_t cells = (size_t)a.n_bricks * 512, per_brick = ((size_t)a.n_bricks + 3) & ~(size_t)3;
+    const size_t per_voxel = ((size_t)a.n_cells + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
+    const size_t n_small = 4 * per_brick + (size_t)kClustersCountRing * kClCountWords + 4;   // side x 2, active x 2, counts, totals
+    // layout: label 0 | label 1 | side 0 | side 1 | active 0 | active 1 | counts | totals | size | flag | number
+    DM_RESERVE(dm->clusters_work, 4ull * (2 * cells + n_small + 3 * per_voxel));
+    uint32_t *base = (uint32_t *)dm->clusters_work.ptr, *small = base + 2 * cells;
+    a.lab[0] = base;
+    a.lab[1] = base + cells;
+    a.side[0] = small;
+    a.side[1] = small + per_brick;
+    a.active[0] = small + 2 * per_brick;
+    a.active[1] = small + 3 * per_brick;
+    a.count = small + 4 * per_brick;
+    a.totals = a.count + (size_t)kClustersCountRing * kClCountWords;
+    a.size = small + n_small;
+    a.flag = a.size + per_voxel;
+    a.number = a.flag + per_voxel;
+    DM_TRY(hipMemsetAsync(small, 0, 4ull * (n_small + per_voxel), st));   // (the sizes too)
+    const uint32_t probe = dm->n_blocks == 0 ? 0u : 1u;   // an empty map: every voxel MISSING, the pool is not read
+    RegionArgs r = region_args(dm, g);
+    if (p.from_list) {
+        DM_TRY(hipMemsetAsync(a.lab[0], 0xFF, 4ull * cells, st));
+        if (p.n_members) hipLaunchKernelGGL(dm_cl_list, dim3(cdiv(p.n_members, 256)), dim3(256), 0, st, r, a, p.member_mask, probe, p.members, p.n_members);
+    } else {
+        hipLaunchKernelGGL(dm_cl_enter, dim3(a.n_bricks * 2u), dim3(256), 0, st, r, a, p.member_mask, probe);
+    }
+    DM_TRY(hipGetLastError());
+    memset(&stats, 0, sizeof(stats));
+    rec.m = 0;
+    uint32_t queued = 0;   // rounds launched: side[queued & 1] is the array the last of them wrote
+    if (!p.from_list || p.n_members) {
+        void (*round_kernel)(ClustersArgs, uint32_t, uint32_t) =
+            p.connectivity == 6 ? dm_cl_round<6> : p.connectivity == 18 ? dm_cl_round<18> : dm_cl_round<26>;
+        uint32_t h_count[LA3DM_CLUSTERS_BATCH * kClCountWords];
+        bool ended = false;
+        while (!ended) {   // at most LA3DM_CLUSTERS_MAX_ROUNDS / LA3DM_CLUSTERS_BATCH trips
+            if (queued >= LA3DM_CLUSTERS_MAX_ROUNDS)
+                return dm_fail(dm, LA3DM_ERR_LIMIT, "la3dm_devmap_clusters: no fixed point after LA3DM_CLUSTERS_MAX_ROUNDS (2^16) rounds; the outputs are unspecified");
+            const uint32_t slot = queued % kClustersCountRing;   // (a batch never straddles the ring's end: 1024 is a multiple of the batch)
+            if (slot == 0 && queued) DM_TRY(hipMemsetAsync(a.count, 0, 4ull * kClustersCountRing * kClCountWords, st));
+            for (uint32_t q = 0; q < LA3DM_CLUSTERS_BATCH; ++q)
+                hipLaunchKernelGGL(round_kernel, dim3(a.n_bricks), dim3(512), 0, st, a, (queued + q) & 1u, slot + q);
+            DM_TRY(hipGetLastError());
+            DM_TRY(hipMemcpyAsync(h_count, a.count + (size_t)slot * kClCountWords, sizeof(h_count), hipMemcpyDeviceToHost, st));
+            DM_TRY(hipStreamSynchronize(st));
+            queued += LA3DM_CLUSTERS_BATCH;
+            for (uint32_t q = 0; q < LA3DM_CLUSTERS_BATCH && !ended; ++q) {
+                const uint32_t *c = h_count + q * kClCountWords;
+                stats.brick_runs += c[1];
+                stats.capped += c[2];
+                if (c[0] == 0)
+                    ended = true;
+                else
+                    ++stats.rounds;
+            }
+        }
+    }
+    const uint32_t *side = a.side[queued & 1u];
+    hipLaunchKernelGGL(dm_cl_sizes, dim3(a.n_bricks), dim3(512), 0, st, a, side);
+    hipLaunchKernelGGL(dm_cl_flags, dim3(cdiv(a.n_cells + 1u, 256)), dim3(256), 0, st, a, side);
+    DM_TRY(hipGetLastError());
+    dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
+    int rc = exclusive_scan(dm, a.flag, a.number, a.n_cells + 1u);
+    if (rc != LA3DM_OK) return rc;
+    if (o.label) hipLaunchKernelGGL(dm_cl_label, dim3(cdiv(a.n_cells, 256)), dim3(256), 0, st, a, side, o.label);
+    if (o.of_member && p.n_members)
+        hipLaunchKernelGGL(dm_cl_gather, dim3(cdiv(p.n_members, 256)), dim3(256), 0, st, a, side, p.members, p.n_members, o.of_member);
+    DM_TRY(hipGetLastError());
+    uint32_t totals[3], n = 0;
+    DM_TRY(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(&n, a.number + a.n_cells, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    stats.n_members = totals[0];
+    stats.n_dropped = totals[1];
+    stats.largest = totals[2];
+    stats.n_clusters = n_found = n;
+    const uint32_t m = std::min(n, p.cap);
+    if (m == 0) return LA3DM_OK;
+    // layout: sum [3 m] | key [m] (64-bit words) | lo [3 m] | hi [3 m] | first | size | rep [m]
+    DM_RESERVE(dm->clusters_rec, 68ull * m);
+    rec.m = m;
+    rec.sum = (unsigned long long *)dm->clusters_rec.ptr;
+    rec.key = rec.sum + 3ull * m;
+    rec.lo = (uint32_t *)(rec.key + m);
+    rec.hi = rec.lo + 3ull * m;
+    rec.first = rec.hi + 3ull * m;
+    rec.size = rec.first + m;
+    rec.rep = rec.size + m;
+    hipLaunchKernelGGL(dm_cl_rec_init, dim3(cdiv(m, 256)), dim3(256), 0, st, rec);
+    hipLaunchKernelGGL(dm_cl_records, dim3(a.n_bricks), dim3(512), 0, st, a, side, rec);
+    hipLaunchKernelGGL(dm_cl_rep, dim3(a.n_bricks), dim3(512), 0, st, a, side, rec);
+    hipLaunchKernelGGL(dm_cl_emit, dim3(cdiv(m, 256)), dim3(256), 0, st, rec, o.first, o.size, o.lo, o.hi, (unsigned long long *)o.sum, o.rep);
+    DM_TRY(hipGetLastError());
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_clusters_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                                 const la3dm_clusters_out *d_out, uint32_t *n_found, la3dm_clusters_stats *stats,
+                                 la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = clusters_resolve(dm, lo3, dims3, params, d_out, "la3dm_devmap_clusters_device", g);
+    if (rc != LA3DM_OK) return rc;
+    la3dm_clusters_out o;
+    memset(&o, 0, sizeof(o));
+    if (d_out) o = *d_out;
+    la3dm_clusters_stats s;
+    ClustersRec rec;
+    uint32_t n = 0;
+    rc = clusters_launch(dm, g, *params, o, n, s, rec);
+    if (rc != LA3DM_OK) return rc;
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    if (n_found) *n_found = n;
+    if (stats) *stats = s;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_clusters_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                               const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    int rc = clusters_resolve(dm, lo3, dims3, params, out, "la3dm_devmap_clusters_host", g);
+    if (rc != LA3DM_OK) return rc;
+    la3dm_clusters_out h;
+    memset(&h, 0, sizeof(h));
+    if (out) h = *out;
+    hipStream_t st = dm->ctx->stream;
+    const size_t n = (size_t)g.total;
+    la3dm_clusters_params p = *params;
+    if (!p.from_list) p.n_members = 0;   // (checked, not used)
+    // the list in `cloud`; the dense label and the label per entry in `q_out`; the records are copied from the working storage
+    const size_t n_label = h.label ? n : 0, n_of = h.of_member ? p.n_members : 0;
+    DM_RESERVE(dm->cloud, 4ull * p.n_members);
+    DM_RESERVE(dm->q_out, 4ull * (n_label + n_of));
+    uint32_t *d_members = (uint32_t *)dm->cloud.ptr;
+    if (p.n_members) DM_TRY(hipMemcpyAsync(d_members, p.members, 4ull * p.n_members, hipMemcpyHostToDevice, st));
+    p.members = d_members;
+    la3dm_clusters_out d;
+    memset(&d, 0, sizeof(d));
+    d.label = h.label ? (uint32_t *)dm->q_out.ptr : nullptr;
+    d.of_member = n_of ? (uint32_t *)dm->q_out.ptr + n_label : nullptr;
+    la3dm_clusters_stats s;
+    ClustersRec rec;
+    uint32_t found = 0;
+    rc = clusters_launch(dm, g, p, d, found, s, rec);
+    if (rc != LA3DM_OK) return rc;
+    const size_t m = rec.m;
+    if (h.label) DM_TRY(hipMemcpyAsync(h.label, d.label, 4ull * n, hipMemcpyDeviceToHost, st));
+    if (n_of) DM_TRY(hipMemcpyAsync(h.of_member, d.of_member, 4ull * n_of, hipMemcpyDeviceToHost, st));
+    if (m && h.first) DM_TRY(hipMemcpyAsync(h.first, rec.first, 4ull * m, hipMemcpyDeviceToHost, st));
+    if (m && h.size) DM_TRY(hipMemcpyAsync(h.size, rec.size, 4ull * m, hipMemcpyDeviceToHost, st));
+    if (m && h.lo) DM_TRY(hipMemcpyAsync(h.lo, rec.lo, 12ull * m, hipMemcpyDeviceToHost, st));
+    if (m && h.hi) DM_TRY(hipMemcpyAsync(h.hi, rec.hi, 12ull * m, hipMemcpyDeviceToHost, st));
+    if (m && h.sum) DM_TRY(hipMemcpyAsync(h.sum, rec.sum, 24ull * m, hipMemcpyDeviceToHost, st));
+    if (m && h.rep) DM_TRY(hipMemcpyAsync(h.rep, rec.rep, 4ull * m, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (n_found) *n_found = found;
     if (stats) *stats = s;
     if (info) *info = g.info;
     return LA3DM_OK;

@@ -1231,6 +1231,137 @@ void BGKOctoMap::travel(const float *lo3, const uint32_t *dims3, const uint32_t 
     if (stats) *stats = s;
 }
 
+// ---- clusters of a region.  The host form below is the definition; the device kernels (csrc/devmap_clusters.h) reproduce
+// it bit for bit.  box's classes (and the list) give the members; a flood fill from every unlabelled member in ascending
+// flat order numbers the clusters by their smallest index; the kept ones are renumbered in that order; one pass over the
+// voxels gives the records and a second one rep, once the sums are final.
+void BGKOctoMap::clusters(const float *lo3, const uint32_t *dims3, const la3dm_clusters_params &p, const la3dm_clusters_out *out,
+                          uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_clusters_host(dmap, lo3, dims3, &p, out, n_found, stats, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::clusters: ") + la3dm_last_error(ctx));
+        return;
+    }
+    std::string refusal = la3dm_region::clusters_check(&p, out);
+    if (!refusal.empty()) throw std::invalid_argument("BGKOctoMap::clusters: " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kClusters, true, "clusters", g0, inf);
+    refusal = la3dm_region::clusters_region_check(dims3);
+    if (!refusal.empty()) throw std::invalid_argument("BGKOctoMap::clusters: " + refusal);
+    if (info) *info = inf;
+    la3dm_clusters_out o;
+    std::memset(&o, 0, sizeof(o));
+    if (out) o = *out;
+    const uint32_t nx = dims3[0], ny = dims3[1], nz = dims3[2];
+    const size_t n = (size_t)nx * ny * nz;
+    std::vector<uint8_t> cls(n);
+    la3dm_box_out bo;
+    bo.cls = cls.data();
+    bo.leaf_depth = nullptr;
+    bo.A = bo.B = nullptr;
+    box(lo3, dims3, bo, nullptr);
+    const uint32_t n_list = p.from_list ? p.n_members : 0;
+    std::vector<uint8_t> member(n, 0);
+    if (p.from_list) {
+        for (uint32_t t = 0; t < n_list; ++t)
+            if (p.members[t] < n && ((p.member_mask >> cls[p.members[t]]) & 1u)) member[p.members[t]] = 1;
+    } else {
+        for (size_t f = 0; f < n; ++f) member[f] = (p.member_mask >> cls[f]) & 1u;
+    }
+    const int far = p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3;
+    int offs[26][3], n_offs = 0;
+    for (int di = -1; di <= 1; ++di)
+        for (int dj = -1; dj <= 1; ++dj)
+            for (int dk = -1; dk <= 1; ++dk) {
+                const int s = std::abs(di) + std::abs(dj) + std::abs(dk);
+                if (s >= 1 && s <= far) offs[n_offs][0] = di, offs[n_offs][1] = dj, offs[n_offs++][2] = dk;
+            }
+    const uint32_t tile = p.tile ? p.tile : 0xFFFFFFFFu;   // (untiled: every voxel in tile 0)
+    // the flood fill: comp[f] = the cluster's number among ALL clusters, in ascending order of their smallest index
+    std::vector<uint32_t> comp(n, LA3DM_CLUSTERS_NONE), sizes, stack;
+    la3dm_clusters_stats s;
+    std::memset(&s, 0, sizeof(s));
+    for (size_t f0 = 0; f0 < n; ++f0) {
+        if (!member[f0] || comp[f0] != LA3DM_CLUSTERS_NONE) continue;
+        const uint32_t c = (uint32_t)sizes.size();
+        uint32_t count = 0;
+        comp[f0] = c;
+        stack.push_back((uint32_t)f0);
+        while (!stack.empty()) {
+            const uint32_t f = stack.back();
+            stack.pop_back();
+            ++count;
+            const uint32_t k = f % nz, j = (f / nz) % ny, i = f / (nz * ny);
+            for (int q = 0; q < n_offs; ++q) {
+                const uint32_t ui = i + (uint32_t)offs[q][0], uj = j + (uint32_t)offs[q][1], uk = k + (uint32_t)offs[q][2];   // (0 - 1 wraps above nx)
+                if (ui >= nx || uj >= ny || uk >= nz || ui / tile != i / tile || uj / tile != j / tile || uk / tile != k / tile) continue;
+                const size_t u = ((size_t)ui * ny + uj) * nz + uk;
+                if (!member[u] || comp[u] != LA3DM_CLUSTERS_NONE) continue;
+                comp[u] = c;
+                stack.push_back((uint32_t)u);
+            }
+        }
+        sizes.push_back(count);
+        s.n_members += count;
+    }
+    std::vector<uint32_t> number(sizes.size());
+    for (size_t c = 0; c < sizes.size(); ++c) {
+        const bool keep = sizes[c] >= p.min_size;
+        number[c] = keep ? s.n_clusters++ : LA3DM_CLUSTERS_NONE;
+        if (keep)
+            s.largest = std::max(s.largest, sizes[c]);
+        else
+            ++s.n_dropped;
+    }
+    const uint32_t m = std::min(s.n_clusters, p.cap);
+    std::vector<uint64_t> sum(3 * (size_t)m, 0), key(m, ~0ull);
+    std::vector<uint32_t> size_of(m, 0);
+    for (uint32_t c = 0; c < m; ++c)
+        for (int a = 0; a < 3; ++a) {
+            if (o.lo) o.lo[3 * c + a] = 0xFFFFFFFFu;
+            if (o.hi) o.hi[3 * c + a] = 0;
+        }
+    for (size_t f = 0; f < n; ++f) {
+        const uint32_t c = comp[f] == LA3DM_CLUSTERS_NONE ? LA3DM_CLUSTERS_NONE : number[comp[f]];
+        if (o.label) o.label[f] = c;
+        if (c >= m) continue;   // (NONE is no record)
+        const uint32_t v[3] = {(uint32_t)(f / ((size_t)nz * ny)), (uint32_t)((f / nz) % ny), (uint32_t)(f % nz)};
+        if (size_of[c]++ == 0 && o.first) o.first[c] = (uint32_t)f;   // ascending f: the first member seen is the smallest index
+        for (int a = 0; a < 3; ++a) {
+            sum[3 * c + a] += v[a];
+            if (o.lo) o.lo[3 * c + a] = std::min(o.lo[3 * c + a], v[a]);
+            if (o.hi) o.hi[3 * c + a] = std::max(o.hi[3 * c + a], v[a]);
+        }
+    }
+    if (o.rep)
+        for (size_t f = 0; f < n; ++f) {   // ascending f and a strict comparison: ties go to the smallest index
+            const uint32_t c = comp[f] == LA3DM_CLUSTERS_NONE ? LA3DM_CLUSTERS_NONE : number[comp[f]];
+            if (c >= m) continue;
+            const int64_t v[3] = {(int64_t)(f / ((size_t)nz * ny)), (int64_t)((f / nz) % ny), (int64_t)(f % nz)};
+            uint64_t d = 0;
+            for (int a = 0; a < 3; ++a) {
+                const int64_t ca = (int64_t)((2 * sum[3 * c + a] + size_of[c]) / (2ull * size_of[c]));
+                d += (uint64_t)((v[a] - ca) * (v[a] - ca));
+            }
+            const uint64_t cand = (d << 32) | (uint64_t)f;
+            if (cand < key[c]) key[c] = cand;
+        }
+    for (uint32_t c = 0; c < m; ++c) {
+        if (o.size) o.size[c] = size_of[c];
+        if (o.rep) o.rep[c] = (uint32_t)key[c];
+        if (o.sum)
+            for (int a = 0; a < 3; ++a) o.sum[3 * c + a] = sum[3 * c + a];
+    }
+    for (uint32_t t = 0; t < n_list && o.of_member; ++t) {
+        const uint32_t f = p.members[t];
+        o.of_member[t] = f < n && comp[f] != LA3DM_CLUSTERS_NONE ? number[comp[f]] : LA3DM_CLUSTERS_NONE;
+    }
+    if (n_found) *n_found = s.n_clusters;
+    if (stats) *stats = s;
+}
+
 // ---- gain of candidate viewpoints.  The host form below is the definition; the device kernels (csrc/devmap_gain.h)
 // reproduce it bit for bit.  Per segment the loop is raycast_many's, row for row; what is added is the mark: the row's
 // lattice position (block-key fields * lim + the cell of its node key) against the region, and one bit per voxel and

@@ -492,6 +492,16 @@ public:
     void travel(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, const la3dm_travel_params &p,
                 const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out &out, la3dm_travel_stats *stats = nullptr,
                 la3dm_region_info *info = nullptr) const;
+    /// Clusters over box's region (contract: include/la3dm_hip.h, la3dm_devmap_clusters_host): the maximal sets of members
+    /// — voxels with a class in p.member_mask, all of them or those of the list p.members — connected under p.connectivity
+    /// inside tiles of p.tile voxels (0: untiled); those with fewer than p.min_size members are dropped, the others
+    /// numbered in ascending order of their smallest flat index.  out (may be null, and so may each array) = the dense
+    /// label, the label per list entry and, for the first p.cap clusters, first, size, bounding box, coordinate sums and
+    /// rep, the member nearest the rounded centroid; *n_found = the number of kept clusters.  Bad arguments throw
+    /// std::invalid_argument.  A device-resident map relaxes bricks of the region on the device pool (no mirror
+    /// refresh); a host-mode map flood-fills box's classes: that form is the definition, and both give the same integers.
+    void clusters(const float *lo3, const uint32_t *dims3, const la3dm_clusters_params &p, const la3dm_clusters_out *out,
+                  uint32_t *n_found = nullptr, la3dm_clusters_stats *stats = nullptr, la3dm_region_info *info = nullptr) const;
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {

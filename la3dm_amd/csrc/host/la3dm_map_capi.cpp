@@ -436,6 +436,14 @@ int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3
         return 0;)
 }
 
+int la3dm_map_clusters(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                       const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info) {
+    GUARD(
+        if (params == nullptr) throw std::invalid_argument("BGKOctoMap::clusters: params is NULL");
+        m->map->clusters(lo3, dims3, *params, out, n_found, stats, info);
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);

@@ -31,6 +31,8 @@ constexpr Query kGain = {LA3DM_GAIN_MAX_CELLS, "dims: more than LA3DM_GAIN_MAX_C
 constexpr Query kReach = {LA3DM_REACH_MAX_CELLS, "dims: more than LA3DM_REACH_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
 constexpr Query kTravel = {LA3DM_TRAVEL_MAX_CELLS, "dims: more than LA3DM_TRAVEL_MAX_CELLS (2^28) voxels in the region rounded up to whole bricks", false, false, "",
                            LA3DM_TRAVEL_BRICK};
+// clusters: box's own limit here; the axis and brick limits follow the region's checks (clusters_region_check)
+constexpr Query kClusters = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, false, ""};
 
 struct Anchor {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
@@ -188,6 +190,33 @@ inline uint32_t travel_entry(const la3dm_travel_params &p, uint32_t d2) {
     if (p.clearance > 0 && d2 != LA3DM_DF_FAR && d2 <= p.clearance * p.clearance) return kTravelBlocked;
     const uint32_t s2 = p.soft_radius * p.soft_radius;
     return s2 > 0 && d2 <= s2 ? (uint32_t)((uint64_t)p.penalty * (s2 - d2) / s2) : 0u;
+}
+
+// the checks of clusters' own arguments and buffers, all before the region's; `out` may be null
+inline std::string clusters_check(const la3dm_clusters_params *p, const la3dm_clusters_out *out) {
+    if (!p) return "params is NULL";
+    if (p->member_mask == 0 || (p->member_mask & ~0x1Fu)) return "member_mask must hold at least one of the bits 0x1F and no other";
+    if (p->connectivity != 6 && p->connectivity != 18 && p->connectivity != 26) return "connectivity must be 6, 18 or 26";
+    if (p->tile % LA3DM_CLUSTERS_BRICK != 0 || p->tile > LA3DM_CLUSTERS_MAX_TILE)
+        return "tile must be 0 or a multiple of LA3DM_CLUSTERS_BRICK (8) of at most LA3DM_CLUSTERS_MAX_TILE (2^15)";
+    if (p->min_size == 0) return "min_size must be >= 1";
+    if (p->from_list > 1) return "from_list must be 0 or 1";
+    if (p->n_members > LA3DM_CLUSTERS_MAX_MEMBERS) return "n_members: more than LA3DM_CLUSTERS_MAX_MEMBERS (2^28) entries";
+    if (p->n_members > 0 && !p->members) return "members is NULL with n_members > 0";
+    if (out && out->of_member && p->from_list == 0) return "of_member is set with from_list = 0";
+    if (p->cap > 0 && !(out && (out->first || out->size || out->lo || out->hi || out->sum || out->rep)))
+        return "cap > 0 with no record array (first, size, lo, hi, sum, rep)";
+    return "";
+}
+
+// the limits of clusters that follow the region's checks
+inline std::string clusters_region_check(const uint32_t *dims) {
+    for (int k = 0; k < 3; ++k)
+        if (dims[k] > LA3DM_CLUSTERS_MAX_AXIS) return "dims: an axis longer than LA3DM_CLUSTERS_MAX_AXIS (2^15)";
+    uint64_t cells = 1;
+    for (int k = 0; k < 3; ++k) cells *= ((uint64_t)dims[k] + LA3DM_CLUSTERS_BRICK - 1) / LA3DM_CLUSTERS_BRICK * LA3DM_CLUSTERS_BRICK;   // < 2^46
+    if (cells > LA3DM_CLUSTERS_MAX_CELLS) return "dims: more than LA3DM_CLUSTERS_MAX_CELLS (2^28) voxels in the region rounded up to whole bricks";
+    return "";
 }
 
 }  // namespace la3dm_region
