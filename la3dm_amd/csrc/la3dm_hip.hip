@@ -921,6 +921,10 @@ int la3dm_bgkl_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream
         sp.bdesc = (uint4 *)ctx->l_bdesc.ptr;
         sp.nb_first = (uint32_t *)ctx->l_nb_first.ptr;
         sp.part = (float2 *)ctx->l_part.ptr;
+        // a slot whose training block holds no rows (train_off[b] == train_off[b + 1]) has no item: the replay's workgroup of
+        // that (tile, slot) leaves at once and writes no sums, while bgkl_split_apply reads every slot with nbr >= 0 — it
+        // must find (0, 0) there (kbar = 0 fails the gate), not what an earlier scan left in the arena
+        HIP_TRY(ctx, hipMemsetAsync(sp.part, 0, sizeof(float2) * 7 * kWave * (size_t)n_split, stream));
         // every item owns kLItemVals value slots (64 KB): no read-back of the hit total, no second distance pass.  The
         // scratch is sized from a device counter: bound it (a low bgkl_split_rows on a large scan asks for 10^5 items).
         const size_t vals_bytes = sizeof(float) * (size_t)n_items * kLItemVals;

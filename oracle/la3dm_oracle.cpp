@@ -1482,6 +1482,15 @@ int64_t orc_l_training_data(const float *xyz, int64_t n, const float *origin, fl
 float orc_l_seg_dist(const float *p, const float *p0, const float *p1) {
     return seg_dist_l(V3{p[0], p[1], p[2]}, V3{p0[0], p0[1], p0[2]}, V3{p1[0], p1[1], p1[2]});
 }
+// BGKLInference::predict on bare arrays: M points xs, N rows of 6 floats (segment start, end) with labels y; the sums in the
+// mode orc_set_sum_mode selects
+void orc_l_predict(float sf2, float ell, const float *xs, int M, const float *rows6, const float *y, int N, float *ybar,
+                   float *kbar) {
+    std::vector<Seg> rows((size_t)N);
+    for (int j = 0; j < N; ++j)
+        rows[j] = Seg{V3{rows6[6 * j], rows6[6 * j + 1], rows6[6 * j + 2]}, V3{rows6[6 * j + 3], rows6[6 * j + 4], rows6[6 * j + 5]}};
+    bgkl_predict(sf2, ell, xs, M, rows.data(), y, N, ybar, kbar);
+}
 // stages B..G on a prepared training set (x,y,z,label per point)
 void orc_insert_training_data(void *h, const float *xyzy, int64_t n) {
     Map *m = (Map *)h;

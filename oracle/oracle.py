@@ -127,6 +127,7 @@ def _load(name):
                                         C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
     lib.orc_l_seg_dist.restype = C.c_float
     lib.orc_l_seg_dist.argtypes = [f32p, f32p, f32p]
+    lib.orc_l_predict.argtypes = [C.c_float, C.c_float, f32p, C.c_int, f32p, f32p, C.c_int, f32p, f32p]
     lib.orc_insert_xy.argtypes = [C.c_void_p, f32p, C.c_int64]
     lib.orc_insert_training_data.argtypes = [C.c_void_p, f32p, C.c_int64]
     lib.orc_stats.argtypes = [C.c_void_p, f64p]
@@ -314,6 +315,17 @@ def l_training_data(xyz, origin, ds_resolution, free_res, max_range):
     L.orc_l_training_data(xyz, xyz.shape[0], origin, ds_resolution, free_res, max_range, xy.ctypes.data, n,
                           rays.ctypes.data, nr.value, C.byref(nr))
     return xy, rays
+
+
+def l_predict(sf2, ell, xs, rows6, y, omp=False):
+    """BGKLInference::predict (bgklinference.h:80-88) on bare arrays: (ybar, kbar) of the points xs against rows of 6 floats
+    (segment start, end; a hit is a degenerate segment) with labels y, summed in the mode of set_sum_mode"""
+    xs = np.ascontiguousarray(xs, np.float32).reshape(-1, 3)
+    rows6 = np.ascontiguousarray(rows6, np.float32).reshape(-1, 6)
+    y = np.ascontiguousarray(y, np.float32)
+    ybar, kbar = np.zeros(len(xs), np.float32), np.zeros(len(xs), np.float32)
+    lib(omp).orc_l_predict(sf2, ell, xs, len(xs), rows6, y, len(y), ybar, kbar)
+    return ybar, kbar
 
 
 GP_YAML = dict(resolution=0.1, block_depth=3, sf2=1.0, ell=1.0, noise=0.01, l=100.0, min_var=0.001, max_var=1000.0,
