@@ -725,7 +725,7 @@ int la3dm_devmap_reach_device(la3dm_devmap *dm, const float *lo3, const uint32_t
  *   An empty map (every voxel MISSING) is answered from the definition without reading the pool, as reach does.
  *   Integers throughout, and the answer is unique: the results equal the host form (BGKOctoMap::travel on a host-mode
  *     map: box's classes, the host distance transform, Dijkstra with a binary heap, then the parent pass) exactly.
- *   Device form (csrc/devmap_travel.h): min-plus relaxation to its fixed point, which is unique whatever the order of the
+ *   Device form (csrc/devmap_travel.h on csrc/devmap_brick.h): min-plus relaxation to its fixed point, which is unique whatever the order of the
  *     relaxations.  The cost lives in bricks of LA3DM_TRAVEL_BRICK^3 voxels; one workgroup relaxes one brick in LDS until
  *     nothing changes (at most LA3DM_TRAVEL_INNER iterations) before anything is written back, so a round moves the wave
  *     by a brick.  The host queues LA3DM_TRAVEL_BATCH rounds, reads that batch's counts and stops at the first round in
@@ -816,7 +816,7 @@ int la3dm_devmap_travel_device(la3dm_devmap *dm, const float *lo3, const uint32_
  *   Integers throughout, and the answer is unique: the results equal the host form (BGKOctoMap::clusters on a host-mode
  *     map: box's classes, a flood fill from every unlabelled member in ascending flat order, the records in one pass,
  *     rep in a second) exactly.
- *   Device form (csrc/devmap_clusters.h): travel's scheme with min in place of min-plus.  The label of a member starts
+ *   Device form (csrc/devmap_clusters.h on csrc/devmap_brick.h): travel's scheme with min in place of min-plus.  The label of a member starts
  *     as its own flat index; the fixed point of "take the smallest label among yourself and your adjacent members" is
  *     the cluster's `first`, whatever the order of the relaxations.  The labels live in bricks of LA3DM_CLUSTERS_BRICK^3
  *     voxels; one workgroup relaxes one brick in LDS until nothing changes (at most LA3DM_CLUSTERS_INNER iterations);

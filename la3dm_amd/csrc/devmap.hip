@@ -3128,6 +3128,74 @@ int la3dm_devmap_reach_host(la3dm_devmap *dm, const float *lo3, const uint32_t *
     return LA3DM_OK;
 }
 
+// ---- the host side of the brick scheme that travel and clusters share (devmap_brick.h) ---------------------------------
+constexpr uint32_t kBrickCountRing = 1024;   // rounds whose counts the working storage holds before they are cleared again
+static_assert(kBrickCountRing % LA3DM_TRAVEL_BATCH == 0 && kBrickCountRing % LA3DM_CLUSTERS_BATCH == 0, "a batch never straddles the ring's end");
+
+// Fills the grid of region g and lays a query's working storage out in `work`:
+//   value 0 | value 1 | `more_cells` further arrays of a word per cell | side 0 | side 1 | active 0 | active 1 | counts |
+//   totals (4 words) | `own_words` words of the query's own
+// `own` = where those last begin.  Nothing is cleared here: side .. totals are the words [b.side[0], own).
+static int brick_layout(la3dm_devmap *dm, Arena &work, const RegionGeom &g, size_t more_cells, size_t own_words, BrickGrid &b, uint32_t *&totals,
+                        uint32_t *&own) {
+    b.nx = g.dims[0];
+    b.ny = g.dims[1];
+    b.nz = g.dims[2];
+    b.BX = cdiv(b.nx, 8);
+    b.BY = cdiv(b.ny, 8);
+    b.BZ = cdiv(b.nz, 8);
+    b.n_bricks = b.BX * b.BY * b.BZ;   // * 512 <= LA3DM_TRAVEL_MAX_CELLS, LA3DM_CLUSTERS_MAX_CELLS
+    b.n_cells = (uint32_t)g.total;
+    const size_t cells = (size_t)b.n_bricks * 512, per_brick = ((size_t)b.n_bricks + 3) & ~(size_t)3;
+    const size_t n_small = 4 * per_brick + (size_t)kBrickCountRing * kBrickCountWords + 4;
+    DM_RESERVE(work, 4ull * ((2 + more_cells) * cells + n_small + own_words));
+    uint32_t *base = (uint32_t *)work.ptr, *small = base + (2 + more_cells) * cells;
+    b.val[0] = base;
+    b.val[1] = base + cells;
+    b.side[0] = small;
+    b.side[1] = small + per_brick;
+    b.active[0] = small + 2 * per_brick;
+    b.active[1] = small + 3 * per_brick;
+    b.count = small + 4 * per_brick;
+    totals = b.count + (size_t)kBrickCountRing * kBrickCountWords;
+    own = small + n_small;
+    return LA3DM_OK;
+}
+
+// The rounds of a query on the map's stream, kBatch at a time: launch(turn, slot) queues one round kernel.  The counts of
+// a batch are then read, and the first round in which no voxel changed ends the loop (the rounds queued behind it found
+// every brick inactive and only copied `side`).  `queued` = rounds launched: side[queued & 1] is the array the last of
+// them wrote.  Ends in a synchronise.
+extern "C++" {   // (a template, inside the C ABI's block)
+template <uint32_t kBatch, class Launch>
+static int brick_rounds(la3dm_devmap *dm, const BrickGrid &b, Launch launch, uint32_t max_rounds, const char *limit_text, uint32_t &queued,
+                        uint32_t &rounds, uint32_t &brick_runs, uint32_t &capped) {
+    hipStream_t st = dm->ctx->stream;
+    uint32_t h_count[kBatch * kBrickCountWords];
+    bool ended = false;
+    while (!ended) {   // at most max_rounds / kBatch trips
+        if (queued >= max_rounds) return dm_fail(dm, LA3DM_ERR_LIMIT, limit_text);
+        const uint32_t slot = queued % kBrickCountRing;
+        if (slot == 0 && queued) DM_TRY(hipMemsetAsync(b.count, 0, 4ull * kBrickCountRing * kBrickCountWords, st));
+        for (uint32_t q = 0; q < kBatch; ++q) launch((queued + q) & 1u, slot + q);
+        DM_TRY(hipGetLastError());
+        DM_TRY(hipMemcpyAsync(h_count, b.count + (size_t)slot * kBrickCountWords, sizeof(h_count), hipMemcpyDeviceToHost, st));
+        DM_TRY(hipStreamSynchronize(st));
+        queued += kBatch;
+        for (uint32_t q = 0; q < kBatch && !ended; ++q) {
+            const uint32_t *c = h_count + q * kBrickCountWords;
+            brick_runs += c[1];
+            capped += c[2];
+            if (c[0] == 0)
+                ended = true;
+            else
+                ++rounds;
+        }
+    }
+    return LA3DM_OK;
+}
+}  // extern "C++"
+
 // ---- travel: least path cost from seeds through the passable voxels of a region, with parents (devmap_travel.h) -------
 static int travel_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                           const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
@@ -3139,98 +3207,60 @@ static int travel_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *di
     return region_resolve(dm, lo3, dims3, la3dm_region::kTravel, true, true, who, g);
 }
 
-constexpr uint32_t kTravelCountRing = 1024;   // rounds whose counts the working storage holds before they are cleared again
-
 // The whole query on the map's stream; every pointer but `stats` is device memory.  The working storage is initialised
-// here on every call.  The rounds are queued LA3DM_TRAVEL_BATCH at a time; the counts of a batch are then read, and the
-// first round in which no voxel changed ends the loop (the rounds queued behind it found every brick inactive and only
-// copied `side`).  o.cost and o.parent may be null: dm_tv_finish then only accumulates the totals.
+// here on every call.  The rounds are queued LA3DM_TRAVEL_BATCH at a time (brick_rounds).  o.cost and o.parent may be
+// null: dm_tv_finish then only accumulates the totals.
 static int travel_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d_seeds, uint32_t n_seeds, const la3dm_travel_params &p,
                          const uint32_t *d_targets, uint32_t n_targets, const la3dm_travel_out &o, la3dm_travel_stats &stats) {
     hipStream_t st = dm->ctx->stream;
     const size_t n = (size_t)g.total;
     TravelArgs a;
     memset(&a, 0, sizeof(a));
-    a.nx = g.dims[0];
-    a.ny = g.dims[1];
-    a.nz = g.dims[2];
-    a.BX = cdiv(a.nx, LA3DM_TRAVEL_BRICK);
-    a.BY = cdiv(a.ny, LA3DM_TRAVEL_BRICK);
-    a.BZ = cdiv(a.nz, LA3DM_TRAVEL_BRICK);
-    a.n_bricks = a.BX * a.BY * a.BZ;   // * 512 <= LA3DM_TRAVEL_MAX_CELLS
-    a.n_cells = (uint32_t)n;
     for (int k = 0; k < 3; ++k) a.move[k] = p.move_cost[k];
     a.max_cost = p.max_cost;
-    const size_t cells = (size_t)a.n_bricks * 512, per_brick = ((size_t)a.n_bricks + 3) & ~(size_t)3;
-    const size_t n_small = 4 * per_brick + (size_t)kTravelCountRing * kTvCountWords + 4;   // side x 2, active x 2, counts, totals
     const uint32_t R = std::max(p.clearance, p.soft_radius);
     const bool empty = dm->n_blocks == 0;   // every voxel MISSING: the pool is not read
     const bool transform = R > 0 && !empty;
-    // layout: cost 0 | cost 1 | E | side 0 | side 1 | active 0 | active 1 | counts | totals | d2
-    DM_RESERVE(dm->travel_work, 4ull * (3 * cells + n_small + (transform ? n : 0)));
-    uint32_t *base = (uint32_t *)dm->travel_work.ptr, *small = base + 3 * cells;
-    a.cost[0] = base;
-    a.cost[1] = base + cells;
-    a.E = base + 2 * cells;
-    a.side[0] = small;
-    a.side[1] = small + per_brick;
-    a.active[0] = small + 2 * per_brick;
-    a.active[1] = small + 3 * per_brick;
-    a.count = small + 4 * per_brick;
-    a.totals = a.count + (size_t)kTravelCountRing * kTvCountWords;
+    // layout: cost 0 | cost 1 | E | side .. totals | d2
+    uint32_t *own;
+    int rc = brick_layout(dm, dm->travel_work, g, 1, transform ? n : 0, a.g, a.totals, own);
+    if (rc != LA3DM_OK) return rc;
+    a.E = a.g.val[1] + (size_t)a.g.n_bricks * 512;
     const uint32_t *d2 = nullptr;
     uint32_t d2_fill = LA3DM_DF_FAR;
     if (transform) {
         DM_RESERVE(dm->df_work, 4ull * n);
         la3dm_distance_out dd;
-        dd.d2 = small + n_small;
+        dd.d2 = own;
         dd.dist = nullptr;
         distance_launch(dm, g, p.obstacle_mask, R, dm->df_work.ptr, dd);
         d2 = dd.d2;
     } else if (R > 0 && ((p.obstacle_mask >> LA3DM_RAY_MISSING) & 1u)) {
         d2_fill = 0u;   // (the empty map with MISSING as an obstacle: every voxel is one)
     }
-    DM_TRY(hipMemsetAsync(small, 0, 4ull * n_small, st));
+    DM_TRY(hipMemsetAsync(a.g.side[0], 0, 4ull * (own - a.g.side[0]), st));
     RegionArgs r = region_args(dm, g);
-    hipLaunchKernelGGL(dm_tv_enter, dim3(a.n_bricks * 2u), dim3(256), 0, st, r, a, p.pass_mask, empty ? 0u : 1u, d2, d2_fill, p.clearance,
+    hipLaunchKernelGGL(dm_tv_enter, dim3(a.g.n_bricks * 2u), dim3(256), 0, st, r, a, p.pass_mask, empty ? 0u : 1u, d2, d2_fill, p.clearance,
                        p.soft_radius * p.soft_radius, p.penalty);
     DM_TRY(hipGetLastError());
     memset(&stats, 0, sizeof(stats));
-    uint32_t queued = 0;   // rounds launched: side[queued & 1] is the array the last of them wrote
+    uint32_t queued = 0;
     if (n_seeds) {
         hipLaunchKernelGGL(dm_tv_seed, dim3(cdiv(n_seeds, 256)), dim3(256), 0, st, a, d_seeds, n_seeds,
                            p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3);
         DM_TRY(hipGetLastError());
         void (*round_kernel)(TravelArgs, uint32_t, uint32_t) =
             p.connectivity == 6 ? dm_tv_round<6> : p.connectivity == 18 ? dm_tv_round<18> : dm_tv_round<26>;
-        uint32_t h_count[LA3DM_TRAVEL_BATCH * kTvCountWords];
-        bool ended = false;
-        while (!ended) {   // at most LA3DM_TRAVEL_MAX_ROUNDS / LA3DM_TRAVEL_BATCH trips
-            if (queued >= LA3DM_TRAVEL_MAX_ROUNDS)
-                return dm_fail(dm, LA3DM_ERR_LIMIT, "la3dm_devmap_travel: no fixed point after LA3DM_TRAVEL_MAX_ROUNDS (2^16) rounds; the outputs are unspecified");
-            const uint32_t slot = queued % kTravelCountRing;   // (a batch never straddles the ring's end: 1024 is a multiple of the batch)
-            if (slot == 0 && queued) DM_TRY(hipMemsetAsync(a.count, 0, 4ull * kTravelCountRing * kTvCountWords, st));
-            for (uint32_t q = 0; q < LA3DM_TRAVEL_BATCH; ++q)
-                hipLaunchKernelGGL(round_kernel, dim3(a.n_bricks), dim3(512), 0, st, a, (queued + q) & 1u, slot + q);
-            DM_TRY(hipGetLastError());
-            DM_TRY(hipMemcpyAsync(h_count, a.count + (size_t)slot * kTvCountWords, sizeof(h_count), hipMemcpyDeviceToHost, st));
-            DM_TRY(hipStreamSynchronize(st));
-            queued += LA3DM_TRAVEL_BATCH;
-            for (uint32_t q = 0; q < LA3DM_TRAVEL_BATCH && !ended; ++q) {
-                const uint32_t *c = h_count + q * kTvCountWords;
-                stats.brick_runs += c[1];
-                stats.capped += c[2];
-                if (c[0] == 0)
-                    ended = true;
-                else
-                    ++stats.rounds;
-            }
-        }
+        rc = brick_rounds<LA3DM_TRAVEL_BATCH>(
+            dm, a.g, [&](uint32_t turn, uint32_t slot) { hipLaunchKernelGGL(round_kernel, dim3(a.g.n_bricks), dim3(512), 0, st, a, turn, slot); },
+            LA3DM_TRAVEL_MAX_ROUNDS, "la3dm_devmap_travel: no fixed point after LA3DM_TRAVEL_MAX_ROUNDS (2^16) rounds; the outputs are unspecified",
+            queued, stats.rounds, stats.brick_runs, stats.capped);
+        if (rc != LA3DM_OK) return rc;
     }
-    const uint32_t *side = a.side[queued & 1u];
+    const uint32_t *side = a.g.side[queued & 1u];
     void (*finish_kernel)(TravelArgs, const uint32_t *, uint32_t *, uint8_t *) =
         p.connectivity == 6 ? dm_tv_finish<6> : p.connectivity == 18 ? dm_tv_finish<18> : dm_tv_finish<26>;
-    hipLaunchKernelGGL(finish_kernel, dim3(cdiv(a.n_cells, 256)), dim3(256), 0, st, a, side, o.cost, o.parent);
+    hipLaunchKernelGGL(finish_kernel, dim3(cdiv(a.g.n_cells, 256)), dim3(256), 0, st, a, side, o.cost, o.parent);
     DM_TRY(hipGetLastError());
     if (n_targets) {
         hipLaunchKernelGGL(dm_tv_gather, dim3(cdiv(n_targets, 256)), dim3(256), 0, st, a, side, d_targets, n_targets, o.target_cost);
@@ -3304,11 +3334,9 @@ static int clusters_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *
     return LA3DM_OK;
 }
 
-constexpr uint32_t kClustersCountRing = 1024;   // rounds whose counts the working storage holds before they are cleared again
-
 // The whole query on the map's stream; every pointer of p and o is device memory.  The working storage is initialised
-// here on every call.  The rounds are queued LA3DM_CLUSTERS_BATCH at a time; the counts of a batch are then read, and the
-// first round in which no voxel changed ends the loop.  n and the totals are read before the records, whose storage is
+// here on every call.  The rounds are queued LA3DM_CLUSTERS_BATCH at a time (brick_rounds).  n and the totals are read
+// before the records, whose storage is
 // sized by min(n, cap).  `rec` = where the records lie in the working storage (rec.m of them) for a caller that copies
 // them itself; o's record arrays may all be null.
 static int clusters_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_clusters_params &p, const la3dm_clusters_out &o,
@@ -3316,87 +3344,51 @@ static int clusters_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_cl
     hipStream_t st = dm->ctx->stream;
     ClustersArgs a;
     memset(&a, 0, sizeof(a));
-    a.nx = g.dims[0];
-    a.ny = g.dims[1];
-    a.nz = g.dims[2];
-    a.BX = cdiv(a.nx, LA3DM_CLUSTERS_BRICK);
-    a.BY = cdiv(a.ny, LA3DM_CLUSTERS_BRICK);
-    a.BZ = cdiv(a.nz, LA3DM_CLUSTERS_BRICK);
-    a.n_bricks = a.BX * a.BY * a.BZ;   // * 512 <= LA3DM_CLUSTERS_MAX_CELLS
-    a.n_cells = (uint32_t)g.total;
     a.tb = p.tile ? p.tile / LA3DM_CLUSTERS_BRICK : kClNoTile;
     a.min_size = p.min_size;
-    const size_t cells = (size_t)a.n_bricks * 512, per_brick = ((size_t)a.n_bricks + 3) & ~(size_t)3;
-    const size_t per_voxel = ((size_t)a.n_cells + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
-    const size_t n_small = 4 * per_brick + (size_t)kClustersCountRing * kClCountWords + 4;   // side x 2, active x 2, counts, totals
-    // layout: label 0 | label 1 | side 0 | side 1 | active 0 | active 1 | counts | totals | size | flag | number
-    DM_RESERVE(dm->clusters_work, 4ull * (2 * cells + n_small + 3 * per_voxel));
-    uint32_t *base = (uint32_t *)dm->clusters_work.ptr, *small = base + 2 * cells;
-    a.lab[0] = base;
-    a.lab[1] = base + cells;
-    a.side[0] = small;
-    a.side[1] = small + per_brick;
-    a.active[0] = small + 2 * per_brick;
-    a.active[1] = small + 3 * per_brick;
-    a.count = small + 4 * per_brick;
-    a.totals = a.count + (size_t)kClustersCountRing * kClCountWords;
-    a.size = small + n_small;
+    const size_t per_voxel = ((size_t)g.total + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
+    // layout: label 0 | label 1 | side .. totals | size | flag | number
+    int rc = brick_layout(dm, dm->clusters_work, g, 0, 3 * per_voxel, a.g, a.totals, a.size);
+    if (rc != LA3DM_OK) return rc;
     a.flag = a.size + per_voxel;
     a.number = a.flag + per_voxel;
-    DM_TRY(hipMemsetAsync(small, 0, 4ull * (n_small + per_voxel), st));   // (the sizes too)
+    const uint32_t n_bricks = a.g.n_bricks, n_cells = a.g.n_cells;
+    DM_TRY(hipMemsetAsync(a.g.side[0], 0, 4ull * (a.flag - a.g.side[0]), st));   // (the sizes too)
     const uint32_t probe = dm->n_blocks == 0 ? 0u : 1u;   // an empty map: every voxel MISSING, the pool is not read
     RegionArgs r = region_args(dm, g);
     if (p.from_list) {
-        DM_TRY(hipMemsetAsync(a.lab[0], 0xFF, 4ull * cells, st));
+        DM_TRY(hipMemsetAsync(a.g.val[0], 0xFF, 4ull * n_bricks * 512, st));
         if (p.n_members) hipLaunchKernelGGL(dm_cl_list, dim3(cdiv(p.n_members, 256)), dim3(256), 0, st, r, a, p.member_mask, probe, p.members, p.n_members);
     } else {
-        hipLaunchKernelGGL(dm_cl_enter, dim3(a.n_bricks * 2u), dim3(256), 0, st, r, a, p.member_mask, probe);
+        hipLaunchKernelGGL(dm_cl_enter, dim3(n_bricks * 2u), dim3(256), 0, st, r, a, p.member_mask, probe);
     }
     DM_TRY(hipGetLastError());
     memset(&stats, 0, sizeof(stats));
     rec.m = 0;
-    uint32_t queued = 0;   // rounds launched: side[queued & 1] is the array the last of them wrote
+    uint32_t queued = 0;
     if (!p.from_list || p.n_members) {
         void (*round_kernel)(ClustersArgs, uint32_t, uint32_t) =
             p.connectivity == 6 ? dm_cl_round<6> : p.connectivity == 18 ? dm_cl_round<18> : dm_cl_round<26>;
-        uint32_t h_count[LA3DM_CLUSTERS_BATCH * kClCountWords];
-        bool ended = false;
-        while (!ended) {   // at most LA3DM_CLUSTERS_MAX_ROUNDS / LA3DM_CLUSTERS_BATCH trips
-            if (queued >= LA3DM_CLUSTERS_MAX_ROUNDS)
-                return dm_fail(dm, LA3DM_ERR_LIMIT, "la3dm_devmap_clusters: no fixed point after LA3DM_CLUSTERS_MAX_ROUNDS (2^16) rounds; the outputs are unspecified");
-            const uint32_t slot = queued % kClustersCountRing;   // (a batch never straddles the ring's end: 1024 is a multiple of the batch)
-            if (slot == 0 && queued) DM_TRY(hipMemsetAsync(a.count, 0, 4ull * kClustersCountRing * kClCountWords, st));
-            for (uint32_t q = 0; q < LA3DM_CLUSTERS_BATCH; ++q)
-                hipLaunchKernelGGL(round_kernel, dim3(a.n_bricks), dim3(512), 0, st, a, (queued + q) & 1u, slot + q);
-            DM_TRY(hipGetLastError());
-            DM_TRY(hipMemcpyAsync(h_count, a.count + (size_t)slot * kClCountWords, sizeof(h_count), hipMemcpyDeviceToHost, st));
-            DM_TRY(hipStreamSynchronize(st));
-            queued += LA3DM_CLUSTERS_BATCH;
-            for (uint32_t q = 0; q < LA3DM_CLUSTERS_BATCH && !ended; ++q) {
-                const uint32_t *c = h_count + q * kClCountWords;
-                stats.brick_runs += c[1];
-                stats.capped += c[2];
-                if (c[0] == 0)
-                    ended = true;
-                else
-                    ++stats.rounds;
-            }
-        }
+        rc = brick_rounds<LA3DM_CLUSTERS_BATCH>(
+            dm, a.g, [&](uint32_t turn, uint32_t slot) { hipLaunchKernelGGL(round_kernel, dim3(n_bricks), dim3(512), 0, st, a, turn, slot); },
+            LA3DM_CLUSTERS_MAX_ROUNDS, "la3dm_devmap_clusters: no fixed point after LA3DM_CLUSTERS_MAX_ROUNDS (2^16) rounds; the outputs are unspecified",
+            queued, stats.rounds, stats.brick_runs, stats.capped);
+        if (rc != LA3DM_OK) return rc;
     }
-    const uint32_t *side = a.side[queued & 1u];
-    hipLaunchKernelGGL(dm_cl_sizes, dim3(a.n_bricks), dim3(512), 0, st, a, side);
-    hipLaunchKernelGGL(dm_cl_flags, dim3(cdiv(a.n_cells + 1u, 256)), dim3(256), 0, st, a, side);
+    const uint32_t *side = a.g.side[queued & 1u];
+    hipLaunchKernelGGL(dm_cl_sizes, dim3(n_bricks), dim3(512), 0, st, a, side);
+    hipLaunchKernelGGL(dm_cl_flags, dim3(cdiv(n_cells + 1u, 256)), dim3(256), 0, st, a, side);
     DM_TRY(hipGetLastError());
     dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
-    int rc = exclusive_scan(dm, a.flag, a.number, a.n_cells + 1u);
+    rc = exclusive_scan(dm, a.flag, a.number, n_cells + 1u);
     if (rc != LA3DM_OK) return rc;
-    if (o.label) hipLaunchKernelGGL(dm_cl_label, dim3(cdiv(a.n_cells, 256)), dim3(256), 0, st, a, side, o.label);
+    if (o.label) hipLaunchKernelGGL(dm_cl_label, dim3(cdiv(n_cells, 256)), dim3(256), 0, st, a, side, o.label);
     if (o.of_member && p.n_members)
         hipLaunchKernelGGL(dm_cl_gather, dim3(cdiv(p.n_members, 256)), dim3(256), 0, st, a, side, p.members, p.n_members, o.of_member);
     DM_TRY(hipGetLastError());
     uint32_t totals[3], n = 0;
     DM_TRY(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(&n, a.number + a.n_cells, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(&n, a.number + n_cells, 4, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
     stats.n_members = totals[0];
     stats.n_dropped = totals[1];
@@ -3415,8 +3407,8 @@ static int clusters_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_cl
     rec.size = rec.first + m;
     rec.rep = rec.size + m;
     hipLaunchKernelGGL(dm_cl_rec_init, dim3(cdiv(m, 256)), dim3(256), 0, st, rec);
-    hipLaunchKernelGGL(dm_cl_records, dim3(a.n_bricks), dim3(512), 0, st, a, side, rec);
-    hipLaunchKernelGGL(dm_cl_rep, dim3(a.n_bricks), dim3(512), 0, st, a, side, rec);
+    hipLaunchKernelGGL(dm_cl_records, dim3(n_bricks), dim3(512), 0, st, a, side, rec);
+    hipLaunchKernelGGL(dm_cl_rep, dim3(n_bricks), dim3(512), 0, st, a, side, rec);
     hipLaunchKernelGGL(dm_cl_emit, dim3(cdiv(m, 256)), dim3(256), 0, st, rec, o.first, o.size, o.lo, o.hi, (unsigned long long *)o.sum, o.rep);
     DM_TRY(hipGetLastError());
     return LA3DM_OK;

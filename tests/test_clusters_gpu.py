@@ -218,6 +218,54 @@ def test_hand_built_sets(built):
         H.la3dm_devmap_destroy(dm)
 
 
+def test_batch_boundaries(built):
+    """Lines of 8 B k + {-1, 0, 1, 2} voxels, k = 1, 2, B = LA3DM_CLUSTERS_BATCH, along each axis, every voxel a member, at
+    connectivity 6 and untiled, on the empty map and 100 m from the scans of a non-empty one (the probes run): the smallest
+    label crosses one brick per round, so the query ends before, on and after the end of a batch of rounds.  One cluster;
+    the outputs against the yardstick; rounds, brick runs and capped runs as the helper's model counts them"""
+    import la3dm_amd
+    md, _ = _bgk_pair()
+    empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=0)
+    assert md.leaves()["A"].size > 0 and empty.is_device_resident()
+    B = la3dm_amd.CLUSTERS_BATCH
+    assert B == K.BATCH and la3dm_amd.CLUSTERS_BRICK == K.BRICK and la3dm_amd.CLUSTERS_INNER == K.INNER
+    far = RC.far_lo(md, R.recipe_lo())
+    assert (md.box(far, (3, 3, 16 * B + 2), fields=())["cls"] == R.MISSING).all()
+    syncs = md.mirror_syncs()
+    rounds_seen = set()
+    for length in [8 * B * k + d for k in (1, 2) for d in (-1, 0, 1, 2)]:
+        for axis in range(3):
+            dims = [1, 1, 1]
+            dims[axis] = length
+            cls = np.full(dims, R.MISSING, np.uint8)
+            want = K.yardstick(cls, K.MISS_M, None, 6)
+            model = K.brick_model(np.ones(dims, bool), 6)
+            assert model["capped"] == 0
+            for m, lo in ((empty, np.array((0.05, 0.05, 0.05), np.float32)), (md, far)):
+                got = m.clusters(lo, dims, member=K.MISS_M, connectivity=6)
+                assert got["n"] == 1 and (got["label"] == 0).all() and got["size"][0] == length, (dims, m is md)
+                K.assert_same(got, want, (dims, m is md))
+                assert tuple(got[k] for k in K.DIAG) == tuple(model[k] for k in K.DIAG), (dims, m is md, [got[k] for k in K.DIAG], model)
+                rounds_seen.add(got["rounds"])
+    assert {B, B + 1, 2 * B, 2 * B + 1} <= rounds_seen, rounds_seen
+    assert md.mirror_syncs() == syncs and empty.mirror_syncs() == 0
+
+
+def test_count_ring_wrap(built):
+    """A line of 8 * 1024 + 9 members on the empty map: the smallest label crosses one brick per round, so the query runs
+    past round 1024, where the ring of per-round counts in the working storage is cleared and used again.  The brick runs
+    are a recorded figure: the helper's model (K.brick_model on this line, connectivity 6, untiled) gave rounds 1026, brick
+    runs 528901, capped 0 — it takes about a minute on the CPU, so it is not run here"""
+    import la3dm_amd
+    empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=0)
+    dims = (1, 1, 8 * 1024 + 9)
+    g = empty.clusters(np.array((0.05, 0.05, 0.05), np.float32), dims, member=K.MISS_M, connectivity=6)
+    print(f"ring wrap: device {[g[k] for k in K.DIAG]}")
+    assert g["n"] == 1 and (g["label"] == 0).all() and g["size"][0] == dims[2] and g["n_members"] == dims[2]
+    assert tuple(g[k] for k in K.DIAG) == (1026, 528901, 0)
+    assert empty.is_device_resident() and empty.mirror_syncs() == 0
+
+
 @pytest.mark.parametrize("variant", ["GPOctoMap", "BGKLOctoMap", "BGKLVOctoMap"])
 def test_device_equals_host_on_other_variants(built, variant):
     """GPU test 4: GP, BGK-L and BGK-LV on their own configurations: the frontier's list at tile 8 and the FREE voxels

@@ -207,6 +207,24 @@ def test_batch_boundaries(built):
     _compare(md, mh, lo, (1, 8 * B + 2, 1), [0], "far line", passable=T.MISS_M)
 
 
+def test_count_ring_wrap(built):
+    """A line of 8 * 1024 + 9 voxels on the empty map: the wave crosses one brick per round, so the query runs past round
+    1024, where the ring of per-round counts in the working storage is cleared and used again; cost = 10 k, parents towards
+    the seed; rounds, brick runs and capped runs as the helper's model counts them"""
+    import la3dm_amd
+    empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=0)
+    dims = (1, 1, 8 * 1024 + 9)
+    g = empty.travel(np.array((0.05, 0.05, 0.05), np.float32), dims, [0], passable=T.MISS_M, connectivity=6, move_cost=(10, 14, 17), fields=FIELDS)
+    k = np.arange(dims[2])
+    assert (g["cost"].reshape(-1) == 10 * k).all()
+    assert (g["parent"].reshape(-1) == np.where(k == 0, 13, 12)).all()
+    assert g["n_reached"] == dims[2] and g["max_cost"] == 10 * (dims[2] - 1)
+    model = T.brick_model(np.ones(dims, bool), np.zeros(dims, np.int64), [0], 6, (10, 14, 17))
+    print(f"ring wrap: device {[g[d] for d in DIAG]}, the model {[model[d] for d in DIAG]}")
+    assert tuple(g[d] for d in DIAG) == (1026, 2051, 0) == tuple(model[d] for d in DIAG)
+    assert empty.is_device_resident() and empty.mirror_syncs() == 0
+
+
 @pytest.mark.parametrize("variant", ["GPOctoMap", "BGKLOctoMap", "BGKLVOctoMap"])
 def test_device_equals_host_on_other_variants(built, variant):
     """GPU test 4: GP, BGK-L and BGK-LV on their own configurations; the host form == the yardstick over its own box; on
