@@ -106,7 +106,11 @@ typedef struct la3dm_params {
  *  - leaf_key[l] = (depth << 16) + index  (OcTreeHashKey, bgkoctree.cpp:9-11).
  *  - alpha/beta are in/out (m_A, m_B); state is out (see LA3DM_LEAF_UPDATED).
  * A test block must appear at most once per call (the caller runs repeated keys as
- * separate calls, preserving the reference's serial semantics). */
+ * separate calls, preserving the reference's serial semantics).
+ * A training point at no finite distance (a NaN coordinate, a coordinate so large that the squared distance
+ * overflows) makes ybar / kbar of its training block NaN at every leaf, as in the reference: a gated scan rejects that
+ * neighbour's update (bgk_sum 0) or, with one sum over all seven neighbours, the leaf's only update (bgk_sum 1); an ungated
+ * scan leaves alpha = beta = NaN. */
 typedef struct la3dm_bgk_scan {
     const float *train_xyzy;   /* [n_train_pts * 4] */
     const uint32_t *train_off; /* [n_train_blk + 1] */

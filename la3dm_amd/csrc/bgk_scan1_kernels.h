@@ -10,7 +10,9 @@
 // bgk_predict_fuse_t and deletes this header.  Until then: a change to the table path of one kernel belongs in the other too.
 //
 // Everything else — device functions, the LA3DM_TP_* macros, WaveLdsT, the ablation flags — is bgk_kernels.h's, used
-// from here (include this header after it).  Same pairs, same fp32 terms in the same order: alpha, beta and state are
+// from here (include this header after it).  One difference in the table path: this kernel notes a training point at no
+// finite distance while it stages it and answers as the reference does (NaN sums); the two-launch kernels get the same
+// answer from bgk_poison_nbr (la3dm_hip.hip), which edits the neighbour table ahead of them.  Same pairs, same fp32 terms in the same order: alpha, beta and state are
 // bit-identical to the two-launch path (tests/test_bgk_one_launch_gpu.py).
 #pragma once
 #include "bgk_kernels.h"
@@ -176,6 +178,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         __builtin_amdgcn_wave_barrier();
     };
 
+    unsigned long long nonfinite = 0ull;  // lanes whose point, in some chunk, lay at no finite distance (wave-uniform)
     // A + B for one chunk of 64 training points (lane = point)
     auto chunk = [&](const float4 &pu, const uint32_t cb) {
         // x / ell, y / ell, z / ell as bgk_prepare's IEEE divisions leave them (div_by_ell is the correctly rounded quotient;
@@ -189,7 +192,11 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         const float mz = fminf(fminf(z01.x, z01.y), fminf(z23.x, z23.y));
         // min over the 64 leaves of d2 (+ and * are monotone): staged iff some leaf hits (lanes past the end hold a
         // copy of the last point: masked)
-        const bool keep = mx + (my + mz) < hit_t && cb + lane < M;
+        const float md = mx + (my + mz);
+        const bool keep = md < hit_t && cb + lane < M;
+        // a point at no finite distance (a NaN coordinate, an overflowing square): the reference's kernel matrix holds NaN in
+        // its column, the sums of every leaf are NaN and `kbar > 0` rejects the update (see bgk_poison_nbr in la3dm_hip.hip)
+        nonfinite |= __ballot(!(md < __builtin_inff()) && cb + lane < M);
         const unsigned long long m = __ballot(keep);
         if (m == 0ull) return;
         const float sg = 1.0f - (pu.w + pu.w);  // label 0 -> +1, label 1 -> -1 (exact)
@@ -257,7 +264,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) v
 
     {
         const double s0 = L.acc0[lane], s1 = L.acc1[lane];
-        const double K = s0 + s1, Y = s1;
+        double K = s0 + s1, Y = s1;
+        if (nonfinite != 0ull) K = Y = __builtin_nan("");  // (gated: K > 0 is false, the leaf is left alone; ungated: alpha = beta = NaN)
         uint32_t lw = li;
         asm volatile("" : "+v"(lw));
         if (K > 0.0 || (a.flags & 1u) != 0u) {  // flag 1: insert_training_data, update() runs unconditionally

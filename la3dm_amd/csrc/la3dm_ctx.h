@@ -50,6 +50,7 @@ struct la3dm_ctx {
     size_t ev_used = 0;
     // scratch (device-pointer path)
     Arena pts_scaled, nbr_range, blk_desc, label_seq;
+    Arena nbr_finite, blk_poison;  // la3dm_bgk_scan_device, two launches: the neighbour table without neighbours that hold a point at no finite distance; one flag per test block
     uint32_t scan_seq = 0;  // la3dm_bgk_scan_device calls so far (BgkArgs::seq)
     Arena gp_loff, gp_totals, gp_order, gp_L, gp_alpha, gp_v;
     Arena l_task_item, l_split_list, l_nb_first, l_part, l_counters, l_item_desc, l_rowrec, l_batch_off, l_item_hits, l_bdesc, l_vals, l_rowx, l_dense, l_labmask, l_part64;

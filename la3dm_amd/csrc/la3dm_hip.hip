@@ -27,6 +27,77 @@ using namespace la3dm_dev;
 
 static thread_local std::string g_create_error;
 
+// LA3DM_SCAN_UPDATE_UNGATED: insert_training_data calls update() once per neighbour that HAS a model
+// (src/bgkoctomap/bgkoctomap.cpp:168-181), so a test block none of whose seven neighbours holds a training point is not
+// touched.  bgk_predict_fuse_v5 marks every leaf of an ungated scan as updated (alpha and beta + 0 there: unchanged); this
+// pass, behind it on the same stream and only for ungated scans of the ordered mode (bgk_sum 0, the mode that is bit-identical
+// to the reference's order), takes the mark back for those blocks.  One workgroup per test block.  bgk_sum 1 keeps the
+// restatement's sum mode 1: ONE update per leaf of an ungated scan, wherever the block stands (oracle/la3dm_oracle.cpp,
+// tests/test_bgk_one_launch_gpu.py::test_ungated_update).  (The pass lives here and not in bgk_kernels.h: that header belongs
+// to the source closure the counter files under profiles/ are stamped with.)
+// blk_poison (may be null): set for a test block with a training point at no finite distance among its neighbours (see
+// bgk_poison_nbr): an ungated update adds the NaN sums, alpha = beta = NaN, UNKNOWN — in both sum modes.  unmark: bgk_sum 0.
+__global__ void bgk_ungated_unmark(const int32_t *__restrict__ nbr, const uint32_t *__restrict__ train_off,
+                                   const uint32_t *__restrict__ leaf_off, float *__restrict__ alpha, float *__restrict__ beta,
+                                   uint8_t *__restrict__ state, uint32_t n_test_blk, const uint8_t *__restrict__ blk_poison, int unmark) {
+    const uint32_t blk = blockIdx.x;
+    if (blk >= n_test_blk) return;
+    if (blk_poison && blk_poison[blk]) {
+        for (uint32_t l = leaf_off[blk] + threadIdx.x; l < leaf_off[blk + 1]; l += blockDim.x) {
+            alpha[l] = __builtin_nanf("");
+            beta[l] = __builtin_nanf("");
+            state[l] = (uint8_t)(0x80u | LA3DM_UNKNOWN);
+        }
+        return;
+    }
+    if (!unmark) return;
+    bool trained = false;
+    for (int b = 0; b < 7; ++b) {
+        const int32_t tb = nbr[7 * (size_t)blk + b];
+        if (tb >= 0 && train_off[tb + 1] != train_off[tb]) trained = true;
+    }
+    if (trained) return;
+    for (uint32_t l = leaf_off[blk] + threadIdx.x; l < leaf_off[blk + 1]; l += blockDim.x) state[l] = 0;
+}
+
+// Training points at no finite distance (a NaN coordinate, a point so far away that the squared distance overflows).  The
+// reference's kernel matrix holds NaN in such a point's column (cos / sin of a NaN or infinite argument; the `< 0 -> 0`
+// clean-up lets NaN through, include/bgkoctomap/bgkinference.h:113-125), so ybar and kbar of its training block are NaN at
+// EVERY leaf and `kbar > 0` rejects that neighbour's update (src/bgkoctomap/bgkoctomap.cpp:331-333).  bgk_predict_fuse_v5 /
+// _r / _t drop such a point at their distance tests and would go on with the neighbour's other points.  This pass, ahead of
+// bgk_prepare on the scans that take the two launches, writes the neighbour table those kernels read: a neighbour that holds
+// such a point is taken out (-1) — bgk_sum 0 then skips exactly the update the reference rejects; with bgk_sum 1, ONE sum over
+// all seven neighbours, a NaN in any of them rejects the leaf's only update, so all seven are taken out (whole_block).
+// (bgk_predict_fuse_t1 finds such points itself while it stages them.)  One workgroup of 64 lanes per test block, each
+// neighbour's points strided over the lanes; the distance is taken from the block's centre, in the kernels' arithmetic:
+// for a coordinate that large the leaf's own offset inside the block is below half an ulp, every leaf gets the same d2.
+__global__ void bgk_poison_nbr(const float4 *__restrict__ pts, const uint32_t *__restrict__ train_off, const int32_t *__restrict__ nbr,
+                               const float *__restrict__ blk_center, int32_t *__restrict__ nbr_out, uint8_t *__restrict__ blk_poison,
+                               uint32_t n_test_blk, float ell, int whole_block) {
+    const uint32_t blk = blockIdx.x, lane = threadIdx.x;
+    if (blk >= n_test_blk) return;
+    const float cx = blk_center[3 * (size_t)blk + 0] / ell, cy = blk_center[3 * (size_t)blk + 1] / ell, cz = blk_center[3 * (size_t)blk + 2] / ell;
+    uint32_t bad_mask = 0;
+    for (int b = 0; b < 7; ++b) {
+        const int32_t tb = nbr[7 * (size_t)blk + b];
+        if (tb < 0) continue;
+        const uint32_t first = train_off[tb], cnt = train_off[tb + 1] - first;
+        bool bad = false;
+        for (uint32_t i = lane; i < cnt; i += blockDim.x) {
+            const float4 p = pts[first + i];
+            const float dx = p.x / ell - cx, dy = p.y / ell - cy, dz = p.z / ell - cz;
+            const float d2 = dx * dx + (dy * dy + dz * dz);
+            bad |= !(d2 < __builtin_inff());
+        }
+        if (__ballot(bad) != 0ull) bad_mask |= 1u << b;
+    }
+    if (lane < 7u) {
+        const bool drop = whole_block ? bad_mask != 0u : ((bad_mask >> lane) & 1u) != 0u;
+        nbr_out[7 * (size_t)blk + lane] = drop ? -1 : nbr[7 * (size_t)blk + lane];
+    }
+    if (lane == 0u) blk_poison[blk] = bad_mask != 0u ? 1 : 0;
+}
+
 // the part of LvArgs that only depends on the map's parameters and the number of packed blocks
 static void lv_fill_args(la3dm_ctx *ctx, LvArgs &a, uint32_t n_blk) {
     const int d = ctx->p.block_depth;
@@ -266,7 +337,7 @@ void la3dm_destroy(la3dm_ctx *ctx) {
     }
     (void)hipSetDevice(ctx->device);
     Arena *all[] = {&ctx->l_task_item, &ctx->l_split_list, &ctx->l_nb_first, &ctx->l_part, &ctx->l_counters, &ctx->l_item_desc, &ctx->l_rowrec, &ctx->l_batch_off, &ctx->l_item_hits, &ctx->l_bdesc, &ctx->l_vals, &ctx->l_rowx, &ctx->l_dense, &ctx->l_labmask, &ctx->l_part64,
-                    &ctx->pts_scaled, &ctx->nbr_range, &ctx->blk_desc, &ctx->label_seq, &ctx->gp_loff, &ctx->gp_totals, &ctx->gp_order, &ctx->gp_L, &ctx->gp_alpha, &ctx->gp_v, &ctx->lv_samples, &ctx->lv_sorted, &ctx->lv_rays, &ctx->lv_cell, &ctx->lv_center,
+                    &ctx->pts_scaled, &ctx->nbr_range, &ctx->blk_desc, &ctx->label_seq, &ctx->nbr_finite, &ctx->blk_poison, &ctx->gp_loff, &ctx->gp_totals, &ctx->gp_order, &ctx->gp_L, &ctx->gp_alpha, &ctx->gp_v, &ctx->lv_samples, &ctx->lv_sorted, &ctx->lv_rays, &ctx->lv_cell, &ctx->lv_center,
                     &ctx->lv_cell0, &ctx->lv_alpha, &ctx->lv_beta, &ctx->lv_state, &ctx->lvp_sub_task, &ctx->lvp_task, &ctx->lvp_cand, &ctx->lvp_totals, &ctx->lvp_rows, &ctx->lvp_sub_out, &ctx->h_train, &ctx->h_train_off, &ctx->h_nbr, &ctx->h_center, &ctx->h_leaf_off,
                     &ctx->h_leaf_key, &ctx->h_alpha, &ctx->h_beta, &ctx->h_state, &ctx->h_diag_in, &ctx->h_diag_out};
     for (Arena *a : all)
@@ -452,8 +523,15 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
         // per-neighbour ranges, the others (bgk_predict_fuse_t / _r) the 64-byte descriptors — each of them a dependent chain
         // nbr -> train_off per block, so only the one that will be read is produced
         const bool want_desc = sum_f64;
+        // the neighbour table without the neighbours that hold a point at no finite distance (bgk_poison_nbr)
+        rc = arena_reserve(ctx, ctx->nbr_finite, sizeof(int32_t) * 7 * (size_t)s->n_test_blk);
+        if (rc != LA3DM_OK) return rc;
+        rc = arena_reserve(ctx, ctx->blk_poison, (size_t)s->n_test_blk);
+        if (rc != LA3DM_OK) return rc;
+        hipLaunchKernelGGL(bgk_poison_nbr, dim3(s->n_test_blk), dim3(kWave), 0, stream, (const float4 *)s->train_xyzy, s->train_off, s->nbr,
+                           s->blk_center, (int32_t *)ctx->nbr_finite.ptr, (uint8_t *)ctx->blk_poison.ptr, s->n_test_blk, ctx->p.ell, sum_f64 ? 1 : 0);
         hipLaunchKernelGGL(bgk_prepare, g, b, 0, stream, (const float4 *)s->train_xyzy, (float4 *)ctx->pts_scaled.ptr,
-                           s->n_train_pts, ctx->p.ell, s->nbr, s->train_off, sum_f64 ? (uint2 *)nullptr : (uint2 *)ctx->nbr_range.ptr, n_nbr,
+                           s->n_train_pts, ctx->p.ell, (const int32_t *)ctx->nbr_finite.ptr, s->train_off, sum_f64 ? (uint2 *)nullptr : (uint2 *)ctx->nbr_range.ptr, n_nbr,
                            want_desc ? (uint32_t *)ctx->blk_desc.ptr : (uint32_t *)nullptr,
                            sum_f64 ? (uint32_t *)ctx->label_seq.ptr : (uint32_t *)nullptr, ctx->scan_seq, da);
     }
@@ -530,6 +608,9 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     }
 #undef LAUNCH_BGK
 #undef LAUNCH_BGK_AS
+    if ((s->flags & LA3DM_SCAN_UPDATE_UNGATED) && !one_launch)  // ungated scans only: the reference's order leaves a test block without a trained neighbour alone; NaN sums are added (see bgk_ungated_unmark)
+        hipLaunchKernelGGL(bgk_ungated_unmark, dim3(s->n_test_blk), dim3(kWave), 0, stream, s->nbr, s->train_off, s->leaf_off, s->alpha, s->beta, s->state,
+                           s->n_test_blk, (const uint8_t *)ctx->blk_poison.ptr, sum_f64 ? 0 : 1);
     HIP_TRY(ctx, hipGetLastError());
     if (out) {
         out->n_tiles = a.n_tasks;
