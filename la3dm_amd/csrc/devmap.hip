@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -2218,6 +2219,131 @@ int la3dm_devmap_download(la3dm_devmap *dm, int64_t *keys, float *A, float *B, u
     return LA3DM_OK;
 }
 
+// ---- what the queries' entry points share -----------------------------------------------------------------------
+// Every query has a device-pointer and a host-pointer form with one body, X_query(dm, host, who, ...): the checks, the
+// constant answer of an empty map (Fill), the staging of the caller's arrays (Stage), X_launch, the copies back.
+#define DM_OK(expr)                        \
+    do {                                   \
+        int rc_ = (expr);                  \
+        if (rc_ != LA3DM_OK) return rc_;   \
+    } while (0)
+
+extern "C++" {   // (member templates, inside the C ABI's block)
+namespace {
+struct RegionGeom {
+    uint32_t g0[3], dims[3];
+    uint64_t total;   // box: voxels; columns: columns
+    la3dm_region_info info;
+};
+
+// The device twins of a query's arrays.  in() and out() register an array by the variable that holds the caller's pointer;
+// reserve() sums the sizes, every array aligned to 16 bytes (the widest store of a query kernel), reserves `cloud` for
+// the inputs and `q_out` for the outputs once each — an arena may move when it grows, hence after every registration —,
+// points the variables at the twins and uploads the inputs; download() queues the copies of the outputs back.  A null
+// pointer or a count of 0 gives a null twin and takes no room.  Device-pointer form (host = false): the caller's pointers
+// are the device pointers, nothing is reserved or copied.
+struct Stage {
+    struct Item {
+        void *slot;     // the registered variable (a pointer of any type)
+        void *caller;   // what it held
+        size_t bytes, elem;
+        bool is_out;
+    };
+    la3dm_devmap *dm;
+    bool host;
+    int n_items = 0;
+    Item item[16];
+    Stage(la3dm_devmap *dm_, bool host_) : dm(dm_), host(host_) {}
+    template <class T>
+    int in(const T *&p, size_t count) { return add(&p, (void *)p, count, sizeof(T), false); }
+    template <class T>
+    int out(T *&p, size_t count) { return add(&p, p, count, sizeof(T), true); }
+    int add(void *slot, void *caller, size_t count, size_t elem, bool is_out) {
+        if (!host) return -1;
+        assert(n_items < 16);
+        item[n_items] = Item{slot, caller, caller ? count * elem : 0, elem, is_out};
+        return n_items++;
+    }
+    // fewer elements to copy back than were given room, known only after the launch; i = what out() returned
+    void count(int i, size_t n) {
+        if (i >= 0) item[i].bytes = std::min(item[i].bytes, n * item[i].elem);
+    }
+    int reserve() {
+        size_t total[2] = {0, 0};
+        for (int i = 0; i < n_items; ++i) total[item[i].is_out] += (item[i].bytes + 15) & ~(size_t)15;
+        if (total[0]) DM_RESERVE(dm->cloud, total[0]);
+        if (total[1]) DM_RESERVE(dm->q_out, total[1]);
+        size_t at[2] = {0, 0};
+        for (int i = 0; i < n_items; ++i) {
+            const Item &it = item[i];
+            Arena &arena = it.is_out ? dm->q_out : dm->cloud;
+            void *twin = it.bytes ? (char *)arena.ptr + at[it.is_out] : nullptr;
+            at[it.is_out] += (it.bytes + 15) & ~(size_t)15;
+            memcpy(it.slot, &twin, sizeof(twin));
+            if (it.bytes && !it.is_out) DM_TRY(hipMemcpyAsync(twin, it.caller, it.bytes, hipMemcpyHostToDevice, dm->ctx->stream));
+        }
+        return LA3DM_OK;
+    }
+    int download() {
+        for (int i = 0; i < n_items; ++i) {
+            const Item &it = item[i];
+            if (!it.is_out || !it.bytes) continue;
+            void *twin;
+            memcpy(&twin, it.slot, sizeof(twin));
+            DM_TRY(hipMemcpyAsync(it.caller, twin, it.bytes, hipMemcpyDeviceToHost, dm->ctx->stream));
+        }
+        return LA3DM_OK;
+    }
+};
+
+// The constant answer of an empty map, written without a launch: host memory directly, device memory by memsets on the
+// map's stream.  A null array is left out.
+struct Fill {
+    la3dm_devmap *dm;
+    bool host;
+    int bytes(void *p, int value, size_t n) const {
+        if (!p) return LA3DM_OK;
+        if (host)
+            memset(p, value, n);
+        else
+            DM_TRY(hipMemsetAsync(p, value, n, dm->ctx->stream));
+        return LA3DM_OK;
+    }
+    int words(void *p, uint32_t value, size_t n) const {   // n 32-bit words
+        if (!p) return LA3DM_OK;
+        if (host)
+            for (size_t i = 0; i < n; ++i) memcpy((char *)p + 4 * i, &value, 4);
+        else
+            DM_TRY(hipMemsetD32Async((hipDeviceptr_t)p, (int)value, n, dm->ctx->stream));
+        return LA3DM_OK;
+    }
+    // p[i * stride] = value for i < n, in memory that holds zeros (device: byte by byte down the column of rows, the
+    // non-zero bytes only)
+    int strided(uint32_t *p, uint32_t value, size_t stride, size_t n) const {
+        if (host) {
+            for (size_t i = 0; i < n; ++i) p[i * stride] = value;
+            return LA3DM_OK;
+        }
+        for (uint32_t byte = 0; byte < 4; ++byte)
+            if ((value >> (8 * byte)) & 0xFFu)
+                DM_TRY(hipMemset2DAsync((uint8_t *)p + byte, 4 * stride, (int)((value >> (8 * byte)) & 0xFFu), 1, n, dm->ctx->stream));
+        return LA3DM_OK;
+    }
+};
+inline uint32_t float_bits(float v) {
+    uint32_t w;
+    memcpy(&w, &v, 4);
+    return w;
+}
+}  // namespace
+}  // extern "C++"
+
+// A refused call: LA3DM_ERR_ARG with "<who>: <refusal>" as the context's error; an empty refusal is none (LA3DM_OK).
+static int refuse(la3dm_devmap *dm, const char *who, const std::string &refusal) {
+    if (!dm) return LA3DM_ERR_ARG;
+    return refusal.empty() ? LA3DM_OK : dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+}
+
 int la3dm_devmap_search_host(la3dm_devmap *dm, const float *xyz, uint32_t n, uint8_t *exists, float *A, float *B,
                              uint8_t *state) {
     if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
@@ -2226,26 +2352,22 @@ int la3dm_devmap_search_host(la3dm_devmap *dm, const float *xyz, uint32_t n, uin
     DM_TRY(hipSetDevice(dm->ctx->device));
     hipStream_t st = dm->ctx->stream;
     if (dm->n_blocks == 0) {  // empty map: every query misses
-        for (uint32_t i = 0; i < n; ++i) {
-            exists[i] = 0;
-            A[i] = dm->init_A;
-            B[i] = dm->init_B;
-            state[i] = kStateUnknown;
-        }
-        return LA3DM_OK;
+        const Fill f{dm, true};
+        DM_OK(f.bytes(exists, 0, n));
+        DM_OK(f.words(A, float_bits(dm->init_A), n));
+        DM_OK(f.words(B, float_bits(dm->init_B), n));
+        return f.bytes(state, kStateUnknown, n);
     }
-    DM_RESERVE(dm->cloud, 12ull * n);
-    DM_RESERVE(dm->q_out, 10ull * n + 16);
-    float *qA = (float *)dm->q_out.ptr, *qB = qA + n;
-    uint8_t *qe = (uint8_t *)(qB + n), *qs = qe + n;
-    DM_TRY(hipMemcpyAsync(dm->cloud.ptr, xyz, 12ull * n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dm_search, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float *)dm->cloud.ptr, n, dm->tab_key, dm->tab_val,
-                       dm->tab_cap - 1, dm->A, dm->B, dm->S, dm->npb, dm->depth, dm->block_size, dm->ctx->p.resolution,
-                       dm->init_A, dm->init_B, qe, qA, qB, qs);
-    DM_TRY(hipMemcpyAsync(A, qA, 4ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(B, qB, 4ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(exists, qe, n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(state, qs, n, hipMemcpyDeviceToHost, st));
+    Stage s(dm, true);
+    s.in(xyz, 3ull * n);
+    s.out(A, n);
+    s.out(B, n);
+    s.out(exists, n);
+    s.out(state, n);
+    DM_OK(s.reserve());
+    hipLaunchKernelGGL(dm_search, dim3(cdiv(n, 256)), dim3(256), 0, st, xyz, n, dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->A, dm->B,
+                       dm->S, dm->npb, dm->depth, dm->block_size, dm->ctx->p.resolution, dm->init_A, dm->init_B, exists, A, B, state);
+    DM_OK(s.download());
     DM_TRY(hipStreamSynchronize(st));
     return LA3DM_OK;
 }
@@ -2255,11 +2377,10 @@ static int raycast_check(la3dm_devmap *dm, const float *rays6, uint32_t n, uint3
                          const char *who) {
     if (!dm) return LA3DM_ERR_ARG;
     dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
-    if (max_steps == 0 || max_steps > LA3DM_RAY_MAX_STEPS)
-        return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": max_steps must be 1 ... 2^20");
+    if (max_steps == 0 || max_steps > LA3DM_RAY_MAX_STEPS) return refuse(dm, who, "max_steps must be 1 ... 2^20");
     if (n == 0) return LA3DM_OK;
-    if (!rays6) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": rays6 is NULL");
-    if (!out || !out->steps || !out->flags) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": out, out->steps and out->flags must not be NULL");
+    if (!rays6) return refuse(dm, who, "rays6 is NULL");
+    if (!out || !out->steps || !out->flags) return refuse(dm, who, "out, out->steps and out->flags must not be NULL");
     return LA3DM_OK;
 }
 
@@ -2293,117 +2414,70 @@ static void raycast_launch(la3dm_devmap *dm, const float *d_rays6, uint32_t n, u
     hipLaunchKernelGGL(dm_raycast, dim3(cdiv(n, 256)), dim3(256), 0, dm->ctx->stream, a);
 }
 
-int la3dm_devmap_raycast_device(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
-                                const la3dm_raycast_out *d_out) {
-    int rc = raycast_check(dm, d_rays6, n, max_steps, d_out, "la3dm_devmap_raycast_device");
+// empty map: no ray starts
+static int raycast_empty(const Fill &f, la3dm_devmap *dm, size_t n, const la3dm_raycast_out &o) {
+    DM_OK(f.bytes(o.steps, 0, 4 * n));
+    DM_OK(f.bytes(o.flags, 0, n));
+    DM_OK(f.bytes(o.p, 0, 12 * n));
+    DM_OK(f.bytes(o.block_key, 0, 8 * n));
+    DM_OK(f.bytes(o.node_key, 0, 4 * n));
+    DM_OK(f.bytes(o.cls, (int)LA3DM_RAY_MISSING, n));
+    DM_OK(f.bytes(o.leaf_depth, 255, n));
+    DM_OK(f.words(o.A, float_bits(dm->init_A), n));
+    DM_OK(f.words(o.B, float_bits(dm->init_B), n));
+    return f.bytes(o.counts, 0, 16 * n);
+}
+
+static int raycast_query(la3dm_devmap *dm, bool host, const char *who, const float *rays6, uint32_t n, uint32_t stop_mask,
+                         uint32_t max_steps, const la3dm_raycast_out *out) {
+    int rc = raycast_check(dm, rays6, n, max_steps, out, who);
     if (rc != LA3DM_OK || n == 0) return rc;
     DM_TRY(hipSetDevice(dm->ctx->device));
-    hipStream_t st = dm->ctx->stream;
-    const la3dm_raycast_out &o = *d_out;
-    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched (the constant answer is written by memsets)
-        DM_TRY(hipMemsetAsync(o.steps, 0, 4ull * n, st));
-        DM_TRY(hipMemsetAsync(o.flags, 0, n, st));
-        if (o.p) DM_TRY(hipMemsetAsync(o.p, 0, 12ull * n, st));
-        if (o.block_key) DM_TRY(hipMemsetAsync(o.block_key, 0, 8ull * n, st));
-        if (o.node_key) DM_TRY(hipMemsetAsync(o.node_key, 0, 4ull * n, st));
-        if (o.cls) DM_TRY(hipMemsetAsync(o.cls, (int)LA3DM_RAY_MISSING, n, st));
-        if (o.leaf_depth) DM_TRY(hipMemsetAsync(o.leaf_depth, 255, n, st));
-        uint32_t ab[2];
-        memcpy(&ab[0], &dm->init_A, 4);
-        memcpy(&ab[1], &dm->init_B, 4);
-        if (o.A) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.A, (int)ab[0], n, st));
-        if (o.B) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.B, (int)ab[1], n, st));
-        if (o.counts) DM_TRY(hipMemsetAsync(o.counts, 0, 16ull * n, st));
-        DM_TRY(hipStreamSynchronize(st));
-        return LA3DM_OK;
+    la3dm_raycast_out o = *out;
+    if (dm->n_blocks == 0) {
+        DM_OK(raycast_empty(Fill{dm, host}, dm, n, o));
+    } else {
+        Stage s(dm, host);
+        s.in(rays6, 6ull * n);
+        s.out(o.steps, n);
+        s.out(o.flags, n);
+        s.out(o.p, 3ull * n);
+        s.out(o.block_key, n);
+        s.out(o.node_key, n);
+        s.out(o.cls, n);
+        s.out(o.leaf_depth, n);
+        s.out(o.A, n);
+        s.out(o.B, n);
+        s.out(o.counts, 4ull * n);
+        DM_OK(s.reserve());
+        raycast_launch(dm, rays6, n, stop_mask, max_steps, o);
+        DM_TRY(hipGetLastError());
+        DM_OK(s.download());
     }
-    raycast_launch(dm, d_rays6, n, stop_mask, max_steps, o);
-    DM_TRY(hipGetLastError());
-    DM_TRY(hipStreamSynchronize(st));
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
     return LA3DM_OK;
+}
+
+int la3dm_devmap_raycast_device(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
+                                const la3dm_raycast_out *d_out) {
+    return raycast_query(dm, false, "la3dm_devmap_raycast_device", d_rays6, n, stop_mask, max_steps, d_out);
 }
 
 int la3dm_devmap_raycast_host(la3dm_devmap *dm, const float *rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
                               const la3dm_raycast_out *out) {
-    int rc = raycast_check(dm, rays6, n, max_steps, out, "la3dm_devmap_raycast_host");
-    if (rc != LA3DM_OK || n == 0) return rc;
-    const la3dm_raycast_out &h = *out;
-    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched
-        for (uint32_t i = 0; i < n; ++i) {
-            h.steps[i] = 0;
-            h.flags[i] = 0;
-            if (h.p) h.p[3 * (size_t)i] = h.p[3 * (size_t)i + 1] = h.p[3 * (size_t)i + 2] = 0.f;
-            if (h.block_key) h.block_key[i] = 0;
-            if (h.node_key) h.node_key[i] = 0;
-            if (h.cls) h.cls[i] = (uint8_t)LA3DM_RAY_MISSING;
-            if (h.leaf_depth) h.leaf_depth[i] = 255;
-            if (h.A) h.A[i] = dm->init_A;
-            if (h.B) h.B[i] = dm->init_B;
-            if (h.counts) h.counts[4 * (size_t)i] = h.counts[4 * (size_t)i + 1] = h.counts[4 * (size_t)i + 2] = h.counts[4 * (size_t)i + 3] = 0;
-        }
-        return LA3DM_OK;
-    }
-    DM_TRY(hipSetDevice(dm->ctx->device));
-    hipStream_t st = dm->ctx->stream;
-    // arenas as in la3dm_devmap_search_host: rays in `cloud`, results in `q_out` (widest type first: every array aligned)
-    DM_RESERVE(dm->cloud, 24ull * n);
-    DM_RESERVE(dm->q_out, 55ull * n + 64);
-    la3dm_raycast_out d;
-    d.block_key = (int64_t *)dm->q_out.ptr;
-    d.counts = (uint32_t *)(d.block_key + n);
-    d.p = (float *)(d.counts + 4ull * n);
-    d.steps = (uint32_t *)(d.p + 3ull * n);
-    d.node_key = (int32_t *)(d.steps + n);
-    d.A = (float *)(d.node_key + n);
-    d.B = d.A + n;
-    d.flags = (uint8_t *)(d.B + n);
-    d.cls = d.flags + n;
-    d.leaf_depth = d.cls + n;
-    if (!h.p) d.p = nullptr;
-    if (!h.block_key) d.block_key = nullptr;
-    if (!h.node_key) d.node_key = nullptr;
-    if (!h.cls) d.cls = nullptr;
-    if (!h.leaf_depth) d.leaf_depth = nullptr;
-    if (!h.A) d.A = nullptr;
-    if (!h.B) d.B = nullptr;
-    if (!h.counts) d.counts = nullptr;
-    DM_TRY(hipMemcpyAsync(dm->cloud.ptr, rays6, 24ull * n, hipMemcpyHostToDevice, st));
-    raycast_launch(dm, (const float *)dm->cloud.ptr, n, stop_mask, max_steps, d);
-    DM_TRY(hipGetLastError());
-    DM_TRY(hipMemcpyAsync(h.steps, d.steps, 4ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(h.flags, d.flags, n, hipMemcpyDeviceToHost, st));
-    if (h.p) DM_TRY(hipMemcpyAsync(h.p, d.p, 12ull * n, hipMemcpyDeviceToHost, st));
-    if (h.block_key) DM_TRY(hipMemcpyAsync(h.block_key, d.block_key, 8ull * n, hipMemcpyDeviceToHost, st));
-    if (h.node_key) DM_TRY(hipMemcpyAsync(h.node_key, d.node_key, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.cls) DM_TRY(hipMemcpyAsync(h.cls, d.cls, n, hipMemcpyDeviceToHost, st));
-    if (h.leaf_depth) DM_TRY(hipMemcpyAsync(h.leaf_depth, d.leaf_depth, n, hipMemcpyDeviceToHost, st));
-    if (h.A) DM_TRY(hipMemcpyAsync(h.A, d.A, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.B) DM_TRY(hipMemcpyAsync(h.B, d.B, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.counts) DM_TRY(hipMemcpyAsync(h.counts, d.counts, 16ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    return LA3DM_OK;
+    return raycast_query(dm, true, "la3dm_devmap_raycast_host", rays6, n, stop_mask, max_steps, out);
 }
 
 // ---- dense region reads (devmap_region.h) --------------------------------------------------------------------
-namespace {
-struct RegionGeom {
-    uint32_t g0[3], dims[3];
-    uint64_t total;   // box: voxels; columns: columns
-    la3dm_region_info info;
-};
-}  // namespace
-
 // The region's checks and its anchor (host/region_contract.h, shared with the host twin BGKOctoMap::region_anchor), then
 // info.origin, for which the one LUT entry of the anchor cell is fetched from the device.
 static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_region::Query &q, bool has_out,
                           bool has_mandatory, const char *who, RegionGeom &g) {
     if (!dm) return LA3DM_ERR_ARG;
     dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
-    const std::string w(who);
     la3dm_region::Anchor an;
-    const std::string refusal = la3dm_region::resolve(q, lo3, dims3, dm->ctx->p.resolution, dm->block_size, dm->depth, has_out,
-                                                      has_mandatory, "->", an);
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
+    DM_OK(refuse(dm, who, la3dm_region::resolve(q, lo3, dims3, dm->ctx->p.resolution, dm->block_size, dm->depth, has_out, has_mandatory,
+                                                "->", an)));
     for (int k = 0; k < 3; ++k) {
         g.g0[k] = an.g0[k];
         g.dims[k] = dims3[k];
@@ -2417,7 +2491,7 @@ static int region_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *di
     for (int level = dl - 1; level >= 0; --level)
         index = index * 8u + ((((an.cell[0] >> level) & 1u) << 2) | (((an.cell[1] >> level) & 1u) << 1) | ((an.cell[2] >> level) & 1u));
     const uint32_t entry = (0x249249u & ((1u << (3u * (uint32_t)dl)) - 1u)) + index;
-    if (entry >= dm->ctx->lut_count) return dm_fail(dm, LA3DM_ERR_ARG, w + ": the context's voxel LUT does not reach the finest layer");
+    if (entry >= dm->ctx->lut_count) return refuse(dm, who, "the context's voxel LUT does not reach the finest layer");
     float4 o;
     DM_TRY(hipSetDevice(dm->ctx->device));
     DM_TRY(hipMemcpyAsync(&o, dm->ctx->d_lut + entry, sizeof(o), hipMemcpyDeviceToHost, dm->ctx->stream));
@@ -2463,136 +2537,90 @@ static void columns_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_co
     hipLaunchKernelGGL(dm_columns, dim3(cdiv(a.total, 256)), dim3(256), 0, dm->ctx->stream, a);
 }
 
-int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *d_out,
-                            la3dm_region_info *info) {
+// empty map: every block is missing
+static int box_empty(const Fill &f, la3dm_devmap *dm, size_t n, const la3dm_box_out &o) {
+    DM_OK(f.bytes(o.cls, (int)LA3DM_RAY_MISSING, n));
+    DM_OK(f.bytes(o.leaf_depth, 255, n));
+    DM_OK(f.words(o.A, float_bits(dm->init_A), n));
+    return f.words(o.B, float_bits(dm->init_B), n);
+}
+
+static int box_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out,
+                     la3dm_region_info *info) {
     RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kBox, d_out != nullptr, d_out && d_out->cls, "la3dm_devmap_box_device", g);
-    if (rc != LA3DM_OK) return rc;
-    hipStream_t st = dm->ctx->stream;
-    const la3dm_box_out &o = *d_out;
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kBox, out != nullptr, out && out->cls, who, g));
+    la3dm_box_out o = *out;
     const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: every block is missing, nothing is launched (the constant answer is written by memsets)
-        DM_TRY(hipMemsetAsync(o.cls, (int)LA3DM_RAY_MISSING, n, st));
-        if (o.leaf_depth) DM_TRY(hipMemsetAsync(o.leaf_depth, 255, n, st));
-        uint32_t ab[2];
-        memcpy(&ab[0], &dm->init_A, 4);
-        memcpy(&ab[1], &dm->init_B, 4);
-        if (o.A) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.A, (int)ab[0], n, st));
-        if (o.B) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.B, (int)ab[1], n, st));
+    if (dm->n_blocks == 0) {
+        DM_OK(box_empty(Fill{dm, host}, dm, n, o));
     } else {
+        Stage s(dm, host);   // (every twin aligned for the four-voxel stores)
+        s.out(o.cls, n);
+        s.out(o.leaf_depth, n);
+        s.out(o.A, n);
+        s.out(o.B, n);
+        DM_OK(s.reserve());
         box_launch(dm, g, o);
         DM_TRY(hipGetLastError());
+        DM_OK(s.download());
     }
-    DM_TRY(hipStreamSynchronize(st));
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
     if (info) *info = g.info;
     return LA3DM_OK;
 }
 
+int la3dm_devmap_box_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *d_out,
+                            la3dm_region_info *info) {
+    return box_query(dm, false, "la3dm_devmap_box_device", lo3, dims3, d_out, info);
+}
+
 int la3dm_devmap_box_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_box_out *out,
                           la3dm_region_info *info) {
+    return box_query(dm, true, "la3dm_devmap_box_host", lo3, dims3, out, info);
+}
+
+// empty map: {0, 0, 0, nz} per column (nz <= 2^16), no occupied voxel
+static int columns_empty(const Fill &f, size_t n, uint32_t nz, const la3dm_columns_out &o) {
+    DM_OK(f.bytes(o.counts, 0, 16 * n));
+    DM_OK(f.strided(o.counts + 3, nz, 4, n));
+    DM_OK(f.bytes(o.low_occ, 0xFF, 4 * n));
+    return f.bytes(o.top_occ, 0xFF, 4 * n);
+}
+
+static int columns_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3,
+                         const la3dm_columns_out *out, la3dm_region_info *info) {
     RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kBox, out != nullptr, out && out->cls, "la3dm_devmap_box_host", g);
-    if (rc != LA3DM_OK) return rc;
-    const la3dm_box_out &h = *out;
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kColumns, out != nullptr, out && out->counts, who, g));
+    la3dm_columns_out o = *out;
     const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: every block is missing, nothing is launched
-        memset(h.cls, (int)LA3DM_RAY_MISSING, n);
-        if (h.leaf_depth) memset(h.leaf_depth, 255, n);
-        if (h.A) std::fill(h.A, h.A + n, dm->init_A);
-        if (h.B) std::fill(h.B, h.B + n, dm->init_B);
-        if (info) *info = g.info;
-        return LA3DM_OK;
+    if (dm->n_blocks == 0) {
+        DM_OK(columns_empty(Fill{dm, host}, n, g.dims[2], o));
+    } else {
+        Stage s(dm, host);   // (per column, nothing that grows with nz)
+        s.out(o.counts, 4 * n);
+        s.out(o.low_occ, n);
+        s.out(o.top_occ, n);
+        DM_OK(s.reserve());
+        columns_launch(dm, g, o);
+        DM_TRY(hipGetLastError());
+        DM_OK(s.download());
     }
-    hipStream_t st = dm->ctx->stream;
-    // results in `q_out`, widest type first: every array aligned for the four-voxel stores
-    const size_t n16 = (n + 15) & ~(size_t)15;
-    DM_RESERVE(dm->q_out, 10ull * n16 + 64);
-    la3dm_box_out d;
-    d.A = (float *)dm->q_out.ptr;
-    d.B = d.A + n16;
-    d.cls = (uint8_t *)(d.B + n16);
-    d.leaf_depth = d.cls + n16;
-    if (!h.leaf_depth) d.leaf_depth = nullptr;
-    if (!h.A) d.A = nullptr;
-    if (!h.B) d.B = nullptr;
-    box_launch(dm, g, d);
-    DM_TRY(hipGetLastError());
-    DM_TRY(hipMemcpyAsync(h.cls, d.cls, n, hipMemcpyDeviceToHost, st));
-    if (h.leaf_depth) DM_TRY(hipMemcpyAsync(h.leaf_depth, d.leaf_depth, n, hipMemcpyDeviceToHost, st));
-    if (h.A) DM_TRY(hipMemcpyAsync(h.A, d.A, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.B) DM_TRY(hipMemcpyAsync(h.B, d.B, 4ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
     if (info) *info = g.info;
     return LA3DM_OK;
 }
 
 int la3dm_devmap_columns_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *d_out,
                                 la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kColumns, d_out != nullptr, d_out && d_out->counts, "la3dm_devmap_columns_device", g);
-    if (rc != LA3DM_OK) return rc;
-    hipStream_t st = dm->ctx->stream;
-    const la3dm_columns_out &o = *d_out;
-    const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: {0, 0, 0, nz} per column, no occupied voxel; nothing is launched
-        DM_TRY(hipMemsetAsync(o.counts, 0, 16ull * n, st));
-        for (uint32_t byte = 0; byte < 3; ++byte)   // counts[3] = nz <= 2^16, byte by byte down the column of rows
-            if ((g.dims[2] >> (8 * byte)) & 0xFFu)
-                DM_TRY(hipMemset2DAsync((uint8_t *)(o.counts + 3) + byte, 16, (int)((g.dims[2] >> (8 * byte)) & 0xFFu), 1, n, st));
-        if (o.low_occ) DM_TRY(hipMemsetAsync(o.low_occ, 0xFF, 4ull * n, st));
-        if (o.top_occ) DM_TRY(hipMemsetAsync(o.top_occ, 0xFF, 4ull * n, st));
-    } else {
-        columns_launch(dm, g, o);
-        DM_TRY(hipGetLastError());
-    }
-    DM_TRY(hipStreamSynchronize(st));
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return columns_query(dm, false, "la3dm_devmap_columns_device", lo3, dims3, d_out, info);
 }
 
 int la3dm_devmap_columns_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_columns_out *out,
                               la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kColumns, out != nullptr, out && out->counts, "la3dm_devmap_columns_host", g);
-    if (rc != LA3DM_OK) return rc;
-    const la3dm_columns_out &h = *out;
-    const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: every block is missing, nothing is launched
-        for (size_t c = 0; c < n; ++c) {
-            h.counts[4 * c] = h.counts[4 * c + 1] = h.counts[4 * c + 2] = 0;
-            h.counts[4 * c + 3] = g.dims[2];
-            if (h.low_occ) h.low_occ[c] = -1;
-            if (h.top_occ) h.top_occ[c] = -1;
-        }
-        if (info) *info = g.info;
-        return LA3DM_OK;
-    }
-    hipStream_t st = dm->ctx->stream;
-    DM_RESERVE(dm->q_out, 24ull * n + 64);   // per column, nothing that grows with nz
-    la3dm_columns_out d;
-    d.counts = (uint32_t *)dm->q_out.ptr;
-    d.low_occ = (int32_t *)(d.counts + 4 * n);
-    d.top_occ = d.low_occ + n;
-    if (!h.low_occ) d.low_occ = nullptr;
-    if (!h.top_occ) d.top_occ = nullptr;
-    columns_launch(dm, g, d);
-    DM_TRY(hipGetLastError());
-    DM_TRY(hipMemcpyAsync(h.counts, d.counts, 16ull * n, hipMemcpyDeviceToHost, st));
-    if (h.low_occ) DM_TRY(hipMemcpyAsync(h.low_occ, d.low_occ, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.top_occ) DM_TRY(hipMemcpyAsync(h.top_occ, d.top_occ, 4ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return columns_query(dm, true, "la3dm_devmap_columns_host", lo3, dims3, out, info);
 }
 
 // ---- distance field of a region (devmap_distance.h) -------------------------------------------------------------
-static int distance_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
-                            const la3dm_distance_out *out, const char *who, RegionGeom &g) {
-    if (!dm) return LA3DM_ERR_ARG;
-    const std::string refusal = la3dm_region::distance_check(obstacle_mask, radius);
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
-    return region_resolve(dm, lo3, dims3, la3dm_region::kDistance, out != nullptr, out && (out->d2 || out->dist), who, g);
-}
 
 // a min-plus pass over 16-bit z distances or (wide) 32-bit partial sums: staged in LDS where the rows of a workgroup and
 // their halo fit, else straight from global memory
@@ -2644,72 +2672,48 @@ static void distance_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t obst
     df_pass_launch(st, y_pass, p.n_lt * p.n_ct, rows, p);
 }
 
-int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
-                                 uint32_t radius, const la3dm_distance_out *d_out, la3dm_region_info *info) {
+// empty map: every voxel is MISSING — all obstacles (0 everywhere) or none (FAR, +inf)
+static int distance_empty(const Fill &f, size_t n, uint32_t obstacle_mask, const la3dm_distance_out &o) {
+    const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
+    DM_OK(f.bytes(o.d2, all ? 0 : 0xFF, 4 * n));
+    return f.words(o.dist, all ? 0u : 0x7F800000u, n);
+}
+
+static int distance_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                          uint32_t radius, const la3dm_distance_out *out, la3dm_region_info *info) {
     RegionGeom g;
-    int rc = distance_resolve(dm, lo3, dims3, obstacle_mask, radius, d_out, "la3dm_devmap_distance_device", g);
-    if (rc != LA3DM_OK) return rc;
-    hipStream_t st = dm->ctx->stream;
-    const la3dm_distance_out &o = *d_out;
+    DM_OK(refuse(dm, who, la3dm_region::distance_check(obstacle_mask, radius)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kDistance, out != nullptr, out && (out->d2 || out->dist), who, g));
+    la3dm_distance_out o = *out;
     const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: every voxel is MISSING — all obstacles or none; nothing is launched
-        const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
-        if (o.d2) DM_TRY(hipMemsetAsync(o.d2, all ? 0 : 0xFF, 4ull * n, st));
-        if (o.dist) DM_TRY(hipMemsetD32Async((hipDeviceptr_t)o.dist, all ? 0 : 0x7F800000, n, st));
+    if (dm->n_blocks == 0) {
+        DM_OK(distance_empty(Fill{dm, host}, n, obstacle_mask, o));
     } else {
+        Stage s(dm, host);
+        s.out(o.d2, n);
+        s.out(o.dist, n);
+        DM_OK(s.reserve());
         DM_RESERVE(dm->df_work, 4ull * n);
         distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, o);
         DM_TRY(hipGetLastError());
+        DM_OK(s.download());
     }
-    DM_TRY(hipStreamSynchronize(st));
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
     if (info) *info = g.info;
     return LA3DM_OK;
+}
+
+int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                                 uint32_t radius, const la3dm_distance_out *d_out, la3dm_region_info *info) {
+    return distance_query(dm, false, "la3dm_devmap_distance_device", lo3, dims3, obstacle_mask, radius, d_out, info);
 }
 
 int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
                                uint32_t radius, const la3dm_distance_out *out, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = distance_resolve(dm, lo3, dims3, obstacle_mask, radius, out, "la3dm_devmap_distance_host", g);
-    if (rc != LA3DM_OK) return rc;
-    const la3dm_distance_out &h = *out;
-    const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: every voxel is MISSING — all obstacles or none; nothing is launched
-        const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
-        if (h.d2) std::fill(h.d2, h.d2 + n, all ? 0u : LA3DM_DF_FAR);
-        if (h.dist) std::fill(h.dist, h.dist + n, all ? 0.0f : std::numeric_limits<float>::infinity());
-        if (info) *info = g.info;
-        return LA3DM_OK;
-    }
-    hipStream_t st = dm->ctx->stream;
-    DM_RESERVE(dm->df_work, 4ull * n);
-    DM_RESERVE(dm->q_out, 4ull * n * ((h.d2 ? 1 : 0) + (h.dist ? 1 : 0)));   // the outputs asked for
-    la3dm_distance_out d;
-    d.d2 = h.d2 ? (uint32_t *)dm->q_out.ptr : nullptr;
-    d.dist = h.dist ? (float *)dm->q_out.ptr + (h.d2 ? n : 0) : nullptr;
-    distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, d);
-    DM_TRY(hipGetLastError());
-    if (h.d2) DM_TRY(hipMemcpyAsync(h.d2, d.d2, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.dist) DM_TRY(hipMemcpyAsync(h.dist, d.dist, 4ull * n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return distance_query(dm, true, "la3dm_devmap_distance_host", lo3, dims3, obstacle_mask, radius, out, info);
 }
 
 // ---- frontier of a region (devmap_frontier.h) -----------------------------------------------------------------
-static int frontier_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask,
-                            uint32_t connectivity, uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out *out,
-                            const uint64_t *n_found, const char *who, RegionGeom &g) {
-    if (!dm) return LA3DM_ERR_ARG;
-    const std::string w(who);
-    const std::string refusal = la3dm_region::frontier_check(open_mask, unknown_mask, connectivity, min_neighbours);
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
-    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kFrontier, true, true, who, g);   // lo, dims, the limit and the range: before any buffer
-    if (rc != LA3DM_OK) return rc;
-    if (cap > 0 && !out) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out is NULL with cap > 0");
-    if (cap > 0 && !out->index) return dm_fail(dm, LA3DM_ERR_ARG, w + ": out->index must not be NULL with cap > 0");
-    if (!n_found) return dm_fail(dm, LA3DM_ERR_ARG, w + ": n_found is NULL");
-    return LA3DM_OK;
-}
 
 // Bits, stencil, scan and (cap > 0) emit on the map's stream; o's arrays are device memory.  d_total: where the launches
 // leave the number of frontier voxels (a word of the query's working storage).
@@ -2717,7 +2721,7 @@ static int frontier_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t open_
                            uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out &o, const uint32_t *&d_total) {
     hipStream_t st = dm->ctx->stream;
     RegionArgs a = region_args(dm, g);
-    for (int k = 0; k < 3; ++k) a.g0[k] = g.g0[k] - 1u;   // (frontier_resolve: g0 >= 1)
+    for (int k = 0; k < 3; ++k) a.g0[k] = g.g0[k] - 1u;   // (frontier_query's region check: g0 >= 1)
     a.nx = g.dims[0] + 2u;
     a.ny = g.dims[1] + 2u;
     a.nz = g.dims[2] + 2u;
@@ -2766,103 +2770,81 @@ static int frontier_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t open_
     return LA3DM_OK;
 }
 
-int la3dm_devmap_frontier_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
-                                 uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
-                                 const la3dm_frontier_out *d_out, uint64_t *n_found, la3dm_region_info *info) {
+// empty map: every voxel and its surroundings are MISSING — all voxels are frontier (the list 0, 1, 2, ... until cap) or
+// none; the pool is not read
+static int frontier_empty(const Fill &f, size_t n, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity, uint64_t cap,
+                          const la3dm_frontier_out &o, uint32_t &total) {
+    const bool all = ((open_mask & unknown_mask) >> LA3DM_RAY_MISSING) & 1u;
+    total = all ? (uint32_t)n : 0u;
+    DM_OK(f.bytes(o.score, all ? (int)connectivity : 0, n));
+    const uint32_t m = (uint32_t)std::min<uint64_t>(total, cap);
+    if (m && f.host) {
+        for (uint32_t t = 0; t < m; ++t) {
+            o.index[t] = t;
+            if (o.nbrs) o.nbrs[t] = (uint8_t)connectivity;
+        }
+    } else if (m) {
+        la3dm_devmap *dm = f.dm;
+        hipLaunchKernelGGL(dm_fr_all, dim3(cdiv(m, 256)), dim3(256), 0, dm->ctx->stream, o.index, o.nbrs, m, connectivity);
+        DM_TRY(hipGetLastError());
+    }
+    return LA3DM_OK;
+}
+
+static int frontier_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
+                          uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
+                          const la3dm_frontier_out *out, uint64_t *n_found, la3dm_region_info *info) {
     RegionGeom g;
-    int rc = frontier_resolve(dm, lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, d_out, n_found,
-                              "la3dm_devmap_frontier_device", g);
-    if (rc != LA3DM_OK) return rc;
+    DM_OK(refuse(dm, who, la3dm_region::frontier_check(open_mask, unknown_mask, connectivity, min_neighbours)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kFrontier, true, true, who, g));   // lo, dims, the limit and the range: before any buffer
+    if (cap > 0 && !out) return refuse(dm, who, "out is NULL with cap > 0");
+    if (cap > 0 && !out->index) return refuse(dm, who, "out->index must not be NULL with cap > 0");
+    if (!n_found) return refuse(dm, who, "n_found is NULL");
     hipStream_t st = dm->ctx->stream;
     la3dm_frontier_out o;
     memset(&o, 0, sizeof(o));
-    if (d_out) o = *d_out;
+    if (out) o = *out;
     const size_t n = (size_t)g.total;
     uint32_t total = 0;
-    if (dm->n_blocks == 0) {  // empty map: every voxel and its surroundings are MISSING — all voxels or none; the pool is not read
-        const bool all = ((open_mask & unknown_mask) >> LA3DM_RAY_MISSING) & 1u;
-        total = all ? (uint32_t)n : 0u;
-        if (o.score) DM_TRY(hipMemsetAsync(o.score, all ? (int)connectivity : 0, n, st));
-        const uint32_t m = (uint32_t)std::min<uint64_t>(total, cap);
-        if (m) {
-            hipLaunchKernelGGL(dm_fr_all, dim3(cdiv(m, 256)), dim3(256), 0, st, o.index, o.nbrs, m, connectivity);
-            DM_TRY(hipGetLastError());
-        }
+    if (dm->n_blocks == 0) {
+        DM_OK(frontier_empty(Fill{dm, host}, n, open_mask, unknown_mask, connectivity, cap, o, total));
+        DM_TRY(hipStreamSynchronize(st));
     } else {
+        // the list has at most one entry per voxel and no more than cap; only what was found is copied back
+        const size_t room = (size_t)std::min<uint64_t>(cap, n);
+        Stage s(dm, host);
+        const int i_index = s.out(o.index, room), i_nbrs = s.out(o.nbrs, room);
+        s.out(o.score, n);
+        DM_OK(s.reserve());
         const uint32_t *d_total = nullptr;
-        rc = frontier_launch(dm, g, open_mask, unknown_mask, connectivity, min_neighbours, cap, o, d_total);
-        if (rc != LA3DM_OK) return rc;
+        DM_OK(frontier_launch(dm, g, open_mask, unknown_mask, connectivity, min_neighbours, room, o, d_total));
         DM_TRY(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
+        DM_TRY(hipStreamSynchronize(st));
+        s.count(i_index, total);
+        s.count(i_nbrs, total);
+        DM_OK(s.download());
+        if (host) DM_TRY(hipStreamSynchronize(st));
     }
-    DM_TRY(hipStreamSynchronize(st));
     *n_found = total;
     if (info) *info = g.info;
     return LA3DM_OK;
+}
+
+int la3dm_devmap_frontier_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
+                                 uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
+                                 const la3dm_frontier_out *d_out, uint64_t *n_found, la3dm_region_info *info) {
+    return frontier_query(dm, false, "la3dm_devmap_frontier_device", lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap,
+                          d_out, n_found, info);
 }
 
 int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t open_mask,
                                uint32_t unknown_mask, uint32_t connectivity, uint32_t min_neighbours, uint64_t cap,
                                const la3dm_frontier_out *out, uint64_t *n_found, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = frontier_resolve(dm, lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, out, n_found,
-                              "la3dm_devmap_frontier_host", g);
-    if (rc != LA3DM_OK) return rc;
-    la3dm_frontier_out h;
-    memset(&h, 0, sizeof(h));
-    if (out) h = *out;
-    const size_t n = (size_t)g.total;
-    if (dm->n_blocks == 0) {  // empty map: every voxel and its surroundings are MISSING — all voxels or none; nothing is launched
-        const bool all = ((open_mask & unknown_mask) >> LA3DM_RAY_MISSING) & 1u;
-        if (h.score) memset(h.score, all ? (int)connectivity : 0, n);
-        const uint64_t m = all ? std::min<uint64_t>(n, cap) : 0;
-        for (uint64_t t = 0; t < m; ++t) {
-            h.index[t] = (uint32_t)t;
-            if (h.nbrs) h.nbrs[t] = (uint8_t)connectivity;
-        }
-        *n_found = all ? n : 0;
-        if (info) *info = g.info;
-        return LA3DM_OK;
-    }
-    hipStream_t st = dm->ctx->stream;
-    // outputs staged in `q_out`: index (at most one entry per voxel, and no more than cap), then nbrs, then score
-    const size_t room = (size_t)std::min<uint64_t>(cap, n), room4 = (room + 3) & ~(size_t)3;
-    DM_RESERVE(dm->q_out, 4ull * room + (h.nbrs ? room4 : 0) + (h.score ? n : 0) + 16);
-    la3dm_frontier_out d;
-    d.index = (uint32_t *)dm->q_out.ptr;
-    d.nbrs = h.nbrs ? (uint8_t *)(d.index + room) : nullptr;
-    d.score = h.score ? (uint8_t *)(d.index + room) + (h.nbrs ? room4 : 0) : nullptr;
-    const uint32_t *d_total = nullptr;
-    rc = frontier_launch(dm, g, open_mask, unknown_mask, connectivity, min_neighbours, room, d, d_total);
-    if (rc != LA3DM_OK) return rc;
-    uint32_t total = 0;
-    DM_TRY(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, st));
-    if (h.score) DM_TRY(hipMemcpyAsync(h.score, d.score, n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    const size_t m = (size_t)std::min<uint64_t>(total, room);   // only what was found is downloaded
-    if (m) {
-        DM_TRY(hipMemcpyAsync(h.index, d.index, 4ull * m, hipMemcpyDeviceToHost, st));
-        if (h.nbrs) DM_TRY(hipMemcpyAsync(h.nbrs, d.nbrs, m, hipMemcpyDeviceToHost, st));
-        DM_TRY(hipStreamSynchronize(st));
-    }
-    *n_found = total;
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return frontier_query(dm, true, "la3dm_devmap_frontier_host", lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, out,
+                          n_found, info);
 }
 
 // ---- gain of candidate viewpoints (devmap_gain.h) ---------------------------------------------------------------
-static int gain_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
-                        const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
-                        const la3dm_gain_out *out, const char *who, RegionGeom &g) {
-    if (!dm) return LA3DM_ERR_ARG;
-    const std::string w(who);
-    std::string refusal = la3dm_region::gain_check(count_mask, stop_mask, max_steps, n, m);
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
-    int rc = region_resolve(dm, lo3, dims3, la3dm_region::kGain, true, true, who, g);   // lo, dims, the limit and the range: before any buffer
-    if (rc != LA3DM_OK) return rc;
-    refusal = la3dm_region::gain_buffers(g.total, n, origins3 != nullptr, offsets3 != nullptr, out != nullptr, out && out->gain, "->");
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, w + ": " + refusal);
-    return LA3DM_OK;
-}
 
 // Zeroing, mark and count on the map's stream; every pointer is device memory.  o.seen null: the sets live in the arena;
 // `sets` returns where they are.
@@ -2911,83 +2893,62 @@ static int gain_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_ori
     return LA3DM_OK;
 }
 
-int la3dm_devmap_gain_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_origins3, uint32_t n,
-                             const float *d_offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
-                             const la3dm_gain_out *d_out, la3dm_region_info *info) {
+// empty map: no ray starts
+static int gain_empty(const Fill &f, size_t n, size_t words, const la3dm_gain_out &o) {
+    DM_OK(f.bytes(o.gain, 0, 4 * n));
+    DM_OK(f.bytes(o.started, 0, 4 * n));
+    DM_OK(f.bytes(o.hits, 0, 4 * n));
+    return f.bytes(o.seen, 0, 4 * words);
+}
+
+static int gain_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const float *origins3,
+                      uint32_t n, const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                      const la3dm_gain_out *out, la3dm_region_info *info) {
     RegionGeom g;
-    int rc = gain_resolve(dm, lo3, dims3, d_origins3, n, d_offsets3, m, count_mask, stop_mask, max_steps, d_out,
-                          "la3dm_devmap_gain_device", g);
-    if (rc != LA3DM_OK) return rc;
+    DM_OK(refuse(dm, who, la3dm_region::gain_check(count_mask, stop_mask, max_steps, n, m)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kGain, true, true, who, g));   // lo, dims, the limit and the range: before any buffer
+    DM_OK(refuse(dm, who, la3dm_region::gain_buffers(g.total, n, origins3 != nullptr, offsets3 != nullptr, out != nullptr, out && out->gain, "->")));
     if (info) *info = g.info;
     if (n == 0) return LA3DM_OK;
     hipStream_t st = dm->ctx->stream;
-    const la3dm_gain_out &o = *d_out;
-    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched (the constant answer is written by memsets)
-        DM_TRY(hipMemsetAsync(o.gain, 0, 4ull * n, st));
-        if (o.started) DM_TRY(hipMemsetAsync(o.started, 0, 4ull * n, st));
-        if (o.hits) DM_TRY(hipMemsetAsync(o.hits, 0, 4ull * n, st));
-        if (o.seen) DM_TRY(hipMemsetAsync(o.seen, 0, 4ull * n * la3dm_region::gain_words(g.total), st));
+    la3dm_gain_out o = *out;
+    const size_t words = (size_t)n * la3dm_region::gain_words(g.total);
+    if (dm->n_blocks == 0) {
+        DM_OK(gain_empty(Fill{dm, host}, n, words, o));
     } else {
+        // host pointers: the sets stay in their own arena (gain_launch) and are copied from there
+        uint32_t *h_seen = host ? o.seen : nullptr;
+        if (host) o.seen = nullptr;
+        Stage s(dm, host);
+        s.in(origins3, 3ull * n);
+        s.in(offsets3, 3ull * m);
+        s.out(o.gain, n);
+        s.out(o.started, n);
+        s.out(o.hits, n);
+        DM_OK(s.reserve());
         const uint32_t *sets = nullptr;
-        rc = gain_launch(dm, g, d_origins3, n, d_offsets3, m, count_mask, stop_mask, max_steps, o, sets);
-        if (rc != LA3DM_OK) return rc;
+        DM_OK(gain_launch(dm, g, origins3, n, offsets3, m, count_mask, stop_mask, max_steps, o, sets));
+        DM_OK(s.download());
+        if (h_seen) DM_TRY(hipMemcpyAsync(h_seen, sets, 4ull * words, hipMemcpyDeviceToHost, st));
     }
     DM_TRY(hipStreamSynchronize(st));
     return LA3DM_OK;
+}
+
+int la3dm_devmap_gain_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_origins3, uint32_t n,
+                             const float *d_offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
+                             const la3dm_gain_out *d_out, la3dm_region_info *info) {
+    return gain_query(dm, false, "la3dm_devmap_gain_device", lo3, dims3, d_origins3, n, d_offsets3, m, count_mask, stop_mask, max_steps, d_out,
+                      info);
 }
 
 int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
                            const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                            const la3dm_gain_out *out, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = gain_resolve(dm, lo3, dims3, origins3, n, offsets3, m, count_mask, stop_mask, max_steps, out,
-                          "la3dm_devmap_gain_host", g);
-    if (rc != LA3DM_OK) return rc;
-    if (info) *info = g.info;
-    if (n == 0) return LA3DM_OK;
-    const la3dm_gain_out &h = *out;
-    const size_t words = (size_t)n * la3dm_region::gain_words(g.total);
-    if (dm->n_blocks == 0) {  // empty map: no ray starts, nothing is launched
-        memset(h.gain, 0, 4ull * n);
-        if (h.started) memset(h.started, 0, 4ull * n);
-        if (h.hits) memset(h.hits, 0, 4ull * n);
-        if (h.seen) memset(h.seen, 0, 4ull * words);
-        return LA3DM_OK;
-    }
-    hipStream_t st = dm->ctx->stream;
-    // origins and offsets in `cloud`; gain, started, hits in `q_out`; the sets in their own arena
-    DM_RESERVE(dm->cloud, 12ull * n + 12ull * m);
-    DM_RESERVE(dm->q_out, 12ull * n);
-    float *d_origins = (float *)dm->cloud.ptr, *d_offsets = d_origins + 3ull * n;
-    la3dm_gain_out d;
-    d.gain = (uint32_t *)dm->q_out.ptr;
-    d.started = h.started ? d.gain + n : nullptr;
-    d.hits = h.hits ? d.gain + 2ull * n : nullptr;
-    d.seen = nullptr;
-    DM_TRY(hipMemcpyAsync(d_origins, origins3, 12ull * n, hipMemcpyHostToDevice, st));
-    DM_TRY(hipMemcpyAsync(d_offsets, offsets3, 12ull * m, hipMemcpyHostToDevice, st));
-    const uint32_t *sets = nullptr;
-    rc = gain_launch(dm, g, d_origins, n, d_offsets, m, count_mask, stop_mask, max_steps, d, sets);
-    if (rc != LA3DM_OK) return rc;
-    DM_TRY(hipMemcpyAsync(h.gain, d.gain, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.started) DM_TRY(hipMemcpyAsync(h.started, d.started, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.hits) DM_TRY(hipMemcpyAsync(h.hits, d.hits, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (h.seen) DM_TRY(hipMemcpyAsync(h.seen, sets, 4ull * words, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    return LA3DM_OK;
+    return gain_query(dm, true, "la3dm_devmap_gain_host", lo3, dims3, origins3, n, offsets3, m, count_mask, stop_mask, max_steps, out, info);
 }
 
 // ---- reach: hop distance from seeds through the passable voxels of a region (devmap_reach.h) -------------------------
-static int reach_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
-                         uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
-                         const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, const char *who, RegionGeom &g) {
-    if (!dm) return LA3DM_ERR_ARG;
-    const std::string refusal = la3dm_region::reach_check(pass_mask, obstacle_mask, clearance, connectivity, max_steps, n_seeds, n_targets,
-                                                          seeds != nullptr, targets != nullptr, out != nullptr, out && out->steps,
-                                                          out && out->target_steps, "->");
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
-    return region_resolve(dm, lo3, dims3, la3dm_region::kReach, true, true, who, g);
-}
 
 // The whole query on the map's stream; every pointer but `stats` is device memory.  The working storage is initialised
 // here on every call.  d_steps: where the dense steps are — o.steps, or the query's working storage when the caller gave
@@ -3077,55 +3038,50 @@ static int reach_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d
     return LA3DM_OK;
 }
 
+static int reach_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const uint32_t *seeds,
+                       uint32_t n_seeds, uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
+                       uint32_t max_steps, const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,
+                       la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::reach_check(pass_mask, obstacle_mask, clearance, connectivity, max_steps, n_seeds, n_targets,
+                                                    seeds != nullptr, targets != nullptr, out != nullptr, out && out->steps,
+                                                    out && out->target_steps, "->")));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kReach, true, true, who, g));
+    hipStream_t st = dm->ctx->stream;
+    la3dm_reach_out o = *out;
+    // host pointers: the dense steps stay in the working storage (reach_launch) and are copied from there
+    uint32_t *h_steps = host ? o.steps : nullptr;
+    if (host) o.steps = nullptr;
+    Stage s(dm, host);
+    s.in(seeds, n_seeds);
+    s.in(targets, n_targets);
+    s.out(o.target_steps, n_targets);
+    DM_OK(s.reserve());
+    la3dm_reach_stats rs;
+    const uint32_t *d_steps = nullptr;
+    DM_OK(reach_launch(dm, g, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, targets, n_targets, o, rs, d_steps));
+    DM_OK(s.download());
+    if (h_steps) DM_TRY(hipMemcpyAsync(h_steps, d_steps, 4ull * (size_t)g.total, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (stats) *stats = rs;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
 int la3dm_devmap_reach_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
                               uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
                               uint32_t max_steps, const uint32_t *d_targets, uint32_t n_targets, const la3dm_reach_out *d_out,
                               la3dm_reach_stats *stats, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = reach_resolve(dm, lo3, dims3, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, d_targets,
-                           n_targets, d_out, "la3dm_devmap_reach_device", g);
-    if (rc != LA3DM_OK) return rc;
-    la3dm_reach_stats s;
-    const uint32_t *d_steps = nullptr;
-    rc = reach_launch(dm, g, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, d_targets, n_targets,
-                      *d_out, s, d_steps);
-    if (rc != LA3DM_OK) return rc;
-    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
-    if (stats) *stats = s;
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return reach_query(dm, false, "la3dm_devmap_reach_device", lo3, dims3, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity,
+                       max_steps, d_targets, n_targets, d_out, stats, info);
 }
 
 int la3dm_devmap_reach_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                             uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity,
                             uint32_t max_steps, const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out,
                             la3dm_reach_stats *stats, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = reach_resolve(dm, lo3, dims3, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, targets,
-                           n_targets, out, "la3dm_devmap_reach_host", g);
-    if (rc != LA3DM_OK) return rc;
-    const la3dm_reach_out &h = *out;
-    hipStream_t st = dm->ctx->stream;
-    // seeds and targets in `cloud`, the steps at the targets in `q_out`; the dense steps stay in the working storage
-    DM_RESERVE(dm->cloud, 4ull * n_seeds + 4ull * n_targets);
-    DM_RESERVE(dm->q_out, 4ull * n_targets);
-    uint32_t *d_seeds = (uint32_t *)dm->cloud.ptr, *d_targets = d_seeds + n_seeds;
-    if (n_seeds) DM_TRY(hipMemcpyAsync(d_seeds, seeds, 4ull * n_seeds, hipMemcpyHostToDevice, st));
-    if (n_targets) DM_TRY(hipMemcpyAsync(d_targets, targets, 4ull * n_targets, hipMemcpyHostToDevice, st));
-    la3dm_reach_out d;
-    d.steps = nullptr;
-    d.target_steps = n_targets ? (uint32_t *)dm->q_out.ptr : nullptr;
-    la3dm_reach_stats s;
-    const uint32_t *d_steps = nullptr;
-    rc = reach_launch(dm, g, d_seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity, max_steps, d_targets, n_targets, d, s,
-                      d_steps);
-    if (rc != LA3DM_OK) return rc;
-    if (h.steps) DM_TRY(hipMemcpyAsync(h.steps, d_steps, 4ull * (size_t)g.total, hipMemcpyDeviceToHost, st));
-    if (n_targets) DM_TRY(hipMemcpyAsync(h.target_steps, d.target_steps, 4ull * n_targets, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (stats) *stats = s;
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return reach_query(dm, true, "la3dm_devmap_reach_host", lo3, dims3, seeds, n_seeds, pass_mask, obstacle_mask, clearance, connectivity,
+                       max_steps, targets, n_targets, out, stats, info);
 }
 
 // ---- the host side of the brick scheme that travel and clusters share (devmap_brick.h) ---------------------------------
@@ -3197,15 +3153,6 @@ static int brick_rounds(la3dm_devmap *dm, const BrickGrid &b, Launch launch, uin
 }  // extern "C++"
 
 // ---- travel: least path cost from seeds through the passable voxels of a region, with parents (devmap_travel.h) -------
-static int travel_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
-                          const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
-                          const char *who, RegionGeom &g) {
-    if (!dm) return LA3DM_ERR_ARG;
-    const std::string refusal = la3dm_region::travel_check(params, n_seeds, n_targets, seeds != nullptr, targets != nullptr, out != nullptr,
-                                                           out && out->cost, out && out->target_cost, "->");
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
-    return region_resolve(dm, lo3, dims3, la3dm_region::kTravel, true, true, who, g);
-}
 
 // The whole query on the map's stream; every pointer but `stats` is device memory.  The working storage is initialised
 // here on every call.  The rounds are queued LA3DM_TRAVEL_BATCH at a time (brick_rounds).  o.cost and o.parent may be
@@ -3275,64 +3222,44 @@ static int travel_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *
     return LA3DM_OK;
 }
 
+static int travel_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const uint32_t *seeds,
+                        uint32_t n_seeds, const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets,
+                        const la3dm_travel_out *out, la3dm_travel_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::travel_check(params, n_seeds, n_targets, seeds != nullptr, targets != nullptr, out != nullptr,
+                                                     out && out->cost, out && out->target_cost, "->")));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kTravel, true, true, who, g));
+    la3dm_travel_out o = *out;
+    const size_t n = (size_t)g.total;
+    Stage s(dm, host);
+    s.in(seeds, n_seeds);
+    s.in(targets, n_targets);
+    s.out(o.cost, n);
+    s.out(o.target_cost, n_targets);
+    s.out(o.parent, n);
+    DM_OK(s.reserve());
+    la3dm_travel_stats ts;
+    DM_OK(travel_launch(dm, g, seeds, n_seeds, *params, targets, n_targets, o, ts));   // (ends in a synchronise)
+    DM_OK(s.download());
+    if (host) DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    if (stats) *stats = ts;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
 int la3dm_devmap_travel_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
                                const la3dm_travel_params *params, const uint32_t *d_targets, uint32_t n_targets,
                                const la3dm_travel_out *d_out, la3dm_travel_stats *stats, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = travel_resolve(dm, lo3, dims3, d_seeds, n_seeds, params, d_targets, n_targets, d_out, "la3dm_devmap_travel_device", g);
-    if (rc != LA3DM_OK) return rc;
-    la3dm_travel_stats s;
-    rc = travel_launch(dm, g, d_seeds, n_seeds, *params, d_targets, n_targets, *d_out, s);   // (ends in a synchronise)
-    if (rc != LA3DM_OK) return rc;
-    if (stats) *stats = s;
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return travel_query(dm, false, "la3dm_devmap_travel_device", lo3, dims3, d_seeds, n_seeds, params, d_targets, n_targets, d_out, stats, info);
 }
 
 int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                              const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
                              la3dm_travel_stats *stats, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = travel_resolve(dm, lo3, dims3, seeds, n_seeds, params, targets, n_targets, out, "la3dm_devmap_travel_host", g);
-    if (rc != LA3DM_OK) return rc;
-    const la3dm_travel_out &h = *out;
-    hipStream_t st = dm->ctx->stream;
-    const size_t n = (size_t)g.total;
-    // seeds and targets in `cloud`; the dense cost, the costs at the targets and the parents in `q_out`
-    const size_t n_cost = h.cost ? n : 0, n_parent = h.parent ? n : 0;
-    DM_RESERVE(dm->cloud, 4ull * n_seeds + 4ull * n_targets);
-    DM_RESERVE(dm->q_out, 4ull * (n_cost + n_targets) + n_parent);
-    uint32_t *d_seeds = (uint32_t *)dm->cloud.ptr, *d_targets = d_seeds + n_seeds;
-    if (n_seeds) DM_TRY(hipMemcpyAsync(d_seeds, seeds, 4ull * n_seeds, hipMemcpyHostToDevice, st));
-    if (n_targets) DM_TRY(hipMemcpyAsync(d_targets, targets, 4ull * n_targets, hipMemcpyHostToDevice, st));
-    la3dm_travel_out d;
-    d.cost = h.cost ? (uint32_t *)dm->q_out.ptr : nullptr;
-    d.target_cost = n_targets ? (uint32_t *)dm->q_out.ptr + n_cost : nullptr;
-    d.parent = h.parent ? (uint8_t *)((uint32_t *)dm->q_out.ptr + n_cost + n_targets) : nullptr;
-    la3dm_travel_stats s;
-    rc = travel_launch(dm, g, d_seeds, n_seeds, *params, d_targets, n_targets, d, s);
-    if (rc != LA3DM_OK) return rc;
-    if (h.cost) DM_TRY(hipMemcpyAsync(h.cost, d.cost, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (n_targets) DM_TRY(hipMemcpyAsync(h.target_cost, d.target_cost, 4ull * n_targets, hipMemcpyDeviceToHost, st));
-    if (h.parent) DM_TRY(hipMemcpyAsync(h.parent, d.parent, n, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (stats) *stats = s;
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return travel_query(dm, true, "la3dm_devmap_travel_host", lo3, dims3, seeds, n_seeds, params, targets, n_targets, out, stats, info);
 }
 
 // ---- clusters: connected groups of a region's member voxels, optionally tiled (devmap_clusters.h) ----------------------
-static int clusters_resolve(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
-                            const la3dm_clusters_out *out, const char *who, RegionGeom &g) {
-    if (!dm) return LA3DM_ERR_ARG;
-    std::string refusal = la3dm_region::clusters_check(params, out);
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
-    const int rc = region_resolve(dm, lo3, dims3, la3dm_region::kClusters, true, true, who, g);
-    if (rc != LA3DM_OK) return rc;
-    refusal = la3dm_region::clusters_region_check(dims3);
-    if (!refusal.empty()) return dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
-    return LA3DM_OK;
-}
 
 // The whole query on the map's stream; every pointer of p and o is device memory.  The working storage is initialised
 // here on every call.  The rounds are queued LA3DM_CLUSTERS_BATCH at a time (brick_rounds).  n and the totals are read
@@ -3414,69 +3341,60 @@ static int clusters_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_cl
     return LA3DM_OK;
 }
 
-int la3dm_devmap_clusters_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
-                                 const la3dm_clusters_out *d_out, uint32_t *n_found, la3dm_clusters_stats *stats,
-                                 la3dm_region_info *info) {
+static int clusters_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3,
+                          const la3dm_clusters_params *params, const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats,
+                          la3dm_region_info *info) {
     RegionGeom g;
-    int rc = clusters_resolve(dm, lo3, dims3, params, d_out, "la3dm_devmap_clusters_device", g);
-    if (rc != LA3DM_OK) return rc;
+    DM_OK(refuse(dm, who, la3dm_region::clusters_check(params, out)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kClusters, true, true, who, g));
+    DM_OK(refuse(dm, who, la3dm_region::clusters_region_check(dims3)));
+    hipStream_t st = dm->ctx->stream;
     la3dm_clusters_out o;
     memset(&o, 0, sizeof(o));
-    if (d_out) o = *d_out;
-    la3dm_clusters_stats s;
+    if (out) o = *out;
+    la3dm_clusters_params p = *params;
+    if (!p.from_list) p.n_members = 0;   // (checked, not used)
+    // host pointers: the records are copied straight from the working storage (clusters_launch), not emitted
+    const la3dm_clusters_out h = o;
+    if (host) {
+        o.first = o.size = o.lo = o.hi = o.rep = nullptr;
+        o.sum = nullptr;
+    }
+    Stage s(dm, host);
+    s.in(p.members, p.n_members);
+    s.out(o.label, (size_t)g.total);
+    s.out(o.of_member, p.n_members);
+    DM_OK(s.reserve());
+    la3dm_clusters_stats cs;
     ClustersRec rec;
-    uint32_t n = 0;
-    rc = clusters_launch(dm, g, *params, o, n, s, rec);
-    if (rc != LA3DM_OK) return rc;
-    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
-    if (n_found) *n_found = n;
-    if (stats) *stats = s;
+    uint32_t found = 0;
+    DM_OK(clusters_launch(dm, g, p, o, found, cs, rec));
+    DM_OK(s.download());
+    if (host && rec.m) {
+        const size_t m = rec.m;
+        if (h.first) DM_TRY(hipMemcpyAsync(h.first, rec.first, 4ull * m, hipMemcpyDeviceToHost, st));
+        if (h.size) DM_TRY(hipMemcpyAsync(h.size, rec.size, 4ull * m, hipMemcpyDeviceToHost, st));
+        if (h.lo) DM_TRY(hipMemcpyAsync(h.lo, rec.lo, 12ull * m, hipMemcpyDeviceToHost, st));
+        if (h.hi) DM_TRY(hipMemcpyAsync(h.hi, rec.hi, 12ull * m, hipMemcpyDeviceToHost, st));
+        if (h.sum) DM_TRY(hipMemcpyAsync(h.sum, rec.sum, 24ull * m, hipMemcpyDeviceToHost, st));
+        if (h.rep) DM_TRY(hipMemcpyAsync(h.rep, rec.rep, 4ull * m, hipMemcpyDeviceToHost, st));
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    if (n_found) *n_found = found;
+    if (stats) *stats = cs;
     if (info) *info = g.info;
     return LA3DM_OK;
 }
 
+int la3dm_devmap_clusters_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
+                                 const la3dm_clusters_out *d_out, uint32_t *n_found, la3dm_clusters_stats *stats,
+                                 la3dm_region_info *info) {
+    return clusters_query(dm, false, "la3dm_devmap_clusters_device", lo3, dims3, params, d_out, n_found, stats, info);
+}
+
 int la3dm_devmap_clusters_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
                                const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info) {
-    RegionGeom g;
-    int rc = clusters_resolve(dm, lo3, dims3, params, out, "la3dm_devmap_clusters_host", g);
-    if (rc != LA3DM_OK) return rc;
-    la3dm_clusters_out h;
-    memset(&h, 0, sizeof(h));
-    if (out) h = *out;
-    hipStream_t st = dm->ctx->stream;
-    const size_t n = (size_t)g.total;
-    la3dm_clusters_params p = *params;
-    if (!p.from_list) p.n_members = 0;   // (checked, not used)
-    // the list in `cloud`; the dense label and the label per entry in `q_out`; the records are copied from the working storage
-    const size_t n_label = h.label ? n : 0, n_of = h.of_member ? p.n_members : 0;
-    DM_RESERVE(dm->cloud, 4ull * p.n_members);
-    DM_RESERVE(dm->q_out, 4ull * (n_label + n_of));
-    uint32_t *d_members = (uint32_t *)dm->cloud.ptr;
-    if (p.n_members) DM_TRY(hipMemcpyAsync(d_members, p.members, 4ull * p.n_members, hipMemcpyHostToDevice, st));
-    p.members = d_members;
-    la3dm_clusters_out d;
-    memset(&d, 0, sizeof(d));
-    d.label = h.label ? (uint32_t *)dm->q_out.ptr : nullptr;
-    d.of_member = n_of ? (uint32_t *)dm->q_out.ptr + n_label : nullptr;
-    la3dm_clusters_stats s;
-    ClustersRec rec;
-    uint32_t found = 0;
-    rc = clusters_launch(dm, g, p, d, found, s, rec);
-    if (rc != LA3DM_OK) return rc;
-    const size_t m = rec.m;
-    if (h.label) DM_TRY(hipMemcpyAsync(h.label, d.label, 4ull * n, hipMemcpyDeviceToHost, st));
-    if (n_of) DM_TRY(hipMemcpyAsync(h.of_member, d.of_member, 4ull * n_of, hipMemcpyDeviceToHost, st));
-    if (m && h.first) DM_TRY(hipMemcpyAsync(h.first, rec.first, 4ull * m, hipMemcpyDeviceToHost, st));
-    if (m && h.size) DM_TRY(hipMemcpyAsync(h.size, rec.size, 4ull * m, hipMemcpyDeviceToHost, st));
-    if (m && h.lo) DM_TRY(hipMemcpyAsync(h.lo, rec.lo, 12ull * m, hipMemcpyDeviceToHost, st));
-    if (m && h.hi) DM_TRY(hipMemcpyAsync(h.hi, rec.hi, 12ull * m, hipMemcpyDeviceToHost, st));
-    if (m && h.sum) DM_TRY(hipMemcpyAsync(h.sum, rec.sum, 24ull * m, hipMemcpyDeviceToHost, st));
-    if (m && h.rep) DM_TRY(hipMemcpyAsync(h.rep, rec.rep, 4ull * m, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (n_found) *n_found = found;
-    if (stats) *stats = s;
-    if (info) *info = g.info;
-    return LA3DM_OK;
+    return clusters_query(dm, true, "la3dm_devmap_clusters_host", lo3, dims3, params, out, n_found, stats, info);
 }
 
 int la3dm_devmap_key_bounds(la3dm_devmap *dm, int32_t lo[3], int32_t hi[3]) {
