@@ -395,6 +395,73 @@ int la3dm_devmap_block_count(la3dm_devmap *dm, uint32_t *n_blocks, uint32_t *nod
 /* keys[n_blocks]; A, B, S [n_blocks * nodes_per_block], node order = depth-major (8^d - 1)/7 + index;
  * S: bits 0-2 State (FREE 0, OCCUPIED 1, UNKNOWN 2, PRUNED 3), bit 7 = classified */
 int la3dm_devmap_download(la3dm_devmap *dm, int64_t *keys, float *A, float *B, uint8_t *S);
+/* Save and load: the map as a compact stream of its COVERING LEAVES (csrc/devmap_pack.h; the format's host code — layout,
+ * validator, host writer — is csrc/host/pack_format.h, shared with the host-mode map).
+ *
+ *   A covering leaf is a node that is not PRUNED and is either on the finest layer or has child 0 PRUNED — OcTree::is_leaf,
+ *   the image of covering_leaf over the finest cells.  The leaves of a block tile it; everything else in the pool is dead:
+ *   PRUNED children keep stale values nothing reads, the nodes above the leaves never leave their defaults.
+ *
+ *   The stream.  Little-endian; every section starts at a multiple of 16 bytes; padding bytes are zero, so two packs of
+ *   one pool are byte-identical.
+ *     header, 128 bytes = la3dm_pack_header:
+ *         0  char magic[8] = "LA3DMAP\0"          8  u32 version = 1          12  u32 header_bytes = 128
+ *        16  u32 variant (0 BGK, 1 GP, 2 BGK-LV, 3 BGK-L)   20  u32 block_depth   24  u32 nodes_per_block = (8^block_depth - 1) / 7
+ *        28  u32 flags (bit 0: BGK-LV original_size; the other bits 0)
+ *        32  u64 n_blocks       40  u64 n_leaves       48  u64 total_bytes (the whole stream, header included)
+ *        56  f32 init_A, init_B: the values of a node never written — prior_A, prior_B; GP: 0, min_ivar = 1 / max_var
+ *        64  f32 resolution, sf2, ell, free_thresh, occupied_thresh, var_thresh, prior_A, prior_B, noise, l, min_var, max_var,
+ *            max_known_var, min_W — what the map class was constructed with, 0 where the class has no such argument (GP:
+ *            var_thresh, prior_A, prior_B; noise .. max_known_var on the others; min_W except on BGK-LV).  The raw entry
+ *            points below only know the context's inverses and write min_var = 1 / max_ivar, max_var = 1 / min_ivar,
+ *            max_known_var = 1 / min_known_ivar; the map classes write their constructor arguments.
+ *       120  8 reserved bytes, zero
+ *     then, each at the next multiple of 16:
+ *       keys     i64[n_blocks]        block hash keys (x << 40 | y << 20 | z, 20 bits each), distinct, any order
+ *       leaf_off u32[n_blocks + 1]    exclusive prefix of the blocks' leaf counts; leaf_off[n_blocks] = n_leaves
+ *       mask     u32[n_blocks * W]    W = ceil(nodes_per_block / 32); bit n % 32 of word n / 32 of a block's W words is set when
+ *                                     node n (la3dm_devmap_download's depth-major numbering) is a covering leaf; bits at or
+ *                                     past nodes_per_block are clear
+ *       state    u8[n_leaves]         the pool's S byte unchanged (bits 0-2 State, bit 7 classified)
+ *       A        f32[n_leaves]        a block's leaves in ascending node number, block b's at [leaf_off[b], leaf_off[b + 1]);
+ *       B        f32[n_leaves]        values are copied bit for bit
+ *     Block order is the writer's: pool slot order from the device pool, ascending key from a host-mode map.  An empty map
+ *     is the header alone.  Per block the stream holds 12 + 4 W + 9 L bytes (L leaves, L <= 8^(block_depth - 1)) against the
+ *     8 + 9 nodes_per_block of la3dm_devmap_download: never more from block_depth 2 up.
+ *     NOT in the stream: the last scan's training data, the statistics, the options (la3dm_set_option) and the shard
+ *     configuration.
+ *
+ *   la3dm_devmap_pack_host: count kernel (S only -> leaf counts and mask words, the wave's ballots), the map's one-launch
+ *     scan over the counts, one read-back of n_leaves, emit kernel (state, A, B of the leaves to leaf_off[b] + rank), one
+ *     copy of the stream and one synchronisation.  buf = NULL: *size only.  cap < *size: LA3DM_ERR_ARG, *size set.  Changes
+ *     nothing in the pool.  A poisoned map is refused.
+ *   la3dm_devmap_unpack_host: the stream is validated on the host BEFORE the first allocation or launch (magic, version,
+ *     sizes, section extents, n_blocks * nodes_per_block < 2^32, distinct keys of 60 bits, leaf_off against the mask
+ *     popcounts, no mask bit past the end, no leaf under a leaf, the leaves tile the block, leaf states not PRUNED and known
+ *     to the variant with bits 3-6 clear, zero padding), then compared with the context: variant, block_depth,
+ *     nodes_per_block and, by bit pattern, resolution, init_A, init_B must agree — the other header floats are
+ *     informational, a loaded map may be continued with another ell.  The map must hold no blocks.  One expand kernel
+ *     writes every node of every block once — the CANONICAL pool: a leaf takes its (A, B, state); a node under a leaf
+ *     (init_A, init_B, PRUNED); every other node (init_A, init_B, UNKNOWN) — then the block table is rebuilt.  No insert and
+ *     no query reads more of a dead node than its State; la3dm_devmap_search_host at a collapsed voxel reports PRUNED with
+ *     the default values where the original pool had the values from before the collapse.
+ *   la3dm_pack_info: the validation alone (no GPU, dm-free), *out = the header.
+ *   A refusal returns LA3DM_ERR_ARG, leaves the map exactly as it was, and its text is la3dm_last_error(ctx) — for
+ *   la3dm_pack_info, which has no context, la3dm_last_error(NULL). */
+typedef struct la3dm_pack_header {
+    char magic[8];
+    uint32_t version, header_bytes, variant, block_depth, nodes_per_block, flags;
+    uint64_t n_blocks, n_leaves, total_bytes;
+    float init_A, init_B;
+    float resolution, sf2, ell, free_thresh, occupied_thresh, var_thresh, prior_A, prior_B, noise, l, min_var, max_var,
+        max_known_var, min_W;
+    uint8_t reserved[8];
+} la3dm_pack_header;
+#define LA3DM_PACK_VERSION 1u
+#define LA3DM_PACK_FLAG_LV_ORIGINAL_SIZE 0x1u
+int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *size);
+int la3dm_devmap_unpack_host(la3dm_devmap *dm, const void *buf, uint64_t size);
+int la3dm_pack_info(const void *buf, uint64_t size, la3dm_pack_header *out);
 /* BGKOctoMap::search(x, y, z) (include/bgkoctomap/bgkoctomap.h:315-319) for n query points (host pointers, packed xyz),
  * answered from the device pool without refreshing a host mirror: exists[i] = the block exists; A/B/state = the
  * finest-layer node that holds the point (a default node when the block is missing). */

@@ -193,6 +193,17 @@ int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3
  * without a mirror refresh, host-mode maps flood-fill on the CPU; the results are identical. */
 int la3dm_map_clusters(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
                        const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info);
+/* BGKOctoMap::pack / unpack / save / load: the map as the compact stream of its covering leaves (layout, validation and
+ * refusals: include/la3dm_hip.h, la3dm_devmap_pack_host).  pack: *size = the stream's bytes; buf NULL only sizes; cap < *size
+ * is an error with *size set.  A device-resident map compacts its pool on the GPU (no mirror refresh), a host-mode map
+ * writes the same stream from its blocks in ascending key order.  unpack: into an EMPTY map of the same class, block_depth,
+ * resolution and default node; the stream is validated first and a refused one leaves the map as it was (-1,
+ * la3dm_map_last_error).  save writes the stream to path + ".tmp" and renames it to path; load reads path and unpacks it.
+ * Not in the stream: the last scan's training data, the statistics, the options and the shard configuration. */
+int la3dm_map_pack(const la3dm_map *m, void *buf, uint64_t cap, uint64_t *size);
+int la3dm_map_unpack(la3dm_map *m, const void *buf, uint64_t size);
+int la3dm_map_save(const la3dm_map *m, const char *path);
+int la3dm_map_load(la3dm_map *m, const char *path);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

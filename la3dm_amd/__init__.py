@@ -8,6 +8,7 @@ from .bgkoctomap import TRAVEL_NONE, TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_M
 from .bgkoctomap import TRAVEL_MAX_ROUNDS, TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH, follow_parents  # noqa: F401
 from .bgkoctomap import CLUSTERS_NONE, CLUSTERS_MAX_CELLS, CLUSTERS_MAX_MEMBERS, CLUSTERS_MAX_ROUNDS, CLUSTERS_MAX_AXIS  # noqa: F401
 from .bgkoctomap import CLUSTERS_MAX_TILE, CLUSTERS_BRICK, CLUSTERS_INNER, CLUSTERS_BATCH  # noqa: F401
+from .bgkoctomap import pack_info, load_map, PACK_CLASSES  # noqa: F401
 from .pcd import load_pcd  # noqa: F401
 from .synth import synthetic_scan  # noqa: F401
 

@@ -135,6 +135,15 @@ class RegionInfo(C.Structure):   # la3dm_region_info
     _fields_ = [("block_key", C.c_int64), ("cell", C.c_int32 * 3), ("origin", C.c_float * 3)]
 
 
+class PackHeader(C.Structure):   # la3dm_pack_header: the first 128 bytes of a map stream
+    _fields_ = [("magic", C.c_char * 8)] + \
+               [(k, C.c_uint32) for k in ("version", "header_bytes", "variant", "block_depth", "nodes_per_block", "flags")] + \
+               [(k, C.c_uint64) for k in ("n_blocks", "n_leaves", "total_bytes")] + \
+               [(k, C.c_float) for k in ("init_A", "init_B", "resolution", "sf2", "ell", "free_thresh", "occupied_thresh", "var_thresh",
+                                         "prior_A", "prior_B", "noise", "l", "min_var", "max_var", "max_known_var", "min_W")] + \
+               [("reserved", C.c_uint8 * 8)]
+
+
 HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_destroy", "la3dm_last_error",
                "la3dm_set_option", "la3dm_get_option", "la3dm_bgk_scan_host", "la3dm_bgk_scan_device", "la3dm_gp_scan_host",
                "la3dm_gp_scan_device", "la3dm_bgklv_scan_host", "la3dm_bgklv_scan_device", "la3dm_kernel_times", "la3dm_diag_eval", "la3dm_diag_sweep",
@@ -151,7 +160,8 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_distance_device", "la3dm_devmap_frontier_host", "la3dm_devmap_frontier_device",
                "la3dm_devmap_gain_host", "la3dm_devmap_gain_device", "la3dm_devmap_reach_host",
                "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device",
-               "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device"]
+               "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device",
+               "la3dm_devmap_pack_host", "la3dm_devmap_unpack_host", "la3dm_pack_info"]
 MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
                "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
                "la3dm_map_insert_training_data", "la3dm_map_prepare", "la3dm_map_prepare_training_data",
@@ -165,7 +175,8 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth",
                "la3dm_map_raycast_many", "la3dm_map_mirror_syncs", "la3dm_map_box", "la3dm_map_columns",
                "la3dm_map_distance_field", "la3dm_map_frontier", "la3dm_map_gain", "la3dm_map_reach",
-               "la3dm_map_travel", "la3dm_map_clusters"]
+               "la3dm_map_travel", "la3dm_map_clusters", "la3dm_map_pack", "la3dm_map_unpack", "la3dm_map_save",
+               "la3dm_map_load"]
 
 _hip = None
 _map = None
@@ -273,6 +284,12 @@ def hip():
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClustersParams), C.POINTER(ClustersOut), C.POINTER(C.c_uint32),
                           C.POINTER(ClustersStats), C.POINTER(RegionInfo)]
+        L.la3dm_devmap_pack_host.restype = C.c_int
+        L.la3dm_devmap_pack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.la3dm_devmap_unpack_host.restype = C.c_int
+        L.la3dm_devmap_unpack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.la3dm_pack_info.restype = C.c_int
+        L.la3dm_pack_info.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PackHeader)]
         L.la3dm_devmap_training_data.restype = C.c_int
         L.la3dm_devmap_training_data.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         _hip = L
@@ -337,6 +354,14 @@ def maplib():
         M.la3dm_map_clusters.restype = C.c_int
         M.la3dm_map_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClustersParams), C.POINTER(ClustersOut),
                                          C.POINTER(C.c_uint32), C.POINTER(ClustersStats), C.POINTER(RegionInfo)]
+        M.la3dm_map_pack.restype = C.c_int
+        M.la3dm_map_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        M.la3dm_map_unpack.restype = C.c_int
+        M.la3dm_map_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        M.la3dm_map_save.restype = C.c_int
+        M.la3dm_map_save.argtypes = [C.c_void_p, C.c_char_p]
+        M.la3dm_map_load.restype = C.c_int
+        M.la3dm_map_load.argtypes = [C.c_void_p, C.c_char_p]
         M.la3dm_map_mirror_syncs.restype = C.c_uint64
         M.la3dm_map_mirror_syncs.argtypes = [C.c_void_p]
         M.la3dm_map_raycast.restype = C.c_uint64

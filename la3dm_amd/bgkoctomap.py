@@ -5,6 +5,7 @@ class; all work is done by libla3dm_map.so (host bookkeeping, C++) and
 libla3dm_hip.so (HIP kernels).  No Python compute path exists.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -567,6 +568,36 @@ class BGKOctoMap:
         out.update(self._region_info(info))
         return out
 
+    def pack(self):
+        """The map as the compact stream of its covering leaves (layout: include/la3dm_hip.h, la3dm_devmap_pack_host): a
+        uint8 array of header, block keys, per-block leaf offsets and node masks, and state, A, B of the leaves.  A
+        device-resident map compacts its pool on the GPU before it crosses PCIe (no host mirror refresh; blocks in pool
+        order); a host-mode map writes the same stream from its blocks (ascending key).  Not in the stream: the last
+        scan's training data, the statistics, the options and the shard configuration."""
+        size = C.c_uint64(0)
+        self._chk(self._M.la3dm_map_pack(self._h, None, 0, C.byref(size)))
+        buf = np.empty(int(size.value), np.uint8)
+        self._chk(self._M.la3dm_map_pack(self._h, buf.ctypes.data, buf.size, C.byref(size)))
+        return buf[:int(size.value)]
+
+    def unpack(self, stream):
+        """Load a stream of pack() (bytes or a uint8 array, of either writer) into this EMPTY map: same class, block_depth,
+        resolution and default node, the other parameters may differ.  Validated first; a refused stream raises
+        RuntimeError and leaves the map as it was."""
+        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
+                                   np.uint8).reshape(-1)
+        self._chk(self._M.la3dm_map_unpack(self._h, buf.ctypes.data if buf.size else None, buf.size))
+        return self
+
+    def save(self, path):
+        """pack() written to path + ".tmp" and renamed to path"""
+        self._chk(self._M.la3dm_map_save(self._h, os.fsencode(path)))
+
+    def load(self, path):
+        """unpack() of the file at path"""
+        self._chk(self._M.la3dm_map_load(self._h, os.fsencode(path)))
+        return self
+
     def mirror_syncs(self):
         """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
         return int(self._M.la3dm_map_mirror_syncs(self._h))
@@ -785,6 +816,48 @@ class BGKLVOctoMap(BGKOctoMap):
 
     def lv_commit(self):
         self._chk(self._M.la3dm_map_lv_commit(self._h))
+
+
+PACK_CLASSES = ("BGKOctoMap", "GPOctoMap", "BGKLVOctoMap", "BGKLOctoMap")   # by the header's variant
+
+
+def pack_info(stream_or_path):
+    """The validated header of a map stream (bytes, a uint8 array, or the path of a saved map) as a dict: the fields of
+    la3dm_pack_header (include/la3dm_hip.h) plus `cls`, the name of the map class.  No GPU is needed; a stream that fails
+    validation raises RuntimeError."""
+    if isinstance(stream_or_path, (str, os.PathLike)):
+        stream_or_path = np.fromfile(stream_or_path, np.uint8)
+    if isinstance(stream_or_path, (bytes, bytearray, memoryview)):
+        stream_or_path = np.frombuffer(stream_or_path, np.uint8)
+    buf = np.ascontiguousarray(stream_or_path, np.uint8).reshape(-1)
+    h = _lib.PackHeader()
+    L = _lib.hip()
+    if L.la3dm_pack_info(buf.ctypes.data if buf.size else None, buf.size, C.byref(h)) != 0:
+        raise RuntimeError(L.la3dm_last_error(None).decode())
+    out = {k: getattr(h, k) for k, _ in _lib.PackHeader._fields_ if k not in ("magic", "reserved")}
+    out["magic"] = bytes(h.magic)
+    out["cls"] = PACK_CLASSES[h.variant]
+    return out
+
+
+def load_map(path, device=0, device_resident=True):
+    """The map saved at `path`: an object of the class the stream's header names, constructed with the header's parameters on
+    `device` (-1: a host-mode map without a GPU), device-resident or not, with the stream loaded."""
+    h = pack_info(path)
+    f = lambda k: float(np.float32(h[k]))   # noqa: E731
+    common = dict(resolution=f("resolution"), block_depth=int(h["block_depth"]), sf2=f("sf2"), ell=f("ell"),
+                  free_thresh=f("free_thresh"), occupied_thresh=f("occupied_thresh"), device=device)
+    if h["variant"] == 1:
+        m = GPOctoMap(noise=f("noise"), l=f("l"), min_var=f("min_var"), max_var=f("max_var"), max_known_var=f("max_known_var"), **common)
+    else:
+        common.update(var_thresh=f("var_thresh"), prior_A=f("prior_A"), prior_B=f("prior_B"))
+        if h["variant"] == 2:
+            m = BGKLVOctoMap(original_size=bool(h["flags"] & 1), min_W=f("min_W"), **common)
+        else:
+            m = (BGKLOctoMap if h["variant"] == 3 else BGKOctoMap)(**common)
+    if device >= 0 and m.is_device_resident() != bool(device_resident):
+        m.set_device_resident(bool(device_resident))
+    return m.load(path)
 
 
 def follow_parents(parent, dims, index):

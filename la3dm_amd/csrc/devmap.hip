@@ -34,6 +34,8 @@
 #include "devmap_reach.h"
 #include "devmap_travel.h"
 #include "devmap_clusters.h"
+#include "devmap_pack.h"
+#include "host/pack_format.h"
 
 using namespace la3dm_dev;
 
@@ -88,6 +90,8 @@ struct la3dm_devmap {
     Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
     Arena clusters_work;          // clusters: two brick-major label buffers, side / active per brick, the round counts, sizes, flags, numbers (devmap_clusters.h)
     Arena clusters_rec;           // clusters: the records of the clusters written (sums, keys, boxes, first, size, rep)
+    Arena pack_stream, pack_counts;   // save / load: the stream as it leaves or enters the device; the blocks' leaf counts (devmap_pack.h)
+    la3dm_pack_header pack_hdr;   // the header of the stream being packed (the source of an asynchronous copy)
     Arena c_flag, c_weight, c_scan, t_key0, t_key1, t_ent0, t_ent1, t_blockkey, t_center, t_nbr, t_slot, t_slot0;
     Arena nleaf, leaf_off, leaf_key, leaf_alpha, leaf_beta, leaf_state, leaf_node;
     Arena l_ray_idx, l_rays, l_rows, l_rows_off, l_rflag, l_rscan;  // BGKLOctoMap: beam of every sample, beam segments, training rows
@@ -683,7 +687,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -2342,6 +2346,117 @@ inline uint32_t float_bits(float v) {
 static int refuse(la3dm_devmap *dm, const char *who, const std::string &refusal) {
     if (!dm) return LA3DM_ERR_ARG;
     return refusal.empty() ? LA3DM_OK : dm_fail(dm, LA3DM_ERR_ARG, std::string(who) + ": " + refusal);
+}
+
+// ---- save / load (contract: include/la3dm_hip.h; kernels: devmap_pack.h; format and validator: host/pack_format.h) ----
+// The pool's covering leaves as the stream.  Launch chain: dm_pack_count (S only -> leaf counts + mask words), the one-launch
+// scan over n_blocks + 1 counts straight into the stream's leaf_off section, one read-back of n_leaves, dm_pack_emit, one copy.
+// The stream arena is reserved for the most leaves the blocks can have (every finest cell: 64 / 73 of the raw pool at
+// block_depth 3) before the count is known, so nothing the count launch wrote has to move.
+int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *size) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm || !size) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_pack_host";
+    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    la3dm_ctx *ctx = dm->ctx;
+    const uint64_t nb = dm->n_blocks;
+    if (nb == 0) {   // an empty map is the header alone: no launch
+        *size = la3dm_pack::kHeaderBytes;
+        if (!buf) return LA3DM_OK;
+        if (cap < *size) return refuse(dm, who, "the buffer is smaller than the stream");
+        const la3dm_pack_header h = la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, 0, 0);
+        memcpy(buf, &h, sizeof(h));
+        return LA3DM_OK;
+    }
+    DM_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t npb = dm->npb;
+    const la3dm_pack::Layout worst = la3dm_pack::layout(nb, nb * dm->ncell, npb);
+    DM_RESERVE(dm->pack_stream, worst.total);
+    DM_RESERVE(dm->pack_counts, 4ull * (nb + 1));
+    uint8_t *arena = (uint8_t *)dm->pack_stream.ptr;
+    uint32_t *counts = (uint32_t *)dm->pack_counts.ptr, *leaf_off = (uint32_t *)(arena + worst.leaf_off), *mask = (uint32_t *)(arena + worst.mask);
+    hipLaunchKernelGGL(dm_pack_count, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
+                       (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask);
+    DM_TRY(hipGetLastError());
+    DM_OK(exclusive_scan(dm, counts, leaf_off, (uint32_t)nb + 1u));
+    uint32_t n_leaves = 0, err = 0;
+    DM_TRY(hipMemcpyAsync(&n_leaves, leaf_off + nb, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (err & kScanErrStuck) {
+        dm->poisoned = true;
+        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
+    }
+    if (n_leaves < nb || n_leaves > nb * dm->ncell) return dm_fail(dm, LA3DM_ERR_HIP, "la3dm_devmap_pack_host: the pool's leaves do not tile its blocks (internal error)");
+    const la3dm_pack::Layout l = la3dm_pack::layout(nb, n_leaves, npb);
+    *size = l.total;
+    if (!buf) return LA3DM_OK;
+    if (cap < l.total) return refuse(dm, who, "the buffer is smaller than the stream");
+    dm->pack_hdr = la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, nb, n_leaves);
+    DM_TRY(hipMemcpyAsync(arena, &dm->pack_hdr, sizeof(dm->pack_hdr), hipMemcpyHostToDevice, st));
+    DM_TRY(hipMemcpyAsync(arena + l.keys, dm->blk_key, 8ull * nb, hipMemcpyDeviceToDevice, st));
+    PackGaps gaps;
+    const uint64_t ends[6][2] = {{l.keys + 8ull * nb, l.leaf_off}, {l.leaf_off + 4ull * (nb + 1), l.mask}, {l.mask + 4ull * nb * l.W, l.state},
+                                 {l.state + n_leaves, l.A},         {l.A + 4ull * n_leaves, l.B},           {l.B + 4ull * n_leaves, l.total}};
+    for (int g = 0; g < 6; ++g) {
+        gaps.at[g] = ends[g][0];
+        gaps.len[g] = (uint32_t)(ends[g][1] - ends[g][0]);
+    }
+    hipLaunchKernelGGL(dm_pack_emit, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
+                       (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
+                       (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipMemcpyAsync(buf, arena, l.total, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+// The stream into an empty map: validate (host, before anything is allocated or launched), upload, dm_unpack_expand (the
+// canonical pool), block keys, table rebuild; then the host-side facts an insert caches, as a finished insert leaves them —
+// except the counter block, which the next insert's dm_begin sets up from n_blocks (counters_clean = false).
+int la3dm_devmap_unpack_host(la3dm_devmap *dm, const void *buf, uint64_t size) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_unpack_host";
+    la3dm_ctx *ctx = dm->ctx;
+    if (dm->n_blocks != 0) return refuse(dm, who, "the map already holds blocks (a stream is loaded into an empty map)");
+    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    la3dm_pack_header h;
+    const std::string bad = la3dm_pack::validate(buf, size, &h);
+    if (!bad.empty()) return refuse(dm, who, bad);
+    const std::string other = la3dm_pack::mismatch(h, la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, 0, 0));
+    if (!other.empty()) return refuse(dm, who, other);
+    const bool lv_original_size = h.variant == 2u ? (h.flags & LA3DM_PACK_FLAG_LV_ORIGINAL_SIZE) != 0 : dm->lv_original_size;
+    if (h.n_blocks == 0) {
+        dm->lv_original_size = lv_original_size;
+        return LA3DM_OK;
+    }
+    DM_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint64_t nb = h.n_blocks;
+    const uint32_t npb = dm->npb;
+    const la3dm_pack::Layout l = la3dm_pack::layout(nb, h.n_leaves, npb);
+    DM_OK(grow_pool(dm, nb));
+    DM_OK(grow_table(dm, nb));
+    DM_RESERVE(dm->pack_stream, l.total);
+    uint8_t *arena = (uint8_t *)dm->pack_stream.ptr;
+    DM_TRY(hipMemcpyAsync(arena, buf, l.total, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dm_unpack_expand, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * 8u * l.W, st, dm->A, dm->B, dm->S,
+                       (uint32_t)nb, npb, dm->depth, (const uint32_t *)(arena + l.leaf_off), (const uint32_t *)(arena + l.mask),
+                       (const uint8_t *)(arena + l.state), (const float *)(arena + l.A), (const float *)(arena + l.B), dm->init_A, dm->init_B);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipMemcpyAsync(dm->blk_key, arena + l.keys, 8ull * nb, hipMemcpyDeviceToDevice, st));
+    DM_TRY(hipMemsetAsync(dm->tab_key, 0xFF, 8ull * dm->tab_cap, st));
+    hipLaunchKernelGGL(dm_table_rebuild, dim3(cdiv(nb, 256)), dim3(256), 0, st, dm->blk_key, (uint32_t)nb, dm->tab_key, dm->tab_val,
+                       dm->tab_cap - 1);
+    DM_TRY(hipGetLastError());
+    DM_TRY(hipStreamSynchronize(st));   // (buf is the caller's again)
+    dm->n_blocks = (uint32_t)nb;
+    dm->lv_original_size = lv_original_size;
+    dm->insert_into_empty = false;
+    dm->counters_clean = false;
+    return LA3DM_OK;
 }
 
 int la3dm_devmap_search_host(la3dm_devmap *dm, const float *xyz, uint32_t n, uint8_t *exists, float *A, float *B,

@@ -13,6 +13,7 @@
 //   Occupancy                          src/bgkoctomap/bgkoctree_node.cpp:15-44
 #include "bgkoctomap.h"
 #include "region_contract.h"
+#include "pack_format.h"
 
 #include <algorithm>
 #include <parallel/algorithm>
@@ -438,6 +439,7 @@ BGKOctoMap::BGKOctoMap(int variant_, float resolution_, unsigned short block_dep
                        const GPParams *gp, int device)
     : resolution(resolution_), block_size((float)pow(2, block_depth_ - 1) * resolution_), block_depth(block_depth_),
       ctx(nullptr), scan_flags(0), variant(variant_), train_max_n(0), train_sum_n2(0) {
+    ctor_gp = gp != nullptr ? *gp : GPParams{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, true};
     Block::resolution = resolution;
     Block::size = block_size;
     Block::key_loc_map = init_key_loc_map(resolution, block_depth);
@@ -653,6 +655,113 @@ void BGKOctoMap::sync_mirror() const {
     }
     mirror_dirty = false;
     ++mirror_sync_count;
+}
+
+// ---- save / load (include/la3dm_hip.h, la3dm_devmap_pack_host; the format's host code: pack_format.h) ----
+namespace {
+la3dm_params stream_params(const la3dm_params &created, float resolution, unsigned short block_depth) {
+    la3dm_params p = created;
+    p.resolution = resolution;
+    p.block_depth = block_depth;
+    return p;
+}
+}  // namespace
+
+std::vector<uint8_t> BGKOctoMap::pack() const {
+    bind();
+    const float gp3[3] = {ctor_gp.min_var, ctor_gp.max_var, ctor_gp.max_known_var};
+    const float *exact = variant == 1 ? gp3 : nullptr;
+    if (dmap != nullptr) {   // compacted on the GPU; the mirror is not touched
+        uint64_t size = 0;
+        if (la3dm_devmap_pack_host(dmap, nullptr, 0, &size) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::pack: ") + la3dm_last_error(ctx));
+        std::vector<uint8_t> out(size);
+        if (la3dm_devmap_pack_host(dmap, out.data(), size, &size) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::pack: ") + la3dm_last_error(ctx));
+        if (exact) std::memcpy(out.data() + offsetof(la3dm_pack_header, min_var), exact, sizeof(gp3));   // (the context only knows the inverses)
+        return out;
+    }
+    const la3dm_pack_header proto =
+        la3dm_pack::make_header(stream_params(create_params, resolution, block_depth), mine.original_size, exact, 0, 0);
+    std::vector<int64_t> keys;
+    keys.reserve(block_arr.size());
+    for (const auto &kv : block_arr) keys.push_back(kv.first);
+    std::sort(keys.begin(), keys.end());
+    return la3dm_pack::write(proto, keys, [&](uint64_t b, float *A, float *B, uint8_t *S) {
+        const OcTreeNode *slab = block_arr.find(keys[b])->second->slab;   // (retired layers keep their PRUNED nodes in the slab)
+        for (uint32_t n = 0; n < proto.nodes_per_block; ++n) {
+            A[n] = slab[n].m_A;
+            B[n] = slab[n].m_B;
+            S[n] = (uint8_t)((uint8_t)slab[n].state | (slab[n].classified ? 0x80u : 0u));
+        }
+    });
+}
+
+uint64_t BGKOctoMap::packed_size() const {
+    bind();
+    if (dmap == nullptr) return pack().size();
+    uint64_t size = 0;
+    if (la3dm_devmap_pack_host(dmap, nullptr, 0, &size) != LA3DM_OK)
+        throw std::runtime_error(std::string("BGKOctoMap::pack: ") + la3dm_last_error(ctx));
+    return size;
+}
+
+void BGKOctoMap::unpack(const void *stream, size_t size) {
+    bind();
+    la3dm_pack_header h;
+    if (dmap != nullptr) {
+        if (la3dm_devmap_unpack_host(dmap, stream, size) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::unpack: ") + la3dm_last_error(ctx));
+        std::memcpy(&h, stream, sizeof(h));
+        for (auto &kv : block_arr) delete kv.second;
+        block_arr.clear();
+        mirror_dirty = true;
+    } else {
+        if (!block_arr.empty())
+            throw std::runtime_error("BGKOctoMap::unpack: the map already holds blocks (a stream is loaded into an empty map)");
+        std::string bad = la3dm_pack::validate(stream, size, &h);
+        if (bad.empty())
+            bad = la3dm_pack::mismatch(h, la3dm_pack::make_header(stream_params(create_params, resolution, block_depth), mine.original_size, nullptr, 0, 0));
+        if (!bad.empty()) throw std::runtime_error("BGKOctoMap::unpack: " + bad);
+        const la3dm_pack::Layout l = la3dm_pack::layout(h.n_blocks, h.n_leaves, h.nodes_per_block);
+        std::vector<float> A(h.nodes_per_block), B(h.nodes_per_block);
+        std::vector<uint8_t> S(h.nodes_per_block);
+        for (uint64_t b = 0; b < h.n_blocks; ++b) {
+            int64_t key;
+            std::memcpy(&key, (const uint8_t *)stream + l.keys + 8 * b, 8);
+            la3dm_pack::expand_block((const uint8_t *)stream, h, l, b, A.data(), B.data(), S.data());
+            Block *blk = new Block(hash_key_to_block(key));
+            blk->load_nodes(A.data(), B.data(), S.data(), h.nodes_per_block);
+            block_arr.emplace(key, blk);
+        }
+    }
+    if (h.variant == 2u) {   // BGK-LV: whether export_cells keeps collapsed leaves at their size travels with the map
+        mine.original_size = (h.flags & LA3DM_PACK_FLAG_LV_ORIGINAL_SIZE) != 0;
+        OcTreeNode::original_size = mine.original_size;
+    }
+}
+
+void BGKOctoMap::save(const std::string &path) const {
+    const std::vector<uint8_t> bytes = pack();
+    const std::string tmp = path + ".tmp";
+    {
+        std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+        if (!out) throw std::runtime_error("BGKOctoMap::save: cannot open " + tmp);
+        out.write((const char *)bytes.data(), (std::streamsize)bytes.size());
+        out.flush();
+        if (!out) throw std::runtime_error("BGKOctoMap::save: cannot write " + tmp);
+    }
+    if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("BGKOctoMap::save: cannot rename " + tmp + " to " + path);
+}
+
+void BGKOctoMap::load(const std::string &path) {
+    std::ifstream in(path, std::ios::binary | std::ios::ate);
+    if (!in) throw std::runtime_error("BGKOctoMap::load: cannot open " + path);
+    const std::streamsize size = in.tellg();
+    std::vector<uint8_t> bytes((size_t)std::max<std::streamsize>(size, 0));
+    in.seekg(0);
+    if (!bytes.empty() && !in.read((char *)bytes.data(), size)) throw std::runtime_error("BGKOctoMap::load: cannot read " + path);
+    unpack(bytes.data(), bytes.size());
 }
 
 std::vector<float> BGKOctoMap::device_training_data() const {

@@ -24,6 +24,7 @@
 #include <cstdint>
 #include <fstream>
 #include <ostream>
+#include <string>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -502,6 +503,21 @@ public:
     /// refresh); a host-mode map flood-fills box's classes: that form is the definition, and both give the same integers.
     void clusters(const float *lo3, const uint32_t *dims3, const la3dm_clusters_params &p, const la3dm_clusters_out *out,
                   uint32_t *n_found = nullptr, la3dm_clusters_stats *stats = nullptr, la3dm_region_info *info = nullptr) const;
+    /// Save and load (stream layout and contract: include/la3dm_hip.h, la3dm_devmap_pack_host): the map as the compact stream
+    /// of its covering leaves — block keys, one mask bit per node, and state, A, B of the leaves; not the last scan's training
+    /// data, the statistics, the options or the shard configuration.  pack() of a device-resident map compacts the pool on
+    /// the GPU before it crosses PCIe (blocks in pool slot order; no mirror refresh); a host-mode map, device = -1 included,
+    /// writes the same stream from its blocks (ascending key).  unpack() loads a stream of either writer into an EMPTY map
+    /// of the same class, block_depth, resolution and default node (the other parameters are informational: a loaded map may
+    /// be continued with another ell): every node that is not a leaf becomes (default values, PRUNED under a leaf, UNKNOWN
+    /// above).  A device-resident map expands the stream on the GPU; its mirror is emptied and marked stale.  The stream is
+    /// validated before anything is touched; a refusal throws std::runtime_error and leaves the map as it was.  save() writes
+    /// pack() to path + ".tmp" and renames it to path; load() reads the file and calls unpack().
+    std::vector<uint8_t> pack() const;
+    uint64_t packed_size() const;   ///< pack().size(); on a device-resident map without the gather and the copy
+    void unpack(const void *stream, size_t size);
+    void save(const std::string &path) const;
+    void load(const std::string &path);
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {
@@ -572,6 +588,7 @@ protected:
     /// leaf that covers global voxel (gx, gy, gz), null where the map has no block there
     const OcTreeNode *covering_leaf_at(uint32_t gx, uint32_t gy, uint32_t gz, BlockHashKey &have, const Block *&b, unsigned &d) const;
     la3dm_params create_params;   // what the context was created with (lut_xyz is re-pointed on use)
+    GPParams ctor_gp;             // the variant-specific constructor arguments as given (the stream's header carries them)
     void create_context();        // la3dm_create + the device-resident pool from create_params and the current statics
     void reconfigure(float resolution, unsigned short depth);
     struct ShardCfg {

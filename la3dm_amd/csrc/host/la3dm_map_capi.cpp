@@ -444,6 +444,32 @@ int la3dm_map_clusters(const la3dm_map *m, const float *lo3, const uint32_t *dim
         return 0;)
 }
 
+int la3dm_map_pack(const la3dm_map *m, void *buf, uint64_t cap, uint64_t *size) {
+    GUARD(
+        if (size == nullptr) throw std::invalid_argument("BGKOctoMap::pack: size is NULL");
+        if (buf == nullptr) {
+            *size = m->map->packed_size();
+            return 0;
+        }
+        const std::vector<uint8_t> bytes = m->map->pack();
+        *size = bytes.size();
+        if (cap < bytes.size()) throw std::invalid_argument("BGKOctoMap::pack: the buffer is smaller than the stream");
+        std::memcpy(buf, bytes.data(), bytes.size());
+        return 0;)
+}
+
+int la3dm_map_unpack(la3dm_map *m, const void *buf, uint64_t size) {
+    GUARD(m->map->unpack(buf, (size_t)size); return 0;)
+}
+
+int la3dm_map_save(const la3dm_map *m, const char *path) {
+    GUARD(if (path == nullptr) throw std::invalid_argument("BGKOctoMap::save: path is NULL"); m->map->save(path); return 0;)
+}
+
+int la3dm_map_load(la3dm_map *m, const char *path) {
+    GUARD(if (path == nullptr) throw std::invalid_argument("BGKOctoMap::load: path is NULL"); m->map->load(path); return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);

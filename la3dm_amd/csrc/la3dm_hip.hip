@@ -24,6 +24,7 @@
 using namespace la3dm_dev;
 
 #include "la3dm_ctx.h"
+#include "host/pack_format.h"
 
 static thread_local std::string g_create_error;
 
@@ -255,6 +256,14 @@ int la3dm_device_count(void) {
 const char *la3dm_version(void) { return "la3dm_hip 0.1 (gfx950)"; }
 
 const char *la3dm_last_error(const la3dm_ctx *ctx) { return ctx ? ctx->err.c_str() : g_create_error.c_str(); }
+
+// the stream's validation alone (host/pack_format.h; what la3dm_devmap_unpack_host and the host-mode map run before they load)
+int la3dm_pack_info(const void *buf, uint64_t size, la3dm_pack_header *out) {
+    const std::string bad = la3dm_pack::validate(buf, size, out);
+    if (bad.empty()) return LA3DM_OK;
+    g_create_error = "la3dm_pack_info: " + bad;
+    return LA3DM_ERR_ARG;
+}
 
 int la3dm_create(const la3dm_params *params, la3dm_ctx **out) {
     if (!params || !out) {
