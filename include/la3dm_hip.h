@@ -462,6 +462,46 @@ typedef struct la3dm_pack_header {
 int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *size);
 int la3dm_devmap_unpack_host(la3dm_devmap *dm, const void *buf, uint64_t size);
 int la3dm_pack_info(const void *buf, uint64_t size, la3dm_pack_header *out);
+/* Merge: a map stream fused into a LIVE map on the GPU (csrc/devmap_merge.h; the rule per block on flat arrays, which the
+ * host-mode map runs, is csrc/host/merge_block.h — both give the same bytes).  For maps of class BGKOctoMap (variant 0) and
+ * BGKLOctoMap (variant 3), whose nodes are a pair of evidence sums over a shared prior.
+ *
+ *   The stream is validated and compared with the context exactly as la3dm_devmap_unpack_host does.  The map may hold any
+ *   number of blocks.  For every block key k of the stream:
+ *     - a block the map lacks is created, conceptually all-default (every node init_A, init_B, UNKNOWN, no prune);
+ *     - for every finest-layer cell c, with (A2, B2, S2) the stream's covering leaf of c and (A1, B1, S1) the map's (S = the
+ *       whole byte, bit 7 included), the cell becomes
+ *         kept    (A1, B1, S1)            if A2, B2 are init_A, init_B bit for bit: the incoming leaf carries no evidence
+ *         copied  (A2, B2, S2) verbatim   else if A1, B1 are init_A, init_B bit for bit
+ *         fused   A = A1 + (A2 - init_A), B = B1 + (B2 - init_B) in fp32 in that association; state = Occupancy::update's
+ *                 rule with IEEE divisions — var = (A B) / ((s s)(s + 1)), s = A + B; var > var_thresh: UNKNOWN; else
+ *                 p = A / s > occupied_thresh: OCCUPIED, p < free_thresh: FREE, else UNKNOWN — with bit 7 set;
+ *     - the block is pruned by OcTree::prune's rule, bottom up: eight siblings that are all leaves of one state other than
+ *       UNKNOWN collapse into their parent, which takes child 0's A, B and WHOLE S byte (an untouched coarse leaf that is
+ *       expanded and collapsed again comes back bit-identical; nothing depends on dead nodes' stale bytes);
+ *     - the block is written in unpack's canonical form, every node once: leaves their values, nodes under a leaf
+ *       (init_A, init_B, PRUNED), nodes above the leaves (init_A, init_B, UNKNOWN).
+ *   Blocks the stream does not name are neither read nor written.  New blocks take pool slots n_blocks, n_blocks + 1, ... in
+ *   STREAM ORDER; apart from those slot numbers the result does not depend on the order of the stream's blocks, so replicas
+ *   that merge one stream stay identical and two packs of the result are byte-identical.  NaN payload bits of a fused
+ *   sum are not part of the contract.
+ *
+ *   Refusals — LA3DM_ERR_ARG, the text through la3dm_last_error, the map exactly as it was: a stream the validator
+ *   rejects; a mismatch with the context; a GPOctoMap or BGKLVOctoMap map (ivar clamping and UNCERTAIN make their fusion
+ *   another rule); a poisoned map; a block_depth whose staging does not fit a compute unit's LDS (5: block_depth 1 to 4
+ *   run); a pool that would pass 2^32 nodes.  All but the last come before the first allocation or launch; the last is
+ *   known once the find launch has counted the blocks to create, before the pool is touched.
+ *   Launch chain: one upload, dm_merge_find (table probe per stream block), the map's one-launch scan over the "new" flags,
+ *   one read-back of the number created, grow_pool / grow_table, dm_merge_insert (keys of the new blocks), dm_merge_fuse (one
+ *   wave per block: both trees climbed per finest cell, prune in LDS, every node written once), one read-back of the cell
+ *   counters.  An empty stream (the header alone) is a no-op with zero stats.  Afterwards the host-side facts are as unpack
+ *   leaves them; a following insert works on the merged pool. */
+typedef struct la3dm_merge_stats {
+    uint64_t n_blocks;   /* blocks of the stream */
+    uint64_t n_created;
+    uint64_t cells_kept, cells_copied, cells_fused;
+} la3dm_merge_stats;
+int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la3dm_merge_stats *stats /* may be NULL */);
 /* BGKOctoMap::search(x, y, z) (include/bgkoctomap/bgkoctomap.h:315-319) for n query points (host pointers, packed xyz),
  * answered from the device pool without refreshing a host mirror: exists[i] = the block exists; A/B/state = the
  * finest-layer node that holds the point (a default node when the block is missing). */

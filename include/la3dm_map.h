@@ -204,6 +204,13 @@ int la3dm_map_pack(const la3dm_map *m, void *buf, uint64_t cap, uint64_t *size);
 int la3dm_map_unpack(la3dm_map *m, const void *buf, uint64_t size);
 int la3dm_map_save(const la3dm_map *m, const char *path);
 int la3dm_map_load(la3dm_map *m, const char *path);
+/* BGKOctoMap::merge / BGKLOctoMap::merge: a stream fused into a map that may hold blocks (the rule per finest cell — kept,
+ * copied, fused —, the prune, the canonical form and the refusals: include/la3dm_hip.h, la3dm_devmap_merge_host).  A
+ * device-resident map fuses on the GPU pool (its mirror is marked stale), a host-mode map runs csrc/host/merge_block.h over
+ * its blocks; both leave the same bytes.  stats may be NULL.  merge_file reads path and merges it.  A refused stream leaves
+ * the map as it was (-1, la3dm_map_last_error). */
+int la3dm_map_merge(la3dm_map *m, const void *buf, uint64_t size, la3dm_merge_stats *stats);
+int la3dm_map_merge_file(la3dm_map *m, const char *path, la3dm_merge_stats *stats);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

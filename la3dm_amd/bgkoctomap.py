@@ -598,6 +598,33 @@ class BGKOctoMap:
         self._chk(self._M.la3dm_map_load(self._h, os.fsencode(path)))
         return self
 
+    def merge(self, stream_or_map):
+        """Fuse a stream of pack() (bytes or a uint8 array) or another map of this map's class (packed first) into this
+        map, which may hold blocks (contract: include/la3dm_hip.h, la3dm_devmap_merge_host).  Per finest cell of every
+        block the stream names: kept where the incoming leaf is the default node, copied where this map's is, else the
+        evidence sums are added and the state re-derived; the blocks are pruned and written in unpack()'s canonical form,
+        new blocks appended in stream order.  BGKOctoMap and BGKLOctoMap only.  A device-resident map fuses on the GPU
+        pool, a host-mode map on the CPU: the same bytes.  Validated first; a refused stream raises RuntimeError and
+        leaves the map as it was.  Returns dict(n_blocks, n_created, cells_kept, cells_copied, cells_fused)."""
+        if isinstance(stream_or_map, BGKOctoMap):
+            if type(stream_or_map) is not type(self):
+                raise TypeError(f"merge: a {type(stream_or_map).__name__} is not merged into a {type(self).__name__}")
+            if stream_or_map is self:
+                raise ValueError("merge: a map is not merged into itself")
+            stream_or_map = stream_or_map.pack()
+        stream = stream_or_map
+        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
+                                   np.uint8).reshape(-1)
+        stats = _lib.MergeStats()
+        self._chk(self._M.la3dm_map_merge(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(stats)))
+        return {k: int(getattr(stats, k)) for k, _ in _lib.MergeStats._fields_}
+
+    def merge_file(self, path):
+        """merge() of the file at path (a file save() wrote)"""
+        stats = _lib.MergeStats()
+        self._chk(self._M.la3dm_map_merge_file(self._h, os.fsencode(path), C.byref(stats)))
+        return {k: int(getattr(stats, k)) for k, _ in _lib.MergeStats._fields_}
+
     def mirror_syncs(self):
         """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
         return int(self._M.la3dm_map_mirror_syncs(self._h))

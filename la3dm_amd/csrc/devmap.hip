@@ -35,6 +35,7 @@
 #include "devmap_travel.h"
 #include "devmap_clusters.h"
 #include "devmap_pack.h"
+#include "devmap_merge.h"
 #include "host/pack_format.h"
 
 using namespace la3dm_dev;
@@ -2456,6 +2457,106 @@ int la3dm_devmap_unpack_host(la3dm_devmap *dm, const void *buf, uint64_t size) {
     dm->lv_original_size = lv_original_size;
     dm->insert_into_empty = false;
     dm->counters_clean = false;
+    return LA3DM_OK;
+}
+
+// A stream fused into the live map (contract: include/la3dm_hip.h; kernels: devmap_merge.h).  Every refusal comes before the
+// first allocation or launch, but one: whether the pool would pass 2^32 nodes is known only after dm_merge_find has counted
+// the blocks to create — it writes scratch alone, and the refusal comes before grow_pool.
+// Launch chain: one upload, dm_merge_find, the one-launch scan over the "new" flags, one read-back of the number created,
+// grow_pool / grow_table, dm_merge_insert, dm_merge_fuse, one read-back of the three cell counters.
+int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la3dm_merge_stats *stats) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_merge_host";
+    la3dm_ctx *ctx = dm->ctx;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (ctx->p.variant != 0 && ctx->p.variant != 3)
+        return refuse(dm, who, "merge is defined for BGKOctoMap (variant 0) and BGKLOctoMap (variant 3) maps; GPOctoMap and BGKLVOctoMap fuse by other rules");
+    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    la3dm_pack_header h;
+    const std::string bad = la3dm_pack::validate(buf, size, &h);
+    if (!bad.empty()) return refuse(dm, who, bad);
+    const std::string other = la3dm_pack::mismatch(h, la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, 0, 0));
+    if (!other.empty()) return refuse(dm, who, other);
+    if (!merge_lds_fits(dm->depth))
+        return refuse(dm, who, "block_depth " + std::to_string(dm->depth) + " needs " + std::to_string(kPackWaves * merge_lds_stride(dm->depth)) +
+                                   " bytes of LDS per workgroup, a compute unit has " + std::to_string(kMergeLdsPerCu) + " (merge runs at block_depth 1 to 4)");
+    if (h.n_blocks == 0) return LA3DM_OK;
+    const uint64_t nb = h.n_blocks, cap_max = la3dm_pack::kPoolNodeLimit / dm->npb;
+    const char *too_big = "the merged pool would pass 2^32 nodes";
+    DM_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t npb = dm->npb, n_old = dm->n_blocks;
+    const la3dm_pack::Layout l = la3dm_pack::layout(nb, h.n_leaves, npb);
+    DM_RESERVE(dm->pack_stream, l.total);
+    DM_RESERVE(dm->pack_counts, 4ull * (3 * nb + 2) + 8 + 8ull * kMergeCntWords);
+    uint8_t *arena = (uint8_t *)dm->pack_stream.ptr;
+    uint32_t *slot = (uint32_t *)dm->pack_counts.ptr, *flag = slot + nb, *off = flag + nb + 1;
+    unsigned long long *cells = (unsigned long long *)(((uintptr_t)(off + nb + 1) + 7u) & ~(uintptr_t)7u);
+    const long long *keys = (const long long *)(arena + l.keys);
+    DM_TRY(hipMemcpyAsync(arena, buf, l.total, hipMemcpyHostToDevice, st));
+    DM_TRY(hipMemsetAsync(cells, 0, 8ull * kMergeCntWords, st));
+    const PoolView pool{dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->A, dm->B, dm->S, npb, dm->depth, dm->init_A, dm->init_B};
+    hipLaunchKernelGGL(dm_merge_find, dim3(cdiv(nb + 1, 256)), dim3(256), 0, st, keys, (uint32_t)nb, pool, n_old && dm->tab_cap ? 1u : 0u, slot, flag);
+    DM_TRY(hipGetLastError());
+    dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
+    DM_OK(exclusive_scan(dm, flag, off, (uint32_t)nb + 1u));
+    uint32_t created = 0, err = 0;
+    DM_TRY(hipMemcpyAsync(&created, off + nb, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));   // (buf is the caller's again)
+    if (err & kScanErrStuck) {
+        dm->poisoned = true;
+        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
+    }
+    if (created > nb) return dm_fail(dm, LA3DM_ERR_HIP, "la3dm_devmap_merge_host: more blocks created than the stream has (internal error)");
+    if ((uint64_t)n_old + created > cap_max) return refuse(dm, who, too_big);
+    DM_OK(grow_pool(dm, (size_t)n_old + created));
+    DM_OK(grow_table(dm, (size_t)n_old + created));
+    if (created) {
+        hipLaunchKernelGGL(dm_merge_insert, dim3(cdiv(nb, 256)), dim3(256), 0, st, keys, (uint32_t)nb, (const uint32_t *)flag, (const uint32_t *)off,
+                           n_old, dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->blk_key, slot);
+        DM_TRY(hipGetLastError());
+    }
+    MergeArgs ma;
+    ma.A = dm->A;
+    ma.B = dm->B;
+    ma.S = dm->S;
+    ma.n_blocks = (uint32_t)nb;
+    ma.npb = npb;
+    ma.block_depth = dm->depth;
+    ma.slot = slot;
+    ma.flag = flag;
+    ma.leaf_off = (const uint32_t *)(arena + l.leaf_off);
+    ma.mask = (const uint32_t *)(arena + l.mask);
+    ma.i_state = arena + l.state;
+    ma.i_A = (const float *)(arena + l.A);
+    ma.i_B = (const float *)(arena + l.B);
+    ma.a0 = dm->init_A;
+    ma.b0 = dm->init_B;
+    ma.free_thresh = ctx->p.free_thresh;
+    ma.occupied_thresh = ctx->p.occupied_thresh;
+    ma.var_thresh = ctx->p.var_thresh;
+    ma.cells = cells;
+    hipLaunchKernelGGL(dm_merge_fuse, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * merge_lds_stride(dm->depth), st, ma);
+    DM_TRY(hipGetLastError());
+    std::vector<unsigned long long> slots(kMergeCntWords);
+    DM_TRY(hipMemcpyAsync(slots.data(), cells, 8ull * kMergeCntWords, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    unsigned long long h_cells[3] = {0, 0, 0};
+    for (uint32_t s = 0; s < kMergeCntSlots; ++s)
+        for (uint32_t k = 0; k < 3; ++k) h_cells[k] += slots[(size_t)(3u * s + k) * kMergeCntStride];
+    dm->n_blocks = n_old + created;
+    dm->insert_into_empty = false;
+    dm->counters_clean = false;
+    if (stats) {
+        stats->n_blocks = nb;
+        stats->n_created = created;
+        stats->cells_kept = h_cells[0];
+        stats->cells_copied = h_cells[1];
+        stats->cells_fused = h_cells[2];
+    }
     return LA3DM_OK;
 }
 

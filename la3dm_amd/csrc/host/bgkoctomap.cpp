@@ -13,6 +13,7 @@
 //   Occupancy                          src/bgkoctomap/bgkoctree_node.cpp:15-44
 #include "bgkoctomap.h"
 #include "region_contract.h"
+#include "merge_block.h"
 #include "pack_format.h"
 
 #include <algorithm>
@@ -762,6 +763,84 @@ void BGKOctoMap::load(const std::string &path) {
     in.seekg(0);
     if (!bytes.empty() && !in.read((char *)bytes.data(), size)) throw std::runtime_error("BGKOctoMap::load: cannot read " + path);
     unpack(bytes.data(), bytes.size());
+}
+
+// ---- merge (include/la3dm_hip.h, la3dm_devmap_merge_host; the rule per block: merge_block.h) ----
+la3dm_merge_stats BGKOctoMap::merge(const void *stream, size_t size) {
+    bind();
+    la3dm_merge_stats stats;
+    std::memset(&stats, 0, sizeof(stats));
+    if (dmap != nullptr) {
+        if (la3dm_devmap_merge_host(dmap, stream, size, &stats) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::merge: ") + la3dm_last_error(ctx));
+        mirror_dirty = true;
+        return stats;
+    }
+    if (variant != 0 && variant != 3)
+        throw std::runtime_error("BGKOctoMap::merge: merge is defined for BGKOctoMap (variant 0) and BGKLOctoMap (variant 3) maps; GPOctoMap and BGKLVOctoMap fuse by other rules");
+    la3dm_pack_header h;
+    const la3dm_pack_header my = la3dm_pack::make_header(stream_params(create_params, resolution, block_depth), mine.original_size, nullptr, 0, 0);
+    std::string bad = la3dm_pack::validate(stream, size, &h);
+    if (bad.empty()) bad = la3dm_pack::mismatch(h, my);
+    if (bad.empty() && (block_arr.size() + h.n_blocks) * (uint64_t)h.nodes_per_block > la3dm_pack::kPoolNodeLimit) {
+        uint64_t created = 0;   // (only a stream this large is looked through twice)
+        const la3dm_pack::Layout lk = la3dm_pack::layout(h.n_blocks, h.n_leaves, h.nodes_per_block);
+        for (uint64_t b = 0; b < h.n_blocks; ++b) {
+            int64_t key;
+            std::memcpy(&key, (const uint8_t *)stream + lk.keys + 8 * b, 8);
+            created += block_arr.find(key) == block_arr.end();
+        }
+        if ((block_arr.size() + created) * (uint64_t)h.nodes_per_block > la3dm_pack::kPoolNodeLimit) bad = "the merged pool would pass 2^32 nodes";
+    }
+    if (!bad.empty()) throw std::runtime_error("BGKOctoMap::merge: " + bad);
+    const la3dm_pack::Layout l = la3dm_pack::layout(h.n_blocks, h.n_leaves, h.nodes_per_block);
+    const uint32_t npb = h.nodes_per_block;
+    const la3dm_merge::Rule rule = {h.block_depth,           my.init_A, my.init_B, create_params.free_thresh, create_params.occupied_thresh,
+                                    create_params.var_thresh};
+    la3dm_merge::Counts cells;
+    std::vector<float> A1(npb), B1(npb), A2(npb), B2(npb);
+    std::vector<uint8_t> S1(npb), S2(npb);
+    for (uint64_t b = 0; b < h.n_blocks; ++b) {
+        int64_t key;
+        std::memcpy(&key, (const uint8_t *)stream + l.keys + 8 * b, 8);
+        la3dm_pack::expand_block((const uint8_t *)stream, h, l, b, A2.data(), B2.data(), S2.data());
+        auto it = block_arr.find(key);
+        const bool created = it == block_arr.end();
+        if (created) {
+            it = block_arr.emplace(key, new Block(hash_key_to_block(key))).first;
+            ++stats.n_created;
+        } else {
+            const OcTreeNode *slab = it->second->slab;
+            for (uint32_t n = 0; n < npb; ++n) {
+                A1[n] = slab[n].m_A;
+                B1[n] = slab[n].m_B;
+                S1[n] = (uint8_t)((uint8_t)slab[n].state | (slab[n].classified ? 0x80u : 0u));
+            }
+        }
+        la3dm_merge::merge_block(rule, created, A1.data(), B1.data(), S1.data(), A2.data(), B2.data(), S2.data(), cells);
+        it->second->load_nodes(A1.data(), B1.data(), S1.data(), npb);
+    }
+    stats.n_blocks = h.n_blocks;
+    stats.cells_kept = cells.kept;
+    stats.cells_copied = cells.copied;
+    stats.cells_fused = cells.fused;
+    return stats;
+}
+
+la3dm_merge_stats BGKOctoMap::merge(const BGKOctoMap &other) {
+    if (&other == this) throw std::runtime_error("BGKOctoMap::merge: a map is not merged into itself");
+    const std::vector<uint8_t> bytes = other.pack();   // (binds the other map; merge() binds this one again)
+    return merge(bytes.data(), bytes.size());
+}
+
+la3dm_merge_stats BGKOctoMap::merge_file(const std::string &path) {
+    std::ifstream in(path, std::ios::binary | std::ios::ate);
+    if (!in) throw std::runtime_error("BGKOctoMap::merge_file: cannot open " + path);
+    const std::streamsize size = in.tellg();
+    std::vector<uint8_t> bytes((size_t)std::max<std::streamsize>(size, 0));
+    in.seekg(0);
+    if (!bytes.empty() && !in.read((char *)bytes.data(), size)) throw std::runtime_error("BGKOctoMap::merge_file: cannot read " + path);
+    return merge(bytes.data(), bytes.size());
 }
 
 std::vector<float> BGKOctoMap::device_training_data() const {

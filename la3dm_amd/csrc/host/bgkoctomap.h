@@ -518,6 +518,15 @@ public:
     void unpack(const void *stream, size_t size);
     void save(const std::string &path) const;
     void load(const std::string &path);
+    /// Merge (contract: include/la3dm_hip.h, la3dm_devmap_merge_host): a stream — or another map of the same class, packed
+    /// first — fused into this map, which may hold blocks.  Per finest cell of every block the stream names: kept where the
+    /// incoming leaf is the default node, copied where this map's is, else the evidence sums added and the state re-derived;
+    /// then the block is pruned and written in unpack's canonical form.  BGKOctoMap and BGKLOctoMap only.  A
+    /// device-resident map fuses on the GPU pool (mirror marked stale), a host-mode map runs host/merge_block.h over its
+    /// blocks: the same bytes.  The stream is validated before anything is touched; a refusal throws std::runtime_error.
+    la3dm_merge_stats merge(const void *stream, size_t size);
+    la3dm_merge_stats merge(const BGKOctoMap &other);
+    la3dm_merge_stats merge_file(const std::string &path);
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {

@@ -470,6 +470,18 @@ int la3dm_map_load(la3dm_map *m, const char *path) {
     GUARD(if (path == nullptr) throw std::invalid_argument("BGKOctoMap::load: path is NULL"); m->map->load(path); return 0;)
 }
 
+int la3dm_map_merge(la3dm_map *m, const void *buf, uint64_t size, la3dm_merge_stats *stats) {
+    GUARD(const la3dm_merge_stats s = m->map->merge(buf, (size_t)size); if (stats) *stats = s; return 0;)
+}
+
+int la3dm_map_merge_file(la3dm_map *m, const char *path, la3dm_merge_stats *stats) {
+    GUARD(
+        if (path == nullptr) throw std::invalid_argument("BGKOctoMap::merge_file: path is NULL");
+        const la3dm_merge_stats s = m->map->merge_file(path);
+        if (stats) *stats = s;
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);
