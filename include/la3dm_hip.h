@@ -502,6 +502,48 @@ typedef struct la3dm_merge_stats {
     uint64_t cells_kept, cells_copied, cells_fused;
 } la3dm_merge_stats;
 int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la3dm_merge_stats *stats /* may be NULL */);
+/* The map as a rolling window: the stream of SOME blocks, and blocks leaving the map (csrc/devmap_evict.h; the region test,
+ * shared with the host-mode map: csrc/host/region_blocks.h).  All four map classes, every block_depth pack accepts.
+ *
+ *   THE REGION is a closed box of blocks in integer block-key coordinates, klo[a] <= k[a] <= khi[a] on the axes a = x, y, z,
+ *   where k[a] is the 20-bit field of the block's hash key on that axis (x: bits 59..40, y: 39..20, z: 19..0 — the numbers
+ *   la3dm_devmap_key_bounds reports; the block that holds a world point has the fields of block_to_hash_key of that point).
+ *   inside = 1 selects the blocks in the box, inside = 0 every OTHER block (erase all but the box round the robot).
+ *   klo[a] > khi[a] on any axis, a null bound and an inside other than 0 or 1 are refused (LA3DM_ERR_ARG, the text through
+ *   la3dm_last_error, the map exactly as it was); so is a poisoned map.  Bounds outside 0 .. 2^20 - 1 are no error.
+ *
+ *   PACK_REGION writes the version-1 stream of la3dm_devmap_pack_host, unchanged in format, that holds the selected blocks
+ *   only: la3dm_pack_info, unpack and merge accept it.  The blocks come in ascending pool slot (pack's rule), and each
+ *   block's mask words and leaf bytes are bit for bit what la3dm_devmap_pack_host writes for that block.  The map is not
+ *   changed.  buf = NULL only sizes (*size); cap < *size is LA3DM_ERR_ARG with *size set; no block selected gives the header
+ *   alone (128 bytes).
+ *
+ *   ERASE_REGION removes the selected blocks: their voxels read as missing through every query, the block count drops, a
+ *   later insert or merge may create blocks there again.  THE POOL AFTERWARDS, with n_old blocks before and n_removed
+ *   selected: n_new = n_old - n_removed.  A surviving block in a slot < n_new keeps its slot.  Let the holes be the removed
+ *   slots < n_new in ascending order, h_0 < h_1 < ..., and the tail survivors the surviving slots >= n_new in ascending order,
+ *   t_0 < t_1 < ... — there are equally many; the block in t_i moves to h_i, every node of it (A, B and the state byte, dead
+ *   nodes included) and its key.  That is the fewest blocks that can move; sources and destinations are disjoint, so the move
+ *   runs in place; it is deterministic, so replicas that erase one region stay identical.  Blocks that do not move are neither
+ *   read nor written, apart from their keys.  The block table is rebuilt for the n_new blocks.  Slots >= n_new are dead: their
+ *   bytes are not part of the map, and whoever creates a block later writes every node of it.  Nothing selected is a no-op;
+ *   everything selected leaves an empty map that behaves like a new one.  The last scan's training data, the options, the
+ *   shard settings, the pool's allocation and the table's capacity are untouched.  stats (may be NULL): blocks removed, blocks
+ *   moved (the number of holes), and the block count after the call; all zero after a refusal.
+ *   Launch chains.  Both: dm_evict_select (one lane per block), the map's one-launch scan over n_blocks + 1 flags, one
+ *   read-back of the number selected.  pack_region: dm_evict_list (slot list + keys), then pack's chain over the list
+ *   (dm_pack_count, the scan, one read-back of n_leaves, dm_pack_emit, one copy).  erase_region: dm_evict_plan (holes and tail
+ *   survivors from the same scan), dm_evict_move (one wave per pair), the table cleared, dm_table_rebuild, one copy of the
+ *   number moved. */
+typedef struct la3dm_erase_stats {
+    uint64_t n_removed;
+    uint64_t n_moved;
+    uint64_t n_blocks;   /* after the call */
+} la3dm_erase_stats;
+int la3dm_devmap_pack_region_host(la3dm_devmap *dm, const int32_t klo[3], const int32_t khi[3], int inside, void *buf, uint64_t cap,
+                                  uint64_t *size);
+int la3dm_devmap_erase_region_host(la3dm_devmap *dm, const int32_t klo[3], const int32_t khi[3], int inside,
+                                   la3dm_erase_stats *stats /* may be NULL */);
 /* BGKOctoMap::search(x, y, z) (include/bgkoctomap/bgkoctomap.h:315-319) for n query points (host pointers, packed xyz),
  * answered from the device pool without refreshing a host mirror: exists[i] = the block exists; A/B/state = the
  * finest-layer node that holds the point (a default node when the block is missing). */

@@ -211,6 +211,23 @@ int la3dm_map_load(la3dm_map *m, const char *path);
  * the map as it was (-1, la3dm_map_last_error). */
 int la3dm_map_merge(la3dm_map *m, const void *buf, uint64_t size, la3dm_merge_stats *stats);
 int la3dm_map_merge_file(la3dm_map *m, const char *path, la3dm_merge_stats *stats);
+/* BGKOctoMap::pack_region / erase_region / evict / evict_file, all four classes: the map as a rolling window (the region,
+ * the stream, the pool after an erase and the refusals: include/la3dm_hip.h, la3dm_devmap_pack_region_host).  The region is
+ * given by two world points lo3, hi3: the box of blocks from the block that holds lo3 to the block that holds hi3
+ * (block_to_hash_key of each point, on the host: klo from lo3, khi from hi3; klo > khi on an axis is refused); inside = 1 selects the blocks
+ * in the box, 0 every other block.  pack_region follows la3dm_map_pack's buffer convention (buf = NULL sizes, cap < *size
+ * is -1 with *size set) and does not change the map; a device-resident map writes the selected blocks in pool slot order, a
+ * host-mode map in ascending key order.  erase_region removes the selected blocks (a device-resident map compacts its pool
+ * on the GPU and drops the blocks from its mirror, which is marked stale; a host-mode map erases them from its container);
+ * stats may be NULL.  evict = pack_region, then erase_region of the same region, composed on the host: the stream is in buf
+ * — or, for evict_file, written to path + ".tmp" and renamed to path — BEFORE the first block is removed; if that step
+ * fails (-1, la3dm_map_last_error) the map is as it was.  evict with buf = NULL only sizes and removes nothing.  What was
+ * evicted can be merged back (la3dm_map_merge_file). */
+int la3dm_map_pack_region(const la3dm_map *m, const float *lo3, const float *hi3, int inside, void *buf, uint64_t cap, uint64_t *size);
+int la3dm_map_erase_region(la3dm_map *m, const float *lo3, const float *hi3, int inside, la3dm_erase_stats *stats);
+int la3dm_map_evict(la3dm_map *m, const float *lo3, const float *hi3, int inside, void *buf, uint64_t cap, uint64_t *size,
+                    la3dm_erase_stats *stats);
+int la3dm_map_evict_file(la3dm_map *m, const char *path, const float *lo3, const float *hi3, int inside, la3dm_erase_stats *stats);
 /* how often the host mirror of a device-resident map was refreshed (a download of every node of every block) */
 uint64_t la3dm_map_mirror_syncs(const la3dm_map *m);
 int la3dm_map_get_bbox(const la3dm_map *m, float *lim_min3, float *lim_max3);

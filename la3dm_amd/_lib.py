@@ -139,6 +139,10 @@ class MergeStats(C.Structure):   # la3dm_merge_stats
     _fields_ = [(k, C.c_uint64) for k in ("n_blocks", "n_created", "cells_kept", "cells_copied", "cells_fused")]
 
 
+class EraseStats(C.Structure):   # la3dm_erase_stats
+    _fields_ = [(k, C.c_uint64) for k in ("n_removed", "n_moved", "n_blocks")]
+
+
 class PackHeader(C.Structure):   # la3dm_pack_header: the first 128 bytes of a map stream
     _fields_ = [("magic", C.c_char * 8)] + \
                [(k, C.c_uint32) for k in ("version", "header_bytes", "variant", "block_depth", "nodes_per_block", "flags")] + \
@@ -165,7 +169,8 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_gain_host", "la3dm_devmap_gain_device", "la3dm_devmap_reach_host",
                "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device",
                "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device",
-               "la3dm_devmap_pack_host", "la3dm_devmap_unpack_host", "la3dm_pack_info", "la3dm_devmap_merge_host"]
+               "la3dm_devmap_pack_host", "la3dm_devmap_unpack_host", "la3dm_pack_info", "la3dm_devmap_merge_host",
+               "la3dm_devmap_pack_region_host", "la3dm_devmap_erase_region_host"]
 MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
                "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
                "la3dm_map_insert_training_data", "la3dm_map_prepare", "la3dm_map_prepare_training_data",
@@ -180,7 +185,8 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_raycast_many", "la3dm_map_mirror_syncs", "la3dm_map_box", "la3dm_map_columns",
                "la3dm_map_distance_field", "la3dm_map_frontier", "la3dm_map_gain", "la3dm_map_reach",
                "la3dm_map_travel", "la3dm_map_clusters", "la3dm_map_pack", "la3dm_map_unpack", "la3dm_map_save",
-               "la3dm_map_load", "la3dm_map_merge", "la3dm_map_merge_file"]
+               "la3dm_map_load", "la3dm_map_merge", "la3dm_map_merge_file", "la3dm_map_pack_region",
+               "la3dm_map_erase_region", "la3dm_map_evict", "la3dm_map_evict_file"]
 
 _hip = None
 _map = None
@@ -294,6 +300,11 @@ def hip():
         L.la3dm_devmap_unpack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.la3dm_devmap_merge_host.restype = C.c_int
         L.la3dm_devmap_merge_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MergeStats)]
+        L.la3dm_devmap_pack_region_host.restype = C.c_int
+        L.la3dm_devmap_pack_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_uint64,
+                                                    C.POINTER(C.c_uint64)]
+        L.la3dm_devmap_erase_region_host.restype = C.c_int
+        L.la3dm_devmap_erase_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(EraseStats)]
         L.la3dm_pack_info.restype = C.c_int
         L.la3dm_pack_info.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PackHeader)]
         L.la3dm_devmap_training_data.restype = C.c_int
@@ -372,6 +383,14 @@ def maplib():
         M.la3dm_map_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MergeStats)]
         M.la3dm_map_merge_file.restype = C.c_int
         M.la3dm_map_merge_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(MergeStats)]
+        M.la3dm_map_pack_region.restype = C.c_int
+        M.la3dm_map_pack_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        M.la3dm_map_erase_region.restype = C.c_int
+        M.la3dm_map_erase_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EraseStats)]
+        M.la3dm_map_evict.restype = C.c_int
+        M.la3dm_map_evict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(EraseStats)]
+        M.la3dm_map_evict_file.restype = C.c_int
+        M.la3dm_map_evict_file.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EraseStats)]
         M.la3dm_map_mirror_syncs.restype = C.c_uint64
         M.la3dm_map_mirror_syncs.argtypes = [C.c_void_p]
         M.la3dm_map_raycast.restype = C.c_uint64

@@ -625,6 +625,57 @@ class BGKOctoMap:
         self._chk(self._M.la3dm_map_merge_file(self._h, os.fsencode(path), C.byref(stats)))
         return {k: int(getattr(stats, k)) for k, _ in _lib.MergeStats._fields_}
 
+    @staticmethod
+    def _region_points(lo, hi):
+        lo3, hi3 = np.ascontiguousarray(lo, np.float32).reshape(-1), np.ascontiguousarray(hi, np.float32).reshape(-1)
+        if lo3.size != 3 or hi3.size != 3:
+            raise ValueError("a region is given by two points of three coordinates")
+        return lo3, hi3
+
+    def pack_region(self, lo, hi, inside=True):
+        """The stream of pack() with some of the blocks only (contract: include/la3dm_hip.h, la3dm_devmap_pack_region_host):
+        the box of blocks from the block that holds the world point lo to the block that holds hi; inside=True selects the
+        blocks in the box, False every other block.  The map is not changed; unpack(), merge() and pack_info() take the
+        stream.  A device-resident map compacts the selected blocks on the GPU (pool slot order, no mirror refresh), a
+        host-mode map writes them in ascending key order.  No block selected gives the header alone."""
+        lo3, hi3 = self._region_points(lo, hi)
+        size = C.c_uint64(0)
+        args = (self._h, lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0)
+        self._chk(self._M.la3dm_map_pack_region(*args, None, 0, C.byref(size)))
+        buf = np.empty(int(size.value), np.uint8)
+        self._chk(self._M.la3dm_map_pack_region(*args, buf.ctypes.data, buf.size, C.byref(size)))
+        return buf[:int(size.value)]
+
+    def erase_region(self, lo, hi, inside=True):
+        """Remove the selected blocks (the region as in pack_region): their voxels read as missing through every query,
+        block_count() drops, a later insert or merge may create blocks there again.  A device-resident map compacts its
+        pool in place on the GPU — the surviving blocks of the tail fill the holes, everything else keeps its slot — and
+        rebuilds its block table.  Returns dict(n_removed, n_moved, n_blocks); n_blocks is the count after the call."""
+        lo3, hi3 = self._region_points(lo, hi)
+        stats = _lib.EraseStats()
+        self._chk(self._M.la3dm_map_erase_region(self._h, lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0, C.byref(stats)))
+        return {k: int(getattr(stats, k)) for k, _ in _lib.EraseStats._fields_}
+
+    def evict(self, lo, hi, inside=True):
+        """pack_region(), then erase_region() of the same region: the stream is complete on the host before the first block
+        is removed, and a failure of the pack step leaves the map as it was.  Returns the stream as bytes; merge() of it
+        brings the blocks back."""
+        lo3, hi3 = self._region_points(lo, hi)
+        size = C.c_uint64(0)
+        args = (self._h, lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0)
+        self._chk(self._M.la3dm_map_evict(*args, None, 0, C.byref(size), None))   # (sizes only: nothing is removed)
+        buf = np.empty(int(size.value), np.uint8)
+        self._chk(self._M.la3dm_map_evict(*args, buf.ctypes.data, buf.size, C.byref(size), None))
+        return buf[:int(size.value)].tobytes()
+
+    def evict_file(self, path, lo, hi, inside=True):
+        """evict() into a file: the stream is written to path + ".tmp" and renamed to path before the first block is removed
+        (merge_file(path) brings the blocks back).  Returns erase_region()'s dict."""
+        lo3, hi3 = self._region_points(lo, hi)
+        stats = _lib.EraseStats()
+        self._chk(self._M.la3dm_map_evict_file(self._h, os.fsencode(path), lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0, C.byref(stats)))
+        return {k: int(getattr(stats, k)) for k, _ in _lib.EraseStats._fields_}
+
     def mirror_syncs(self):
         """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
         return int(self._M.la3dm_map_mirror_syncs(self._h))

@@ -36,7 +36,9 @@
 #include "devmap_clusters.h"
 #include "devmap_pack.h"
 #include "devmap_merge.h"
+#include "devmap_evict.h"
 #include "host/pack_format.h"
+#include "host/region_blocks.h"
 
 using namespace la3dm_dev;
 
@@ -2354,14 +2356,19 @@ static int refuse(la3dm_devmap *dm, const char *who, const std::string &refusal)
 // scan over n_blocks + 1 counts straight into the stream's leaf_off section, one read-back of n_leaves, dm_pack_emit, one copy.
 // The stream arena is reserved for the most leaves the blocks can have (every finest cell: 64 / 73 of the raw pool at
 // block_depth 3) before the count is known, so nothing the count launch wrote has to move.
-int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *size) {
-    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
-    if (!dm || !size) return LA3DM_ERR_ARG;
-    const char *who = "la3dm_devmap_pack_host";
-    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+// pl = nullptr: stream block b is pool slot b (pack); else the nb selected slots of pack_region, whose flags and ranks lie in
+// pack_counts already (nothing here may reserve that arena again): dm_evict_list writes the slot list and the keys.
+namespace {
+struct PackList {
+    const uint32_t *flag, *rank;   // per pool slot (+ the closing entry)
+    uint32_t *list, *counts;       // nb slots; nb + 1 leaf counts
+    uint32_t n_pool;
+};
+}  // namespace
+
+static int pack_blocks(la3dm_devmap *dm, const char *who, uint64_t nb, const PackList *pl, void *buf, uint64_t cap, uint64_t *size) {
     la3dm_ctx *ctx = dm->ctx;
-    const uint64_t nb = dm->n_blocks;
-    if (nb == 0) {   // an empty map is the header alone: no launch
+    if (nb == 0) {   // no block is the header alone: no launch
         *size = la3dm_pack::kHeaderBytes;
         if (!buf) return LA3DM_OK;
         if (cap < *size) return refuse(dm, who, "the buffer is smaller than the stream");
@@ -2374,11 +2381,19 @@ int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *
     const uint32_t npb = dm->npb;
     const la3dm_pack::Layout worst = la3dm_pack::layout(nb, nb * dm->ncell, npb);
     DM_RESERVE(dm->pack_stream, worst.total);
-    DM_RESERVE(dm->pack_counts, 4ull * (nb + 1));
+    if (!pl) DM_RESERVE(dm->pack_counts, 4ull * (nb + 1));
     uint8_t *arena = (uint8_t *)dm->pack_stream.ptr;
-    uint32_t *counts = (uint32_t *)dm->pack_counts.ptr, *leaf_off = (uint32_t *)(arena + worst.leaf_off), *mask = (uint32_t *)(arena + worst.mask);
-    hipLaunchKernelGGL(dm_pack_count, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
-                       (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask);
+    uint32_t *counts = pl ? pl->counts : (uint32_t *)dm->pack_counts.ptr, *leaf_off = (uint32_t *)(arena + worst.leaf_off), *mask = (uint32_t *)(arena + worst.mask);
+    if (pl) {
+        hipLaunchKernelGGL(dm_evict_list, dim3(cdiv(pl->n_pool, 256)), dim3(256), 0, st, (const long long *)dm->blk_key, pl->n_pool, pl->flag, pl->rank,
+                           pl->list, (long long *)(arena + worst.keys));
+        DM_TRY(hipGetLastError());
+        hipLaunchKernelGGL(dm_pack_count<true>, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
+                           (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask, (const uint32_t *)pl->list);
+    } else {
+        hipLaunchKernelGGL(dm_pack_count<false>, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
+                           (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask, (const uint32_t *)nullptr);
+    }
     DM_TRY(hipGetLastError());
     DM_OK(exclusive_scan(dm, counts, leaf_off, (uint32_t)nb + 1u));
     uint32_t n_leaves = 0, err = 0;
@@ -2389,14 +2404,14 @@ int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *
         dm->poisoned = true;
         return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
     }
-    if (n_leaves < nb || n_leaves > nb * dm->ncell) return dm_fail(dm, LA3DM_ERR_HIP, "la3dm_devmap_pack_host: the pool's leaves do not tile its blocks (internal error)");
+    if (n_leaves < nb || n_leaves > nb * dm->ncell) return dm_fail(dm, LA3DM_ERR_HIP, std::string(who) + ": the pool's leaves do not tile its blocks (internal error)");
     const la3dm_pack::Layout l = la3dm_pack::layout(nb, n_leaves, npb);
     *size = l.total;
     if (!buf) return LA3DM_OK;
     if (cap < l.total) return refuse(dm, who, "the buffer is smaller than the stream");
     dm->pack_hdr = la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, nb, n_leaves);
     DM_TRY(hipMemcpyAsync(arena, &dm->pack_hdr, sizeof(dm->pack_hdr), hipMemcpyHostToDevice, st));
-    DM_TRY(hipMemcpyAsync(arena + l.keys, dm->blk_key, 8ull * nb, hipMemcpyDeviceToDevice, st));
+    if (!pl) DM_TRY(hipMemcpyAsync(arena + l.keys, dm->blk_key, 8ull * nb, hipMemcpyDeviceToDevice, st));
     PackGaps gaps;
     const uint64_t ends[6][2] = {{l.keys + 8ull * nb, l.leaf_off}, {l.leaf_off + 4ull * (nb + 1), l.mask}, {l.mask + 4ull * nb * l.W, l.state},
                                  {l.state + n_leaves, l.A},         {l.A + 4ull * n_leaves, l.B},           {l.B + 4ull * n_leaves, l.total}};
@@ -2404,12 +2419,121 @@ int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *
         gaps.at[g] = ends[g][0];
         gaps.len[g] = (uint32_t)(ends[g][1] - ends[g][0]);
     }
-    hipLaunchKernelGGL(dm_pack_emit, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
-                       (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
-                       (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps);
+    if (pl)
+        hipLaunchKernelGGL(dm_pack_emit<true>, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
+                           (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
+                           (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps, (const uint32_t *)pl->list);
+    else
+        hipLaunchKernelGGL(dm_pack_emit<false>, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
+                           (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
+                           (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps, (const uint32_t *)nullptr);
     DM_TRY(hipGetLastError());
     DM_TRY(hipMemcpyAsync(buf, arena, l.total, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *size) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm || !size) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_pack_host";
+    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    return pack_blocks(dm, who, dm->n_blocks, nullptr, buf, cap, size);
+}
+
+// ---- pack_region / erase_region (contract: include/la3dm_hip.h; kernels: devmap_evict.h; the region: host/region_blocks.h) ----
+// What both start with: the checks, dm_evict_select over the pool's keys, the one-launch scan over n_blocks + 1 flags, one
+// read-back of the number selected.  pack_counts holds flag[n + 1], rank[n + 1] and 2 n + 2 words for the caller's lists
+// (reserved once: an arena may move when it grows).  *words = the first of those.
+static int evict_select(la3dm_devmap *dm, const char *who, const int32_t *klo, const int32_t *khi, int inside, uint32_t **flag,
+                        uint32_t **rank, uint32_t **words, uint32_t *n_sel) {
+    EvictBox box;
+    const std::string bad = la3dm_region_blocks::check(klo, khi, &box);
+    if (!bad.empty()) return refuse(dm, who, bad);
+    if (inside != 0 && inside != 1) return refuse(dm, who, "inside is neither 0 nor 1");
+    box.inside = inside;
+    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    *n_sel = 0;
+    const uint32_t n = dm->n_blocks;
+    if (n == 0) return LA3DM_OK;
+    DM_TRY(hipSetDevice(dm->ctx->device));
+    hipStream_t st = dm->ctx->stream;
+    DM_RESERVE(dm->pack_counts, 4ull * (4ull * n + 4));
+    *flag = (uint32_t *)dm->pack_counts.ptr;
+    *rank = *flag + n + 1;
+    *words = *rank + n + 1;
+    hipLaunchKernelGGL(dm_evict_select, dim3(cdiv(n + 1, 256)), dim3(256), 0, st, (const long long *)dm->blk_key, n, box, *flag);
+    DM_TRY(hipGetLastError());
+    dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
+    DM_OK(exclusive_scan(dm, *flag, *rank, n + 1u));
+    uint32_t err = 0;
+    DM_TRY(hipMemcpyAsync(n_sel, *rank + n, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (err & kScanErrStuck) {
+        dm->poisoned = true;
+        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
+    }
+    if (*n_sel > n) return dm_fail(dm, LA3DM_ERR_HIP, std::string(who) + ": more blocks selected than the pool has (internal error)");
+    return LA3DM_OK;
+}
+
+// Launch chain: dm_evict_select, the scan, one read-back (blocks selected), dm_evict_list, then pack's own chain over the list
+// (dm_pack_count, the scan, one read-back of n_leaves, dm_pack_emit, one copy).  The map is not written.
+int la3dm_devmap_pack_region_host(la3dm_devmap *dm, const int32_t klo[3], const int32_t khi[3], int inside, void *buf, uint64_t cap,
+                                  uint64_t *size) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm || !size) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_pack_region_host";
+    uint32_t *flag = nullptr, *rank = nullptr, *words = nullptr, n_sel = 0;
+    DM_OK(evict_select(dm, who, klo, khi, inside, &flag, &rank, &words, &n_sel));
+    const PackList pl = {flag, rank, words, words + dm->n_blocks, dm->n_blocks};
+    return pack_blocks(dm, who, n_sel, &pl, buf, cap, size);
+}
+
+// Launch chain: dm_evict_select, the scan, one read-back (blocks removed); then dm_evict_plan (hole[] and tail[] from the same
+// scan), dm_evict_move (one wave per pair, in place), the table cleared and dm_table_rebuild over n_new, one copy of the
+// number moved.  Slots >= n_new are dead afterwards: whoever creates a block writes every node of it (dm_pool_init or the
+// leaf-count launch for an insert, dm_merge_fuse for a merge, dm_unpack_expand for unpack), so nothing is cleared here.
+int la3dm_devmap_erase_region_host(la3dm_devmap *dm, const int32_t klo[3], const int32_t khi[3], int inside, la3dm_erase_stats *stats) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_erase_region_host";
+    if (stats) memset(stats, 0, sizeof(*stats));
+    uint32_t *flag = nullptr, *rank = nullptr, *words = nullptr, n_removed = 0;
+    DM_OK(evict_select(dm, who, klo, khi, inside, &flag, &rank, &words, &n_removed));
+    if (n_removed == 0) {   // nothing selected: a no-op
+        if (stats) stats->n_blocks = dm->n_blocks;
+        return LA3DM_OK;
+    }
+    hipStream_t st = dm->ctx->stream;
+    const uint32_t n = dm->n_blocks, n_new = n - n_removed, most = std::min(n_removed, n_new);
+    uint32_t n_moved = 0;
+    if (most) {
+        uint32_t *hole = words, *tail = words + n;
+        hipLaunchKernelGGL(dm_evict_plan, dim3(cdiv(n, 256)), dim3(256), 0, st, n, (const uint32_t *)flag, (const uint32_t *)rank, hole, tail);
+        DM_TRY(hipGetLastError());
+        hipLaunchKernelGGL(dm_evict_move, dim3(cdiv(most, kPackWaves)), dim3(64 * kPackWaves), 0, st, dm->A, dm->B, dm->S, dm->blk_key, dm->npb,
+                           (const uint32_t *)(rank + n_new), (const uint32_t *)hole, (const uint32_t *)tail);
+        DM_TRY(hipGetLastError());
+        DM_TRY(hipMemcpyAsync(&n_moved, rank + n_new, 4, hipMemcpyDeviceToHost, st));
+    }
+    // from the first launch that writes the map on, the block count is the new one: a failure below leaves a map that says so
+    dm->n_blocks = n_new;
+    dm->counters_clean = false;
+    if (dm->tab_cap) {
+        DM_TRY(hipMemsetAsync(dm->tab_key, 0xFF, 8ull * dm->tab_cap, st));
+        if (n_new) {
+            hipLaunchKernelGGL(dm_table_rebuild, dim3(cdiv(n_new, 256)), dim3(256), 0, st, dm->blk_key, n_new, dm->tab_key, dm->tab_val, dm->tab_cap - 1);
+            DM_TRY(hipGetLastError());
+        }
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    if (stats) {
+        stats->n_removed = n_removed;
+        stats->n_moved = n_moved;
+        stats->n_blocks = n_new;
+    }
     return LA3DM_OK;
 }
 

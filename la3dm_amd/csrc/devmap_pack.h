@@ -10,6 +10,8 @@
 //   dm_pack_emit    re-reads the mask words (the ballots) and gathers state, A, B of the set nodes to leaf_off[b] + rank, rank =
 //                   the prefix popcount inside the 64-node chunk + the popcount of the chunks before it (a running base in a
 //                   scalar): no atomics, no register array indexed at run time.  Workgroup 0 also zeroes the stream's padding.
+//   Both take the pool slot of stream block b behind a template flag: pack reads slot b, pack_region (devmap_evict.h) the
+//   slot its list names; the mask words, counts and leaves are indexed by the STREAM block either way.
 //   dm_unpack_expand loads the block's mask words and their exclusive popcount prefixes into LDS and writes every node of the
 //                   block exactly once, coalesced: a set node takes its leaf's values, a node with a set ancestor (init, PRUNED),
 //                   every other node (init, UNKNOWN).  It only ever sees a stream that host/pack_format.h validated.
@@ -31,15 +33,18 @@ __device__ __forceinline__ uint32_t pack_layer_of(uint32_t n, uint32_t dl) {
 }
 
 // Dynamic LDS: kPackWaves x pack_lds_stride(npb) bytes.
+// kList (pack_region, devmap_evict.h): stream block b is pool slot list[b]; else (pack) it is slot b and list is not read.
+template <bool kList>
 __global__ __launch_bounds__(64 * kPackWaves) void dm_pack_count(const uint8_t *__restrict__ S, uint32_t n_blocks, uint32_t npb,
-                                                                 uint32_t block_depth, uint32_t *counts, uint32_t *mask) {
+                                                                 uint32_t block_depth, uint32_t *counts, uint32_t *mask,
+                                                                 const uint32_t *__restrict__ list) {
     extern __shared__ __attribute__((aligned(16))) uint8_t dm_pack_smem[];
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t b = blockIdx.x * kPackWaves + wv;
     if (b == n_blocks && lane == 0) counts[n_blocks] = 0u;   // (the grid covers n_blocks + 1 waves)
     if (b >= n_blocks) return;
     uint8_t *sS = dm_pack_smem + wv * pack_lds_stride(npb);
-    const uint8_t *Sb = S + (size_t)b * npb;
+    const uint8_t *Sb = S + (size_t)(kList ? list[b] : b) * npb;
     for (uint32_t i = lane; i < npb; i += 64) sS[i] = Sb[i];
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -66,10 +71,12 @@ struct PackGaps {   // the stream's padding: gap g is the bytes [at[g], at[g] + 
     uint32_t len[6];
 };
 
+template <bool kList>
 __global__ __launch_bounds__(64 * kPackWaves) void dm_pack_emit(const float *__restrict__ A, const float *__restrict__ B,
                                                                 const uint8_t *__restrict__ S, uint32_t n_blocks, uint32_t npb,
                                                                 const uint32_t *__restrict__ leaf_off, const uint32_t *__restrict__ mask,
-                                                                uint8_t *o_state, float *o_A, float *o_B, uint8_t *stream, PackGaps gaps) {
+                                                                uint8_t *o_state, float *o_A, float *o_B, uint8_t *stream, PackGaps gaps,
+                                                                const uint32_t *__restrict__ list) {
     if (blockIdx.x == 0 && threadIdx.x < 6u * 16u) {
         const uint32_t g = threadIdx.x >> 4, i = threadIdx.x & 15u;
         if (i < gaps.len[g]) stream[gaps.at[g] + i] = 0;
@@ -79,7 +86,7 @@ __global__ __launch_bounds__(64 * kPackWaves) void dm_pack_emit(const float *__r
     if (b >= n_blocks) return;
     const uint32_t W = (npb + 31u) >> 5;
     const uint32_t *mb = mask + (size_t)b * W;
-    const size_t base = (size_t)b * npb;
+    const size_t base = (size_t)(kList ? list[b] : b) * npb;
     uint32_t out = leaf_off[b];
     for (uint32_t n0 = 0; n0 < npb; n0 += 64) {
         const uint32_t w0 = n0 >> 5;

@@ -14,6 +14,7 @@
 #include "bgkoctomap.h"
 #include "region_contract.h"
 #include "merge_block.h"
+#include "region_blocks.h"
 #include "pack_format.h"
 
 #include <algorithm>
@@ -668,17 +669,19 @@ la3dm_params stream_params(const la3dm_params &created, float resolution, unsign
 }
 }  // namespace
 
-std::vector<uint8_t> BGKOctoMap::pack() const {
+// pack / pack_region: box = nullptr is every block
+std::vector<uint8_t> BGKOctoMap::pack_blocks(const la3dm_region_blocks::Box *box, const char *who) const {
     bind();
     const float gp3[3] = {ctor_gp.min_var, ctor_gp.max_var, ctor_gp.max_known_var};
     const float *exact = variant == 1 ? gp3 : nullptr;
     if (dmap != nullptr) {   // compacted on the GPU; the mirror is not touched
         uint64_t size = 0;
-        if (la3dm_devmap_pack_host(dmap, nullptr, 0, &size) != LA3DM_OK)
-            throw std::runtime_error(std::string("BGKOctoMap::pack: ") + la3dm_last_error(ctx));
+        const auto call = [&](void *buf, uint64_t cap) {
+            return box ? la3dm_devmap_pack_region_host(dmap, box->lo, box->hi, box->inside, buf, cap, &size) : la3dm_devmap_pack_host(dmap, buf, cap, &size);
+        };
+        if (call(nullptr, 0) != LA3DM_OK) throw std::runtime_error(std::string(who) + ": " + la3dm_last_error(ctx));
         std::vector<uint8_t> out(size);
-        if (la3dm_devmap_pack_host(dmap, out.data(), size, &size) != LA3DM_OK)
-            throw std::runtime_error(std::string("BGKOctoMap::pack: ") + la3dm_last_error(ctx));
+        if (call(out.data(), size) != LA3DM_OK) throw std::runtime_error(std::string(who) + ": " + la3dm_last_error(ctx));
         if (exact) std::memcpy(out.data() + offsetof(la3dm_pack_header, min_var), exact, sizeof(gp3));   // (the context only knows the inverses)
         return out;
     }
@@ -687,6 +690,7 @@ std::vector<uint8_t> BGKOctoMap::pack() const {
     std::vector<int64_t> keys;
     keys.reserve(block_arr.size());
     for (const auto &kv : block_arr) keys.push_back(kv.first);
+    if (box) keys = la3dm_region_blocks::select(keys, *box);
     std::sort(keys.begin(), keys.end());
     return la3dm_pack::write(proto, keys, [&](uint64_t b, float *A, float *B, uint8_t *S) {
         const OcTreeNode *slab = block_arr.find(keys[b])->second->slab;   // (retired layers keep their PRUNED nodes in the slab)
@@ -697,6 +701,8 @@ std::vector<uint8_t> BGKOctoMap::pack() const {
         }
     });
 }
+
+std::vector<uint8_t> BGKOctoMap::pack() const { return pack_blocks(nullptr, "BGKOctoMap::pack"); }
 
 uint64_t BGKOctoMap::packed_size() const {
     bind();
@@ -742,18 +748,22 @@ void BGKOctoMap::unpack(const void *stream, size_t size) {
     }
 }
 
-void BGKOctoMap::save(const std::string &path) const {
-    const std::vector<uint8_t> bytes = pack();
+namespace {
+// bytes to path + ".tmp", renamed to path
+void write_renamed(const std::vector<uint8_t> &bytes, const std::string &path, const std::string &who) {
     const std::string tmp = path + ".tmp";
     {
         std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
-        if (!out) throw std::runtime_error("BGKOctoMap::save: cannot open " + tmp);
+        if (!out) throw std::runtime_error(who + ": cannot open " + tmp);
         out.write((const char *)bytes.data(), (std::streamsize)bytes.size());
         out.flush();
-        if (!out) throw std::runtime_error("BGKOctoMap::save: cannot write " + tmp);
+        if (!out) throw std::runtime_error(who + ": cannot write " + tmp);
     }
-    if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error("BGKOctoMap::save: cannot rename " + tmp + " to " + path);
+    if (std::rename(tmp.c_str(), path.c_str()) != 0) throw std::runtime_error(who + ": cannot rename " + tmp + " to " + path);
 }
+}  // namespace
+
+void BGKOctoMap::save(const std::string &path) const { write_renamed(pack(), path, "BGKOctoMap::save"); }
 
 void BGKOctoMap::load(const std::string &path) {
     std::ifstream in(path, std::ios::binary | std::ios::ate);
@@ -841,6 +851,61 @@ la3dm_merge_stats BGKOctoMap::merge_file(const std::string &path) {
     in.seekg(0);
     if (!bytes.empty() && !in.read((char *)bytes.data(), size)) throw std::runtime_error("BGKOctoMap::merge_file: cannot read " + path);
     return merge(bytes.data(), bytes.size());
+}
+
+// ---- pack_region / erase_region / evict (include/la3dm_hip.h, la3dm_devmap_pack_region_host; the region: region_blocks.h) ----
+la3dm_region_blocks::Box BGKOctoMap::region_box(const float *lo3, const float *hi3, bool inside, const char *who) const {
+    bind();   // (block_to_hash_key divides by this map's block size)
+    if (lo3 == nullptr || hi3 == nullptr) throw std::invalid_argument(std::string(who) + ": a region point is NULL");
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(lo3[a]) || !std::isfinite(hi3[a])) throw std::invalid_argument(std::string(who) + ": a region point is not finite");
+    la3dm_region_blocks::Box box;
+    const std::string bad = la3dm_region_blocks::from_corner_keys(block_to_hash_key(lo3[0], lo3[1], lo3[2]), block_to_hash_key(hi3[0], hi3[1], hi3[2]), inside, &box);
+    if (!bad.empty()) throw std::invalid_argument(std::string(who) + ": " + bad);
+    return box;
+}
+
+std::vector<uint8_t> BGKOctoMap::pack_region(const float *lo3, const float *hi3, bool inside) const {
+    const la3dm_region_blocks::Box box = region_box(lo3, hi3, inside, "BGKOctoMap::pack_region");
+    return pack_blocks(&box, "BGKOctoMap::pack_region");
+}
+
+la3dm_erase_stats BGKOctoMap::erase_region(const float *lo3, const float *hi3, bool inside) {
+    const la3dm_region_blocks::Box box = region_box(lo3, hi3, inside, "BGKOctoMap::erase_region");
+    la3dm_erase_stats stats;
+    std::memset(&stats, 0, sizeof(stats));
+    if (dmap != nullptr && la3dm_devmap_erase_region_host(dmap, box.lo, box.hi, box.inside, &stats) != LA3DM_OK)
+        throw std::runtime_error(std::string("BGKOctoMap::erase_region: ") + la3dm_last_error(ctx));
+    // the container: the map itself in host mode; the mirror of a device-resident map, which sync_mirror only ever adds to
+    uint64_t erased = 0;
+    for (auto it = block_arr.begin(); it != block_arr.end();) {
+        if (la3dm_region_blocks::selected(it->first, box)) {
+            delete it->second;
+            it = block_arr.erase(it);
+            ++erased;
+        } else {
+            ++it;
+        }
+    }
+    if (dmap != nullptr) {
+        if (stats.n_removed) mirror_dirty = true;
+        return stats;
+    }
+    stats.n_removed = erased;
+    stats.n_blocks = block_arr.size();   // (n_moved: a host-mode map has no pool slots)
+    return stats;
+}
+
+std::vector<uint8_t> BGKOctoMap::evict(const float *lo3, const float *hi3, bool inside, la3dm_erase_stats *stats) {
+    std::vector<uint8_t> bytes = pack_region(lo3, hi3, inside);   // (on the host before the first block is removed)
+    const la3dm_erase_stats s = erase_region(lo3, hi3, inside);
+    if (stats) *stats = s;
+    return bytes;
+}
+
+la3dm_erase_stats BGKOctoMap::evict_file(const std::string &path, const float *lo3, const float *hi3, bool inside) {
+    write_renamed(pack_region(lo3, hi3, inside), path, "BGKOctoMap::evict_file");
+    return erase_region(lo3, hi3, inside);
 }
 
 std::vector<float> BGKOctoMap::device_training_data() const {

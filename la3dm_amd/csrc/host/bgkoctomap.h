@@ -34,6 +34,9 @@
 namespace la3dm_region {
 struct Query;   // region_contract.h
 }
+namespace la3dm_region_blocks {
+struct Box;   // region_blocks.h
+}
 
 extern "C" void la3dm_node_ab(const void *node, float *A, float *B);  // (m_A, m_B) of an Occupancy
 
@@ -527,6 +530,25 @@ public:
     la3dm_merge_stats merge(const void *stream, size_t size);
     la3dm_merge_stats merge(const BGKOctoMap &other);
     la3dm_merge_stats merge_file(const std::string &path);
+    /// The map as a rolling window (contract: include/la3dm_hip.h, la3dm_devmap_pack_region_host), all four classes.  The
+    /// region is the box of blocks from the block that holds lo3 to the block that holds hi3 (block_to_hash_key, on the
+    /// host; a box whose first block lies past its second on an axis is refused); inside selects the blocks in the box, !inside every other block.  pack_region: the
+    /// stream of the selected blocks only, the map unchanged (device-resident: compacted on the GPU in pool slot order,
+    /// no mirror refresh; host-mode: ascending key).  erase_region: the selected blocks leave the map (device-resident: the
+    /// pool compacted by the hole / tail rule and the table rebuilt on the GPU, the blocks dropped from the mirror, which is
+    /// marked stale; host-mode: erased from the container).  evict: pack_region, then erase_region — the stream is complete on
+    /// the host, and for evict_file written to path + ".tmp" and renamed to path, before the first block is removed; a
+    /// failure of that step throws and leaves the map as it was.  Null points and refusals throw.
+    std::vector<uint8_t> pack_region(const float *lo3, const float *hi3, bool inside) const;
+    la3dm_erase_stats erase_region(const float *lo3, const float *hi3, bool inside);
+    std::vector<uint8_t> evict(const float *lo3, const float *hi3, bool inside, la3dm_erase_stats *stats = nullptr);
+    la3dm_erase_stats evict_file(const std::string &path, const float *lo3, const float *hi3, bool inside);
+
+protected:
+    std::vector<uint8_t> pack_blocks(const la3dm_region_blocks::Box *box, const char *who) const;
+    la3dm_region_blocks::Box region_box(const float *lo3, const float *hi3, bool inside, const char *who) const;
+
+public:
     /// how often the host mirror was refreshed from the device pool (sync_mirror that found it stale)
     uint64_t mirror_syncs() const { return mirror_sync_count; }
     size_t block_count() const {

@@ -482,6 +482,45 @@ int la3dm_map_merge_file(la3dm_map *m, const char *path, la3dm_merge_stats *stat
         return 0;)
 }
 
+int la3dm_map_pack_region(const la3dm_map *m, const float *lo3, const float *hi3, int inside, void *buf, uint64_t cap, uint64_t *size) {
+    GUARD(
+        if (size == nullptr) throw std::invalid_argument("BGKOctoMap::pack_region: size is NULL");
+        const std::vector<uint8_t> bytes = m->map->pack_region(lo3, hi3, inside);
+        *size = bytes.size();
+        if (buf == nullptr) return 0;
+        if (cap < bytes.size()) throw std::invalid_argument("BGKOctoMap::pack_region: the buffer is smaller than the stream");
+        std::memcpy(buf, bytes.data(), bytes.size());
+        return 0;)
+}
+
+int la3dm_map_erase_region(la3dm_map *m, const float *lo3, const float *hi3, int inside, la3dm_erase_stats *stats) {
+    GUARD(const la3dm_erase_stats s = m->map->erase_region(lo3, hi3, inside); if (stats) *stats = s; return 0;)
+}
+
+int la3dm_map_evict(la3dm_map *m, const float *lo3, const float *hi3, int inside, void *buf, uint64_t cap, uint64_t *size,
+                    la3dm_erase_stats *stats) {
+    GUARD(
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        if (size == nullptr) throw std::invalid_argument("BGKOctoMap::evict: size is NULL");
+        const std::vector<uint8_t> bytes = m->map->pack_region(lo3, hi3, inside);
+        *size = bytes.size();
+        if (buf == nullptr) return 0;
+        if (cap < bytes.size()) throw std::invalid_argument("BGKOctoMap::evict: the buffer is smaller than the stream");
+        std::memcpy(buf, bytes.data(), bytes.size());   // the stream is the caller's before the first block leaves
+        const la3dm_erase_stats s = m->map->erase_region(lo3, hi3, inside);
+        if (stats) *stats = s;
+        return 0;)
+}
+
+int la3dm_map_evict_file(la3dm_map *m, const char *path, const float *lo3, const float *hi3, int inside, la3dm_erase_stats *stats) {
+    GUARD(
+        if (stats) std::memset(stats, 0, sizeof(*stats));
+        if (path == nullptr) throw std::invalid_argument("BGKOctoMap::evict_file: path is NULL");
+        const la3dm_erase_stats s = m->map->evict_file(path, lo3, hi3, inside);
+        if (stats) *stats = s;
+        return 0;)
+}
+
 int la3dm_map_get_bbox(const la3dm_map *m, float *lo, float *hi) {
     point3f a, b;
     m->map->get_bbox(a, b);
