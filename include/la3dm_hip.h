@@ -770,6 +770,67 @@ int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *d
 int la3dm_devmap_gain_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_origins3, uint32_t n,
                              const float *d_offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                              const la3dm_gain_out *d_out, la3dm_region_info *info);
+/* Score poses: likelihood-field scoring of one scan under many candidate poses — which pose fits the map best.  Every
+ * point of the cloud is moved by every pose, its voxel resolved as search resolves it, and the squared distance from
+ * that voxel to the nearest obstacle gathered from distance_field's answer; per pose the distances are summed and the
+ * pairs counted by class.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's.
+ *   Cost volume.  d2 = distance_field(lo, dims, obstacle_mask, radius) over the same region, unchanged, with its blind
+ *     spot: obstacles outside the region are not seen.  radius lies in 1 ... LA3DM_SCORE_MAX_RADIUS (255), so every
+ *     finite d2 is <= 65 025 and fits 16 bits.
+ *   Inputs.  points3: n_points packed xyz in the sensor frame.  poses12: n_poses x 12 floats, row-major 3 x 4 [R | t].
+ *     Nothing checks that R is a rotation.
+ *   Transform.  Per axis c, w[c] = ((R[c][0] * x + R[c][1] * y) + R[c][2] * z) + t[c]: three fp32 products and three fp32
+ *     sums, each rounded on its own, in this order — the only floating-point work of the query besides the anchor's.
+ *   Classes of a (pose, point) pair, tested in this order:
+ *     LA3DM_SCORE_INVALID  some axis fails fabsf(w / resolution) < 2^30, the region's test for lo (false for NaN and inf,
+ *                          whether they come from the point or from the pose);
+ *     LA3DM_SCORE_OUTSIDE  per axis the global index is built with the anchor's own arithmetic,
+ *                            b = (int64)((double)w / (double)block_size + 524288.5),
+ *                            center = (float)(b - 524288) * block_size,
+ *                            cell = clamp((int)((w - center) / resolution + (float)(lim / 2)), 0, lim - 1),
+ *                            g = b * lim + cell,
+ *                          the voxel search resolves for w; the pair is OUTSIDE when some b is outside [0, 2^20) or some
+ *                          g - g0 is outside [0, n) of its axis;
+ *     otherwise, f the flat index of (g - g0): LA3DM_SCORE_HIT if d2[f] == 0, LA3DM_SCORE_NEAR if d2[f] is finite,
+ *                          LA3DM_SCORE_FAR if d2[f] == LA3DM_DF_FAR.
+ *   Outputs per pose p.  sum_d2[p] (mandatory) = the sum of d2[f] over the pose's HIT and NEAR pairs; counts[5 p + c]
+ *     (optional) = its pairs of class c, in the order HIT, NEAR, FAR, OUTSIDE, INVALID: they sum to n_points.  The caller
+ *     composes a score, e.g. sum_d2 + penalty * (far + outside).
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, no buffer touched, nothing reserved), in this
+ *     order: an obstacle_mask of 0 or with bits above 0x1F; a radius outside 1 ... LA3DM_SCORE_MAX_RADIUS; n_points >
+ *     LA3DM_SCORE_MAX_POINTS; n_poses > LA3DM_SCORE_MAX_POSES; n_points * n_poses > LA3DM_SCORE_MAX_PAIRS; what box
+ *     refuses for lo and dims; more than LA3DM_SCORE_MAX_CELLS voxels; with n_poses > 0 a NULL poses12, out or
+ *     out->sum_d2 and, with n_points > 0 as well, a NULL points3.
+ *   n_poses = 0 is served and writes nothing; n_points = 0 writes zeros.  An empty map answers from the definition without
+ *     a launch that reads the pool: every voxel is MISSING, so d2 is 0 everywhere if the mask holds bit 3 and FAR
+ *     everywhere otherwise; the classes of the pairs still depend on the transform.
+ *   Working storage: distance_field's 4 bytes per voxel and as many again for d2, in grow-only arenas of the devmap
+ *     (released with it; a smaller request after a larger one allocates nothing).
+ *   All sums are integers: the results equal the host form (BGKOctoMap::score_poses on a host-mode map) exactly. */
+#define LA3DM_SCORE_MAX_RADIUS 255u
+#define LA3DM_SCORE_MAX_POINTS (1u << 20)
+#define LA3DM_SCORE_MAX_POSES  (1u << 20)
+#define LA3DM_SCORE_MAX_PAIRS  (1ull << 32)
+#define LA3DM_SCORE_MAX_CELLS  (1u << 28)
+#define LA3DM_SCORE_HIT     0u
+#define LA3DM_SCORE_NEAR    1u
+#define LA3DM_SCORE_FAR     2u
+#define LA3DM_SCORE_OUTSIDE 3u
+#define LA3DM_SCORE_INVALID 4u
+typedef struct la3dm_score_out {
+    uint64_t *sum_d2;   /* [n_poses]   mandatory: sum of d2 over the pose's HIT and NEAR pairs */
+    uint32_t *counts;   /* [5 n_poses] or NULL: pairs of class HIT, NEAR, FAR, OUTSIDE, INVALID */
+} la3dm_score_out;
+/* host pointers: upload of the points and poses, the launches, download, synchronise — on the map's stream */
+int la3dm_devmap_score_poses_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *points3,
+                                  uint32_t n_points, const float *poses12, uint32_t n_poses, uint32_t obstacle_mask,
+                                  uint32_t radius, const la3dm_score_out *out, la3dm_region_info *info);
+/* device pointers (points3, poses12 and out's arrays already in HBM on the map's device, 4-byte aligned — sum_d2 too;
+ * lo3, dims3 and info stay host-side); returns when the results are complete */
+int la3dm_devmap_score_poses_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_points3,
+                                    uint32_t n_points, const float *d_poses12, uint32_t n_poses, uint32_t obstacle_mask,
+                                    uint32_t radius, const la3dm_score_out *d_out, la3dm_region_info *info);
 /* Reach: the hop distance from seed voxels through the passable voxels of a region — can a goal be got to, and in how
  * many moves.  A breadth-first wave, one launch per level.
  *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; cls(v)

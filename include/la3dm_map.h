@@ -160,6 +160,15 @@ int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dim
 int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
                    const float *offsets3, uint32_t m_dirs, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                    const la3dm_gain_out *out, la3dm_region_info *info);
+/* BGKOctoMap::score_poses: likelihood-field scoring of one scan under many poses.  Every point of points3 (sensor frame) is
+ * moved by every pose of poses12 (n_poses x 12 floats, row-major 3 x 4 [R | t]), its voxel resolved as search resolves it,
+ * and d2 = distance_field(lo, dims, obstacle_mask, radius) gathered there.  out->sum_d2 (mandatory) [n_poses] = the sum of
+ * the finite d2 per pose; out->counts [5 n_poses] = the pairs of class HIT, NEAR, FAR, OUTSIDE, INVALID.  Contract, limits
+ * and refusals: include/la3dm_hip.h (la3dm_devmap_score_poses_host).  Device-resident maps run the query on the device
+ * pool without a mirror refresh, host-mode maps on the CPU; the results are identical. */
+int la3dm_map_score_poses(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
+                          const float *poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out *out,
+                          la3dm_region_info *info);
 /* BGKOctoMap::reach: steps[v] = the least number of moves (connectivity 6, 18 or 26) from any of the seed voxels to v
  * through the passable voxels of box's region — class in pass_mask and, with clearance > 0, farther than clearance voxels
  * from every voxel of the region whose class is in obstacle_mask (distance_field's d2 == LA3DM_DF_FAR) — LA3DM_REACH_NONE

@@ -5,6 +5,7 @@ class; all work is done by libla3dm_map.so (host bookkeeping, C++) and
 libla3dm_hip.so (HIP kernels).  No Python compute path exists.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -18,6 +19,8 @@ RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
 DF_FAR = 0xFFFFFFFF                 # LA3DM_DF_FAR: beyond the radius of distance_field (dist: +inf)
 FR_MAX_CELLS = 1 << 28             # LA3DM_FR_MAX_CELLS: voxels of frontier's region padded by one on every side
 GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: voxels of gain's region, n * m rays, n * W set words
+SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS = 1 << 28, 1 << 20, 1 << 20, 1 << 32, 255   # LA3DM_SCORE_MAX_*
+SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID = range(5)   # LA3DM_SCORE_*: the columns of score_poses' counts
 REACH_NONE = 0xFFFFFFFF             # LA3DM_REACH_NONE: reach found no walk to the voxel
 REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS = 1 << 28, 1 << 16, 1 << 20   # LA3DM_REACH_MAX_*: padded voxels, max_steps, seeds
 REACH_BATCH = 32                    # LA3DM_REACH_BATCH: level launches queued between two reads of the level counts
@@ -407,6 +410,47 @@ class BGKOctoMap:
         self._chk(self._M.la3dm_map_gain(self._h, lo3.ctypes.data, d3.ctypes.data, o.ctypes.data if n else None, n,
                                          f.ctypes.data if f.shape[0] else None, f.shape[0], masks[0], masks[1], int(max_steps),
                                          C.byref(g), C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
+    def score_poses(self, lo, dims, points, poses, obstacles=("occupied",), radius=16, fields=("sum_d2", "counts")):
+        """Likelihood-field scoring of one scan under P candidate poses: every point of `points` (n, 3; sensor frame) is
+        moved by every pose of `poses` (P, 3, 4) or (P, 12), row-major [R | t], in float32 — w[c] = ((R[c][0] x + R[c][1] y)
+        + R[c][2] z) + t[c], every operation rounded on its own — its voxel resolved as search resolves it, and d2 =
+        distance_field(lo, dims, obstacles, radius) gathered there.  Returns a dict: sum_d2 (P,) uint64 = per pose the sum
+        of the finite d2, and, when named in `fields`, counts (P, 5) uint32 = its pairs of class HIT (d2 = 0), NEAR (d2
+        finite), FAR (beyond radius), OUTSIDE (the voxel is not in the region), INVALID (a coordinate the lattice cannot
+        hold: NaN, inf, |w / resolution| >= 2^30) — they sum to n; plus origin, block_key, cell as box() returns them.
+        A score is the caller's to compose, e.g. sum_d2 + penalty * (far + outside).  obstacles: as distance_field takes
+        them; radius: 1 .. 255 voxels.  Obstacles outside the region are not seen.  At most 2^28 voxels, 2^20 points, 2^20
+        poses and 2^32 pairs.  A device-resident map runs the query on the device pool (no host mirror refresh); a
+        host-mode map runs it on the CPU, with identical results."""
+        lo3, d3, d, cells = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= SCORE_MAX_CELLS else 0)(d[0] * d[1] * d[2]))
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(poses, np.float32)
+        if T.ndim < 2 or T.shape[1:] not in ((3, 4), (12,)):
+            raise ValueError("score_poses: poses must have the shape (P, 3, 4) or (P, 12)")
+        T = T.reshape(-1, 12)
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - {"sum_d2", "counts"}
+        if bad:
+            raise ValueError(f"score_poses: unknown fields {sorted(bad)}")
+        if isinstance(obstacles, str):
+            obstacles = (obstacles,)
+        mask = int(obstacles) if isinstance(obstacles, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(obstacles))
+        n, P = pts.shape[0], T.shape[0]
+        if not all(0 <= v < 2 ** 32 for v in (mask, int(radius), n, P)):
+            raise ValueError("score_poses: obstacles, radius and the numbers of points and poses must fit 32 bits")
+        # (a request the call refuses gets one-element arrays: it is refused before a buffer is looked at)
+        served = cells > 0 and n <= SCORE_MAX_POINTS and P <= SCORE_MAX_POSES and n * P <= SCORE_MAX_PAIRS
+        out = dict(sum_d2=np.empty(P if served else 1, np.uint64))
+        if "counts" in fields:
+            out["counts"] = np.empty((P, 5) if served else (1, 5), np.uint32)
+        o = _lib.ScoreOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.ScoreOut._fields_])
+        info = _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_score_poses(self._h, lo3.ctypes.data, d3.ctypes.data, pts.ctypes.data if n else None, n,
+                                                T.ctypes.data if P else None, P, mask, int(radius), C.byref(o), C.byref(info)))
         out.update(self._region_info(info))
         return out
 
@@ -936,6 +980,21 @@ def load_map(path, device=0, device_resident=True):
     if device >= 0 and m.is_device_resident() != bool(device_resident):
         m.set_device_resident(bool(device_resident))
     return m.load(path)
+
+
+def poses_xyz_yaw(center, dxyz_dyaw):
+    """Candidate poses for score_poses: row i of dxyz_dyaw = (dx, dy, dz, dyaw) gives the pose that rotates about `center`
+    by dyaw (radians, about z) and then translates by (dx, dy, dz).  Returns (P, 3, 4) float32 [R | t].  Everything is
+    computed in double and rounded to float32 once per entry — c = cos(dyaw), s = sin(dyaw) from libm (math.cos,
+    math.sin), R = [[c, -s, 0], [s, c, 0], [0, 0, 1]], t = ((cx + dx) - (c * cx - s * cy), (cy + dy) - (s * cx + c * cy),
+    dz) — so a C program that calls libm's cos and sin and does the same double arithmetic builds the same bits."""
+    cx, cy = float(center[0]), float(center[1])
+    rows = np.asarray(dxyz_dyaw, np.float64).reshape(-1, 4)
+    out = np.zeros((rows.shape[0], 3, 4), np.float32)
+    for i, (dx, dy, dz, dyaw) in enumerate(rows.tolist()):
+        c, s = math.cos(dyaw), math.sin(dyaw)
+        out[i] = [[c, -s, 0.0, (cx + dx) - (c * cx - s * cy)], [s, c, 0.0, (cy + dy) - (s * cx + c * cy)], [0.0, 0.0, 1.0, dz]]
+    return out
 
 
 def follow_parents(parent, dims, index):

@@ -31,6 +31,7 @@
 #include "devmap_distance.h"
 #include "devmap_frontier.h"
 #include "devmap_gain.h"
+#include "devmap_score.h"
 #include "devmap_reach.h"
 #include "devmap_travel.h"
 #include "devmap_clusters.h"
@@ -89,6 +90,7 @@ struct la3dm_devmap {
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
+    Arena score_work;             // score_poses: d2 (4 bytes per voxel), then the chunks' partial records (devmap_score.h)
     Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
     Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
     Arena clusters_work;          // clusters: two brick-major label buffers, side / active per brick, the round counts, sizes, flags, numbers (devmap_clusters.h)
@@ -690,7 +692,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->score_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3286,6 +3288,97 @@ int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *d
                            const float *offsets3, uint32_t m, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                            const la3dm_gain_out *out, la3dm_region_info *info) {
     return gain_query(dm, true, "la3dm_devmap_gain_host", lo3, dims3, origins3, n, offsets3, m, count_mask, stop_mask, max_steps, out, info);
+}
+
+// ---- score_poses: one scan under many poses against the distance field of a region (devmap_score.h) ----------------
+
+// Stage 1 (distance_field into working storage) and stage 2 on the map's stream; every pointer is device memory.  An
+// empty map has no stage 1: every voxel costs 0 or FAR.
+static int score_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_points3, uint32_t n_points, const float *d_poses12,
+                        uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out &o) {
+    hipStream_t st = dm->ctx->stream;
+    const size_t n = (size_t)g.total;
+    ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    a.points = d_points3;
+    a.poses = d_poses12;
+    a.n_points = n_points;
+    a.n_poses = n_poses;
+    // Few poses: the cloud is cut into chunks until about four workgroups per compute unit exist, 256 points a chunk at
+    // least; the chunks' records are then added by dm_score_fold.
+    a.chunks = std::max(1u, std::min(cdiv(1024, n_poses), cdiv(n_points, 256)));
+    a.per_chunk = cdiv(cdiv(n_points, a.chunks), 256) * 256u;
+    a.resolution = dm->ctx->p.resolution;
+    a.block_size = dm->block_size;
+    a.lim = 1 << (dm->depth - 1);
+    for (int k = 0; k < 3; ++k) {
+        a.g0[k] = g.g0[k];
+        a.dims[k] = g.dims[k];
+    }
+    const size_t d2_bytes = (4 * n + 15) & ~(size_t)15;
+    DM_RESERVE(dm->score_work, d2_bytes + (a.chunks > 1 ? 4ull * kScoreWords * n_poses * a.chunks : 0));
+    a.partial = (uint32_t *)((char *)dm->score_work.ptr + d2_bytes);
+    a.sum_d2 = (uint32_t *)o.sum_d2;
+    a.counts = o.counts;
+    if (dm->n_blocks == 0) {
+        a.fill = ((obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : LA3DM_DF_FAR;
+    } else {
+        DM_RESERVE(dm->df_work, 4ull * n);
+        la3dm_distance_out dd;
+        dd.d2 = (uint32_t *)dm->score_work.ptr;
+        dd.dist = nullptr;
+        distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, dd);
+        a.cost = dd.d2;
+    }
+    // (n_poses chunks <= 2^20 + 1024 workgroups)
+    hipLaunchKernelGGL(dm_score_pairs, dim3(n_poses * a.chunks), dim3(256), 0, st, a);
+    if (a.chunks > 1) hipLaunchKernelGGL(dm_score_fold, dim3(n_poses), dim3(64), 0, st, a);
+    DM_TRY(hipGetLastError());
+    return LA3DM_OK;
+}
+
+static int score_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const float *points3,
+                       uint32_t n_points, const float *poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius,
+                       const la3dm_score_out *out, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::score_check(obstacle_mask, radius, n_points, n_poses)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kScore, true, true, who, g));   // lo, dims, the limit and the range: before any buffer
+    DM_OK(refuse(dm, who, la3dm_region::score_buffers(n_points, n_poses, points3 != nullptr, poses12 != nullptr, out != nullptr,
+                                                      out && out->sum_d2, "->")));
+    if (info) *info = g.info;
+    if (n_poses == 0) return LA3DM_OK;
+    hipStream_t st = dm->ctx->stream;
+    la3dm_score_out o = *out;
+    if (n_points == 0) {   // no pair: zeros, no launch
+        const Fill f{dm, host};
+        DM_OK(f.bytes(o.sum_d2, 0, 8ull * n_poses));
+        DM_OK(f.bytes(o.counts, 0, 20ull * n_poses));
+    } else {
+        Stage s(dm, host);
+        s.in(points3, 3ull * n_points);
+        s.in(poses12, 12ull * n_poses);
+        s.out(o.sum_d2, n_poses);
+        s.out(o.counts, 5ull * n_poses);
+        DM_OK(s.reserve());
+        DM_OK(score_launch(dm, g, points3, n_points, poses12, n_poses, obstacle_mask, radius, o));
+        DM_OK(s.download());
+    }
+    DM_TRY(hipStreamSynchronize(st));
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_score_poses_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_points3, uint32_t n_points,
+                                    const float *d_poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius,
+                                    const la3dm_score_out *d_out, la3dm_region_info *info) {
+    return score_query(dm, false, "la3dm_devmap_score_poses_device", lo3, dims3, d_points3, n_points, d_poses12, n_poses, obstacle_mask, radius,
+                       d_out, info);
+}
+
+int la3dm_devmap_score_poses_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
+                                  const float *poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius,
+                                  const la3dm_score_out *out, la3dm_region_info *info) {
+    return score_query(dm, true, "la3dm_devmap_score_poses_host", lo3, dims3, points3, n_points, poses12, n_poses, obstacle_mask, radius, out,
+                       info);
 }
 
 // ---- reach: hop distance from seeds through the passable voxels of a region (devmap_reach.h) -------------------------

@@ -1712,6 +1712,56 @@ void BGKOctoMap::gain(const float *lo3, const uint32_t *dims3, const float *orig
     }
 }
 
+// ---- score_poses.  The host form below is the definition; the device kernels (csrc/devmap_score.h) compile the same
+// transform and point-to-voxel inlines (region_contract.h) and reproduce it exactly: everything after them is integers.
+void BGKOctoMap::score_poses(const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points, const float *poses12,
+                             uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out &out,
+                             la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_score_poses_host(dmap, lo3, dims3, points3, n_points, poses12, n_poses, obstacle_mask, radius, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::score_poses: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::score_poses";
+    std::string refusal = la3dm_region::score_check(obstacle_mask, radius, n_points, n_poses);
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kScore, true, "score_poses", g0, inf);
+    refusal = la3dm_region::score_buffers(n_points, n_poses, points3 != nullptr, poses12 != nullptr, true, out.sum_d2 != nullptr, ".");
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    if (info) *info = inf;
+    if (n_poses == 0) return;
+    std::vector<uint32_t> d2;
+    if (n_points > 0) {
+        d2.resize((size_t)dims3[0] * dims3[1] * dims3[2]);
+        la3dm_distance_out dd;
+        dd.d2 = d2.data();
+        dd.dist = nullptr;
+        distance_field(lo3, dims3, obstacle_mask, radius, dd, nullptr);
+    }
+    const int lim = 1 << (block_depth - 1);
+#pragma omp parallel for schedule(static)
+    for (uint32_t p = 0; p < n_poses; ++p) {
+        uint32_t c[5] = {0, 0, 0, 0, 0};
+        uint64_t sum = 0;
+        for (uint32_t i = 0; i < n_points; ++i) {
+            const float *q = points3 + 3 * (size_t)i;
+            uint32_t f = 0;
+            uint32_t cls = la3dm_region::score_voxel(poses12 + 12 * (size_t)p, q[0], q[1], q[2], resolution, block_size, lim, g0, dims3, f);
+            if (cls == LA3DM_SCORE_HIT) {
+                cls = la3dm_region::score_class(d2[f]);
+                if (cls != LA3DM_SCORE_FAR) sum += d2[f];
+            }
+            ++c[cls];
+        }
+        out.sum_d2[p] = sum;
+        if (out.counts)
+            for (int k = 0; k < 5; ++k) out.counts[5 * (size_t)p + k] = c[k];
+    }
+}
+
 namespace {
 // heightMapColor, include/common/markerarray_pub.h:21-76 (s = v = 1)
 void height_map_color(double h, float *rgba) {

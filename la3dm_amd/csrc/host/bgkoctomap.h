@@ -471,6 +471,17 @@ public:
     void gain(const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n, const float *offsets3, uint32_t m,
               uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, const la3dm_gain_out &out,
               la3dm_region_info *info = nullptr) const;
+    /// Likelihood-field scoring of one scan under many poses (contract: include/la3dm_hip.h, la3dm_devmap_score_poses_host):
+    /// every point of points3 (sensor frame) is moved by every pose of poses12 (row-major 3 x 4 [R | t], fp32, op by op as
+    /// the contract spells it), its voxel resolved as search resolves it, and d2 = distance_field(lo, dims, obstacle_mask,
+    /// radius) gathered there.  out.sum_d2[p] = the sum of the finite d2 of pose p; out.counts[5 p + c] = its pairs of class
+    /// HIT (d2 = 0), NEAR (finite), FAR, OUTSIDE (the voxel is not in the region), INVALID (a coordinate the lattice cannot
+    /// hold).  Bad arguments throw std::invalid_argument.  A device-resident map runs the query on the device pool (no
+    /// mirror refresh); a host-mode map runs its own distance_field and a plain loop: that form is the definition, and both
+    /// give the same integers.
+    void score_poses(const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points, const float *poses12,
+                     uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out &out,
+                     la3dm_region_info *info = nullptr) const;
     /// Reach over box's region (contract: include/la3dm_hip.h, la3dm_devmap_reach_host): steps[v] = the least number of
     /// moves (connectivity 6, 18 or 26) from any seed to v through passable voxels of the region — class (box's cls) in
     /// `pass_mask` and, with clearance > 0, distance_field(obstacle_mask, radius = clearance) FAR — LA3DM_REACH_NONE where

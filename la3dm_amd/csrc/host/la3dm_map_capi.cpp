@@ -412,6 +412,17 @@ int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, 
         return 0;)
 }
 
+int la3dm_map_score_poses(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
+                          const float *poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out *out,
+                          la3dm_region_info *info) {
+    GUARD(
+        la3dm_score_out none;
+        none.sum_d2 = nullptr;
+        none.counts = nullptr;
+        m->map->score_poses(lo3, dims3, points3, n_points, poses12, n_poses, obstacle_mask, radius, out ? *out : none, info);
+        return 0;)
+}
+
 int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                     uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
                     const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,

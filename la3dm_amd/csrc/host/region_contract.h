@@ -1,7 +1,8 @@
 // region_contract.h — what a valid region query is (include/la3dm_hip.h "Region"), once for the device library
 // (devmap.hip) and the host map (bgkoctomap.cpp): the limits of each query, their order, their texts and the anchor
-// arithmetic.  Host code only.  A check answers with the text of the refusal, without the caller's prefix, or with an
-// empty string; how a refusal is reported (an error code and a stored text, an exception) is the caller's business.
+// arithmetic.  Host code, but for the inlines marked LA3DM_HD, which the device kernels compile as well (score_poses:
+// csrc/devmap_score.h).  A check answers with the text of the refusal, without the caller's prefix, or with an empty
+// string; how a refusal is reported (an error code and a stored text, an exception) is the caller's business.
 #ifndef LA3DM_REGION_CONTRACT_H
 #define LA3DM_REGION_CONTRACT_H
 
@@ -11,6 +12,12 @@
 #include <string>
 
 #include "../../../include/la3dm_hip.h"
+
+#if defined(__HIPCC__)
+#define LA3DM_HD __host__ __device__
+#else
+#define LA3DM_HD
+#endif
 
 namespace la3dm_region {
 
@@ -33,6 +40,7 @@ constexpr Query kTravel = {LA3DM_TRAVEL_MAX_CELLS, "dims: more than LA3DM_TRAVEL
                            LA3DM_TRAVEL_BRICK};
 // clusters: box's own limit here; the axis and brick limits follow the region's checks (clusters_region_check)
 constexpr Query kClusters = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, false, ""};
+constexpr Query kScore = {LA3DM_SCORE_MAX_CELLS, "dims: more than LA3DM_SCORE_MAX_CELLS (2^28) voxels", false, false, ""};
 
 struct Anchor {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
@@ -41,6 +49,25 @@ struct Anchor {
     int64_t block_key;
     uint64_t total;      // voxels of the region (columns: columns)
 };
+
+// One axis of the voxel that `search` and the RayCaster resolve for the coordinate w: the block field b
+// (block_to_hash_key: the one double operation), the centre of that block (hash_key_to_block) and the cell inside it
+// (Block::get_index: truncation, clamped), lim = 2^(block_depth - 1) cells per axis.  The global index is b * lim + cell.
+// The caller has tested |w / resolution| < 2^30 (axis_in_range) before: no conversion below leaves its integer type.
+struct AxisVoxel {
+    long long b;
+    float center;
+    int cell;
+};
+LA3DM_HD inline bool axis_in_range(float w, float resolution) { return fabsf(w / resolution) < 1073741824.0f; }   // false for NaN and inf
+LA3DM_HD inline AxisVoxel axis_voxel(float w, float resolution, float block_size, int lim) {
+    AxisVoxel v;
+    v.b = (long long)((double)w / (double)block_size + 524288.5);
+    v.center = (float)(v.b - 524288) * block_size;
+    const int t = (int)((w - v.center) / resolution + (float)(lim / 2));
+    v.cell = t < 0 ? 0 : (t > lim - 1 ? lim - 1 : t);
+    return v;
+}
 
 // Every check of a region in the contract's order — lo, dims, the limits and the block-field range before any buffer is
 // looked at — and the anchor, the only floating-point work of a query.  `member` is "->" or ".": how the caller's texts
@@ -65,22 +92,21 @@ inline std::string resolve(const Query &q, const float *lo, const uint32_t *dims
     }
     a.total = q.columns ? ncol : ncol * dims[2];
     const long long lim = 1ll << (block_depth - 1), top = 1ll << 20;
-    long long b[3];
+    AxisVoxel v[3];
     for (int k = 0; k < 3; ++k) {   // (a key only holds fields that fit it: test them before one is built)
-        b[k] = (long long)((double)lo[k] / (double)block_size + 524288.5);   // block_to_hash_key, one axis
-        if (b[k] < 0 || b[k] >= top) return "lo: the block field leaves [0, 2^20)";
+        v[k] = axis_voxel(lo[k], resolution, block_size, (int)lim);
+        if (v[k].b < 0 || v[k].b >= top) return "lo: the block field leaves [0, 2^20)";
     }
     a.block_key = 0;
     for (int k = 0; k < 3; ++k) {
-        a.center[k] = (float)(b[k] - 524288) * block_size;                                  // hash_key_to_block
-        const int t = (int)((lo[k] - a.center[k]) / resolution + (float)(lim / 2));         // Block::get_index: truncation, clamped
-        a.cell[k] = std::max(0, std::min(t, (int)lim - 1));
-        const long long first = b[k] * lim + a.cell[k], last = first + (long long)dims[k] - 1;
+        a.center[k] = v[k].center;
+        a.cell[k] = v[k].cell;
+        const long long first = v[k].b * lim + a.cell[k], last = first + (long long)dims[k] - 1;
         if (last / lim >= top) return "dims: the region's block fields leave [0, 2^20)";
         if (q.padded && (first == 0 || (last + 1) / lim >= top))
             return "dims: the block fields of the region padded by one voxel leave [0, 2^20)";
         a.g0[k] = (uint32_t)first;
-        a.block_key = (a.block_key << 20) | b[k];
+        a.block_key = (a.block_key << 20) | v[k].b;
     }
     if (!has_out) return "out is NULL";
     if (!has_mandatory) {
@@ -116,6 +142,54 @@ inline std::string gain_check(uint32_t count_mask, uint32_t stop_mask, uint32_t 
     if ((uint64_t)n * m > LA3DM_GAIN_MAX_RAYS) return "n * m: more than LA3DM_GAIN_MAX_RAYS (2^28) rays";
     return "";
 }
+
+// ---- score_poses (contract: include/la3dm_hip.h, la3dm_devmap_score_poses_host) ----
+// the checks of score_poses' own arguments, before the region's
+inline std::string score_check(uint32_t obstacle_mask, uint32_t radius, uint32_t n_points, uint32_t n_poses) {
+    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu)) return "obstacle_mask must hold at least one of the bits 0x1F and no other";
+    if (radius == 0 || radius > LA3DM_SCORE_MAX_RADIUS) return "radius must lie in [1, LA3DM_SCORE_MAX_RADIUS (255)]";
+    if (n_points > LA3DM_SCORE_MAX_POINTS) return "n_points: more than LA3DM_SCORE_MAX_POINTS (2^20) points";
+    if (n_poses > LA3DM_SCORE_MAX_POSES) return "n_poses: more than LA3DM_SCORE_MAX_POSES (2^20) poses";
+    if ((uint64_t)n_points * n_poses > LA3DM_SCORE_MAX_PAIRS) return "n_points * n_poses: more than LA3DM_SCORE_MAX_PAIRS (2^32) pairs";
+    return "";
+}
+
+// the checks that follow the region's: the buffers (`member` as in resolve)
+inline std::string score_buffers(uint32_t n_points, uint32_t n_poses, bool has_points, bool has_poses, bool has_out, bool has_sum,
+                                 const char *member) {
+    if (n_poses == 0) return "";
+    if (!has_poses) return "poses12 is NULL";
+    if (!has_out) return "out is NULL";
+    if (!has_sum) return std::string("out") + member + "sum_d2 must not be NULL";
+    if (n_points > 0 && !has_points) return "points3 is NULL";
+    return "";
+}
+
+// One coordinate of a point under a pose, row = the axis' four entries of [R | t]: three fp32 products and three fp32
+// sums, each rounded on its own, in this order (both builds compile with -ffp-contract=off).
+LA3DM_HD inline float pose_axis(const float *row, float x, float y, float z) { return ((row[0] * x + row[1] * y) + row[2] * z) + row[3]; }
+
+// The class of a (pose, point) pair up to the cost volume: LA3DM_SCORE_INVALID, LA3DM_SCORE_OUTSIDE, or LA3DM_SCORE_HIT
+// for a pair whose voxel lies in the region — f is then its flat index, and d2[f] decides between HIT, NEAR and FAR
+// (score_class).
+LA3DM_HD inline uint32_t score_voxel(const float *pose12, float x, float y, float z, float resolution, float block_size, int lim,
+                                     const uint32_t *g0, const uint32_t *dims, uint32_t &f) {
+    float w[3];
+    for (int c = 0; c < 3; ++c) w[c] = pose_axis(pose12 + 4 * c, x, y, z);
+    for (int c = 0; c < 3; ++c)
+        if (!axis_in_range(w[c], resolution)) return LA3DM_SCORE_INVALID;
+    uint32_t at[3];
+    for (int c = 0; c < 3; ++c) {
+        const AxisVoxel v = axis_voxel(w[c], resolution, block_size, lim);
+        if (v.b < 0 || v.b >= (1ll << 20)) return LA3DM_SCORE_OUTSIDE;
+        const long long d = v.b * lim + v.cell - (long long)g0[c];
+        if (d < 0 || d >= (long long)dims[c]) return LA3DM_SCORE_OUTSIDE;
+        at[c] = (uint32_t)d;
+    }
+    f = (at[0] * dims[1] + at[1]) * dims[2] + at[2];
+    return LA3DM_SCORE_HIT;
+}
+LA3DM_HD inline uint32_t score_class(uint32_t d2) { return d2 == 0 ? LA3DM_SCORE_HIT : (d2 != LA3DM_DF_FAR ? LA3DM_SCORE_NEAR : LA3DM_SCORE_FAR); }
 
 // words of one viewpoint's set
 inline uint32_t gain_words(uint64_t total) { return (uint32_t)((total + 31) / 32); }
