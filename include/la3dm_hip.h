@@ -987,6 +987,87 @@ int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t 
 int la3dm_devmap_travel_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
                                const la3dm_travel_params *params, const uint32_t *d_targets, uint32_t n_targets,
                                const la3dm_travel_out *d_out, la3dm_travel_stats *stats, la3dm_region_info *info);
+/* Score paths: cost and clearance of many candidate trajectories — the local planner's question.  Every path is a
+ * polyline of waypoints; it is walked voxel by voxel through the region, the walk stops where it leaves the region or
+ * comes too close to an obstacle, and what was walked is charged in travel's units, so that a walk costs here what it
+ * costs there.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's.
+ *   Distance.  R = max(1, clearance, soft_radius) and d2 = distance_field(lo, dims, obstacle_mask, radius = R) over the
+ *     same region, unchanged, with its blind spot: obstacles outside the region are not seen.
+ *   Inputs.  ways3: n_paths x n_way x 3 floats, world frame, the same n_way >= 1 for every path of a call; a shorter
+ *     path is padded by repeating its last waypoint.  params: obstacle_mask, clearance, soft_radius, penalty and
+ *     move_cost[3] mean what they mean in la3dm_travel_params; max_steps bounds the walk.
+ *   Waypoint voxels.  Per waypoint and axis c the coordinate w is tested as the region tests lo, fabsf(w / resolution) <
+ *     2^30 (false for NaN and inf), and resolved with the anchor's own arithmetic (score_poses: b, center, cell), G[c] =
+ *     b * lim + cell as a 64-bit integer.  b is not restricted to [0, 2^20): such a voxel is simply outside the region.
+ *     If any coordinate of any waypoint of a path fails the range test the whole path is LA3DM_PATH_INVALID, wherever the
+ *     waypoint lies, also beyond a later stop: flags = INVALID, cost 0, steps 0, stop LA3DM_PATH_NONE, min_d2
+ *     LA3DM_DF_FAR, ways 0.  This is the only floating-point work of the query besides the anchor's.
+ *   The walk (integers).  For segment k = 1 ... n_way - 1: d = G[k] - G[k - 1], n_k = max_c |d[c]|, off[0] = 0, off[k] =
+ *     off[k - 1] + n_k, T = off[n_way - 1].  The voxel of ordinal 0 is G[0]; for off[k - 1] < o <= off[k], with s = o -
+ *     off[k - 1], v_o[c] = G[k - 1][c] + floor((2 s d[c] + n_k) / (2 n_k)): a floor division (the numerator can be
+ *     negative) in 64 bits.  A segment with n_k = 0 contributes no voxel.  Hence: consecutive voxels differ by at most 1
+ *     per axis and in at least one axis (the axis of n_k moves by exactly 1), so the walk is a 26-connected walk in
+ *     travel's sense; v at s = n_k is G[k]; and the walk of the reversed waypoint list is the reversed walk (floor((2 (n
+ *     - s) (-d) + n) / (2 n)) = -d + floor((2 s d + n) / (2 n))).
+ *   Stop.  E = min(T, max_steps).  stop = the smallest ordinal in [0, E] whose voxel is outside the region
+ *     (LA3DM_PATH_LEFT) or blocked, d2 != LA3DM_DF_FAR and d2 <= clearance^2 (LA3DM_PATH_BLOCKED); with clearance 0 that
+ *     is the obstacle voxel itself.  (travel_entry leaves class tests to pass_mask; here the obstacle classes block.)
+ *     LA3DM_PATH_TRUNCATED is set iff there is no stop and T > max_steps.  L = stop if there is one, else E + 1.
+ *   Outputs per path.  cost (mandatory, 64 bits) = the sum over o = 1 ... L - 1 of move_cost[nz(o) - 1] + pen(d2[v_o]),
+ *     nz(o) the number of non-zero components of v_o - v_(o-1) and pen travel's formula; voxel 0 is not charged, as
+ *     travel's seed is not.  steps = L.  stop = the ordinal, or LA3DM_PATH_NONE.  min_d2 = the minimum of d2[v_o] over o
+ *     < L, LA3DM_DF_FAR if none.  ways = the number of waypoints k with off[k] < L: how many waypoints the robot reaches.
+ *     flags (uint8) = the LA3DM_PATH_* bits.  All outputs but cost are optional.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written, nothing reserved), in this
+ *     order: a NULL params; an obstacle_mask of 0 or with bits above 0x1F; clearance or soft_radius > LA3DM_DF_MAX_RADIUS;
+ *     soft_radius > 0 with penalty 0; penalty > LA3DM_TRAVEL_MAX_PENALTY; a move_cost of 0 or > LA3DM_TRAVEL_MAX_MOVE;
+ *     max_steps outside 1 ... LA3DM_PATHS_MAX_STEPS; n_way outside 1 ... LA3DM_PATHS_MAX_WAY; n_paths >
+ *     LA3DM_PATHS_MAX_PATHS; n_paths * n_way > LA3DM_PATHS_MAX_WAYPOINTS; with n_paths > 0 a NULL ways3, out or
+ *     out->cost.  Then what box refuses for lo and dims, and more than LA3DM_DF_MAX_CELLS voxels.
+ *   n_paths = 0 is served and writes nothing.  An empty map answers from the definition without a launch that reads the
+ *     pool: every voxel is MISSING, so d2 is 0 everywhere if the mask holds bit 3 and FAR everywhere otherwise.
+ *   No sum overflows: a path charges at most 2^20 steps of at most 2^17 each.
+ *   Working storage: distance_field's 4 bytes per voxel and as many again for d2, in grow-only arenas of the devmap
+ *     (score_poses' own; released with it; a smaller request after a larger one allocates nothing).
+ *   Everything after the waypoint voxels is integers: the results equal the host form (BGKOctoMap::score_paths on a
+ *     host-mode map, a plain loop) exactly.
+ *   Device form (csrc/devmap_paths.h): one wave per path, four paths per workgroup; the waypoint voxels and the offsets
+ *     (saturated at max_steps + 1) live in LDS, lanes take ordinals in ascending chunks of 64. */
+#define LA3DM_PATHS_MAX_STEPS     (1u << 20)
+#define LA3DM_PATHS_MAX_WAY       1024u
+#define LA3DM_PATHS_MAX_PATHS     (1u << 20)
+#define LA3DM_PATHS_MAX_WAYPOINTS (1u << 26)
+#define LA3DM_PATH_BLOCKED   1u
+#define LA3DM_PATH_LEFT      2u
+#define LA3DM_PATH_TRUNCATED 4u
+#define LA3DM_PATH_INVALID   8u
+#define LA3DM_PATH_NONE      0xFFFFFFFFu
+typedef struct la3dm_paths_params {
+    uint32_t obstacle_mask;
+    uint32_t clearance;      /* voxels; 0: only the obstacle voxels themselves block */
+    uint32_t soft_radius;    /* voxels; 0: no penalty */
+    uint32_t penalty;        /* cost units at distance 0 */
+    uint32_t move_cost[3];   /* moves with 1, 2, 3 non-zero components */
+    uint32_t max_steps;      /* 1 ... LA3DM_PATHS_MAX_STEPS */
+} la3dm_paths_params;
+typedef struct la3dm_paths_out {
+    uint64_t *cost;     /* [n_paths] mandatory */
+    uint32_t *steps;    /* [n_paths] or NULL: L, the voxels walked */
+    uint32_t *stop;     /* [n_paths] or NULL: the ordinal of the stop, or LA3DM_PATH_NONE */
+    uint32_t *min_d2;   /* [n_paths] or NULL */
+    uint32_t *ways;     /* [n_paths] or NULL: waypoints reached */
+    uint8_t *flags;     /* [n_paths] or NULL: LA3DM_PATH_* */
+} la3dm_paths_out;
+/* host pointers: upload of the waypoints, the launches, download, synchronise — on the map's stream */
+int la3dm_devmap_score_paths_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *ways3, uint32_t n_paths,
+                                  uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *out,
+                                  la3dm_region_info *info);
+/* device pointers (ways3 and out's arrays already in HBM on the map's device, 4-byte aligned — cost too; flags any
+ * alignment; lo3, dims3, params and info stay host-side); returns when the results are complete */
+int la3dm_devmap_score_paths_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_ways3, uint32_t n_paths,
+                                    uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *d_out,
+                                    la3dm_region_info *info);
 /* Clusters: the connected groups of a region's member voxels, optionally confined to tiles and cut at a minimum size —
  * a dense label and one record per cluster (first voxel, size, bounding box, coordinate sums, a representative member).
  *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; cls(v)

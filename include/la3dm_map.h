@@ -169,6 +169,14 @@ int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, 
 int la3dm_map_score_poses(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
                           const float *poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out *out,
                           la3dm_region_info *info);
+/* BGKOctoMap::score_paths: cost and clearance of many candidate trajectories.  Every path of ways3 (n_paths x n_way x 3
+ * floats, world frame; a shorter path repeats its last waypoint) is walked voxel by voxel through box's region against d2 =
+ * distance_field(lo, dims, obstacle_mask, max(1, clearance, soft_radius)); out->cost (mandatory) [n_paths] = travel's cost
+ * of the walk up to its stop; out->steps, stop, min_d2, ways, flags (LA3DM_PATH_*) [n_paths] are optional.  Contract, limits
+ * and refusals: include/la3dm_hip.h (la3dm_devmap_score_paths_host).  Device-resident maps run the query on the device
+ * pool without a mirror refresh, host-mode maps on the CPU; the results are identical. */
+int la3dm_map_score_paths(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *ways3, uint32_t n_paths,
+                          uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *out, la3dm_region_info *info);
 /* BGKOctoMap::reach: steps[v] = the least number of moves (connectivity 6, 18 or 26) from any of the seed voxels to v
  * through the passable voxels of box's region — class in pass_mask and, with clearance > 0, farther than clearance voxels
  * from every voxel of the region whose class is in obstacle_mask (distance_field's d2 == LA3DM_DF_FAR) — LA3DM_REACH_NONE

@@ -5,6 +5,8 @@ from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR
 from .bgkoctomap import GAIN_MAX_CELLS, GAIN_MAX_RAYS, GAIN_MAX_WORDS  # noqa: F401
 from .bgkoctomap import SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS, poses_xyz_yaw  # noqa: F401
 from .bgkoctomap import SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID  # noqa: F401
+from .bgkoctomap import PATH_BLOCKED, PATH_LEFT, PATH_TRUNCATED, PATH_INVALID, PATH_NONE  # noqa: F401
+from .bgkoctomap import PATHS_MAX_STEPS, PATHS_MAX_WAY, PATHS_MAX_PATHS, PATHS_MAX_WAYPOINTS  # noqa: F401
 from .bgkoctomap import REACH_NONE, REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS, REACH_BATCH  # noqa: F401
 from .bgkoctomap import TRAVEL_NONE, TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_MOVE, TRAVEL_MAX_PENALTY, TRAVEL_MAX_SEEDS  # noqa: F401
 from .bgkoctomap import TRAVEL_MAX_ROUNDS, TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH, follow_parents  # noqa: F401

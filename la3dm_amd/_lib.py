@@ -101,6 +101,15 @@ class ScoreOut(C.Structure):     # la3dm_score_out
     _fields_ = [(k, C.c_void_p) for k in ("sum_d2", "counts")]
 
 
+class PathsParams(C.Structure):  # la3dm_paths_params
+    _fields_ = [("obstacle_mask", C.c_uint32), ("clearance", C.c_uint32), ("soft_radius", C.c_uint32), ("penalty", C.c_uint32),
+                ("move_cost", C.c_uint32 * 3), ("max_steps", C.c_uint32)]
+
+
+class PathsOut(C.Structure):     # la3dm_paths_out
+    _fields_ = [(k, C.c_void_p) for k in ("cost", "steps", "stop", "min_d2", "ways", "flags")]
+
+
 class ReachOut(C.Structure):     # la3dm_reach_out
     _fields_ = [(k, C.c_void_p) for k in ("steps", "target_steps")]
 
@@ -171,7 +180,8 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_columns_host", "la3dm_devmap_columns_device", "la3dm_devmap_distance_host",
                "la3dm_devmap_distance_device", "la3dm_devmap_frontier_host", "la3dm_devmap_frontier_device",
                "la3dm_devmap_gain_host", "la3dm_devmap_gain_device", "la3dm_devmap_score_poses_host",
-               "la3dm_devmap_score_poses_device", "la3dm_devmap_reach_host",
+               "la3dm_devmap_score_poses_device", "la3dm_devmap_score_paths_host", "la3dm_devmap_score_paths_device",
+               "la3dm_devmap_reach_host",
                "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device",
                "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device",
                "la3dm_devmap_pack_host", "la3dm_devmap_unpack_host", "la3dm_pack_info", "la3dm_devmap_merge_host",
@@ -189,6 +199,7 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth",
                "la3dm_map_raycast_many", "la3dm_map_mirror_syncs", "la3dm_map_box", "la3dm_map_columns",
                "la3dm_map_distance_field", "la3dm_map_frontier", "la3dm_map_gain", "la3dm_map_score_poses", "la3dm_map_reach",
+               "la3dm_map_score_paths",
                "la3dm_map_travel", "la3dm_map_clusters", "la3dm_map_pack", "la3dm_map_unpack", "la3dm_map_save",
                "la3dm_map_load", "la3dm_map_merge", "la3dm_map_merge_file", "la3dm_map_pack_region",
                "la3dm_map_erase_region", "la3dm_map_evict", "la3dm_map_evict_file"]
@@ -290,6 +301,11 @@ def hip():
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 3 + \
                          [C.POINTER(ScoreOut), C.POINTER(RegionInfo)]
         for form in ("host", "device"):
+            f = getattr(L, f"la3dm_devmap_score_paths_{form}")
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PathsParams),
+                          C.POINTER(PathsOut), C.POINTER(RegionInfo)]
+        for form in ("host", "device"):
             f = getattr(L, f"la3dm_devmap_reach_{form}")
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + \
@@ -375,6 +391,9 @@ def maplib():
         M.la3dm_map_score_poses.restype = C.c_int
         M.la3dm_map_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 3 + \
                                            [C.POINTER(ScoreOut), C.POINTER(RegionInfo)]
+        M.la3dm_map_score_paths.restype = C.c_int
+        M.la3dm_map_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PathsParams),
+                                           C.POINTER(PathsOut), C.POINTER(RegionInfo)]
         M.la3dm_map_reach.restype = C.c_int
         M.la3dm_map_reach.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + \
                                      [C.c_void_p, C.c_uint32, C.POINTER(ReachOut), C.POINTER(ReachStats), C.POINTER(RegionInfo)]

@@ -21,6 +21,9 @@ FR_MAX_CELLS = 1 << 28             # LA3DM_FR_MAX_CELLS: voxels of frontier's re
 GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: voxels of gain's region, n * m rays, n * W set words
 SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS = 1 << 28, 1 << 20, 1 << 20, 1 << 32, 255   # LA3DM_SCORE_MAX_*
 SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID = range(5)   # LA3DM_SCORE_*: the columns of score_poses' counts
+PATH_BLOCKED, PATH_LEFT, PATH_TRUNCATED, PATH_INVALID = 1, 2, 4, 8   # LA3DM_PATH_*: the bits of score_paths' flags
+PATH_NONE = 0xFFFFFFFF              # LA3DM_PATH_NONE: score_paths' stop of a walk that did not stop
+PATHS_MAX_STEPS, PATHS_MAX_WAY, PATHS_MAX_PATHS, PATHS_MAX_WAYPOINTS = 1 << 20, 1024, 1 << 20, 1 << 26   # LA3DM_PATHS_MAX_*
 REACH_NONE = 0xFFFFFFFF             # LA3DM_REACH_NONE: reach found no walk to the voxel
 REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS = 1 << 28, 1 << 16, 1 << 20   # LA3DM_REACH_MAX_*: padded voxels, max_steps, seeds
 REACH_BATCH = 32                    # LA3DM_REACH_BATCH: level launches queued between two reads of the level counts
@@ -451,6 +454,51 @@ class BGKOctoMap:
         info = _lib.RegionInfo()
         self._chk(self._M.la3dm_map_score_poses(self._h, lo3.ctypes.data, d3.ctypes.data, pts.ctypes.data if n else None, n,
                                                 T.ctypes.data if P else None, P, mask, int(radius), C.byref(o), C.byref(info)))
+        out.update(self._region_info(info))
+        return out
+
+    _PATHS_FIELDS = dict(cost=np.uint64, steps=np.uint32, stop=np.uint32, min_d2=np.uint32, ways=np.uint32, flags=np.uint8)
+
+    def score_paths(self, lo, dims, paths, obstacles=("occupied",), clearance=0, soft_radius=0, penalty=0, move_cost=(10, 14, 17),
+                    max_steps=4096, fields=("cost", "steps", "stop", "min_d2", "ways", "flags")):
+        """Cost and clearance of P candidate trajectories through the region of box(lo, dims).  `paths` is (P, W, 3): W
+        waypoints per path in the world frame (a shorter path repeats its last waypoint).  Every waypoint is resolved to its
+        voxel as search resolves it and every path walked voxel by voxel from waypoint to waypoint (a 26-connected walk; the
+        integer rule is in include/la3dm_hip.h) against d2 = distance_field(lo, dims, obstacles, max(1, clearance,
+        soft_radius)).  The walk stops at the first voxel that is outside the region (PATH_LEFT) or within `clearance` voxels
+        of an obstacle (PATH_BLOCKED; clearance 0: the obstacle voxels themselves), and after max_steps moves
+        (PATH_TRUNCATED); a path with a coordinate the lattice cannot hold (NaN, inf, |w / resolution| >= 2^30) is
+        PATH_INVALID as a whole.  Returns a dict of (P,) arrays, those named in `fields` and always cost: cost uint64 = the
+        moves (move_cost by the number of axes a move changes) plus travel's penalty of every voxel entered, up to the stop
+        — the cost travel gives the same walk with the same clearance, soft_radius, penalty and move_cost; steps = voxels
+        walked; stop = the ordinal of the stop or PATH_NONE; min_d2 = the least d2 on the walk (DF_FAR: none within the
+        radius); ways = waypoints reached; flags uint8 = the PATH_* bits; plus origin, block_key, cell as box() returns
+        them.  At most 2^28 voxels, 2^20 paths, 1024 waypoints a path and 2^26 waypoints.  A device-resident map runs the
+        query on the device pool (no host mirror refresh); a host-mode map runs it on the CPU, with identical results."""
+        lo3, d3, d, cells = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 1 << 28 else 0)(d[0] * d[1] * d[2]))
+        W = np.ascontiguousarray(paths, np.float32)
+        if W.ndim != 3 or W.shape[2] != 3:
+            raise ValueError("score_paths: paths must have the shape (P, W, 3)")
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - set(self._PATHS_FIELDS)
+        if bad:
+            raise ValueError(f"score_paths: unknown fields {sorted(bad)}")
+        if isinstance(obstacles, str):
+            obstacles = (obstacles,)
+        mask = int(obstacles) if isinstance(obstacles, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(obstacles))
+        mc = [int(v) for v in move_cost]
+        P, n_way = W.shape[0], W.shape[1]
+        if len(mc) != 3 or not all(0 <= v < 2 ** 32 for v in [mask, int(clearance), int(soft_radius), int(penalty), int(max_steps), P, n_way] + mc):
+            raise ValueError("score_paths: move_cost must have three entries, and every parameter and count must fit 32 bits")
+        prm = _lib.PathsParams(mask, int(clearance), int(soft_radius), int(penalty), (C.c_uint32 * 3)(*mc), int(max_steps))
+        # (a request the call refuses gets one-element arrays: it is refused before a buffer is looked at)
+        served = cells > 0 and 1 <= n_way <= PATHS_MAX_WAY and P <= PATHS_MAX_PATHS and P * n_way <= PATHS_MAX_WAYPOINTS
+        out = {k: np.empty(P if served else 1, t) for k, t in self._PATHS_FIELDS.items() if k == "cost" or k in fields}
+        o = _lib.PathsOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.PathsOut._fields_])
+        info = _lib.RegionInfo()
+        self._chk(self._M.la3dm_map_score_paths(self._h, lo3.ctypes.data, d3.ctypes.data, W.ctypes.data if W.size else None, P, n_way,
+                                                C.byref(prm), C.byref(o), C.byref(info)))
         out.update(self._region_info(info))
         return out
 

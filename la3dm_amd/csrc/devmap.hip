@@ -32,6 +32,7 @@
 #include "devmap_frontier.h"
 #include "devmap_gain.h"
 #include "devmap_score.h"
+#include "devmap_paths.h"
 #include "devmap_reach.h"
 #include "devmap_travel.h"
 #include "devmap_clusters.h"
@@ -90,7 +91,7 @@ struct la3dm_devmap {
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
-    Arena score_work;             // score_poses: d2 (4 bytes per voxel), then the chunks' partial records (devmap_score.h)
+    Arena score_work;             // score_poses: d2 (4 bytes per voxel), then the chunks' partial records (devmap_score.h); score_paths: d2 (devmap_paths.h)
     Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
     Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
     Arena clusters_work;          // clusters: two brick-major label buffers, side / active per brick, the round counts, sizes, flags, numbers (devmap_clusters.h)
@@ -3379,6 +3380,85 @@ int la3dm_devmap_score_poses_host(la3dm_devmap *dm, const float *lo3, const uint
                                   const la3dm_score_out *out, la3dm_region_info *info) {
     return score_query(dm, true, "la3dm_devmap_score_poses_host", lo3, dims3, points3, n_points, poses12, n_poses, obstacle_mask, radius, out,
                        info);
+}
+
+// ---- score_paths: many polylines walked through the distance field of a region (devmap_paths.h) --------------------
+
+// Stage 1 (distance_field into working storage, score_poses' arena) and stage 2 on the map's stream; every pointer is
+// device memory.  An empty map has no stage 1: every voxel has the distance word 0 or FAR.
+static int paths_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_ways3, uint32_t n_paths, uint32_t n_way,
+                        const la3dm_paths_params &p, const la3dm_paths_out &o) {
+    hipStream_t st = dm->ctx->stream;
+    const size_t n = (size_t)g.total;
+    PathsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ways = d_ways3;
+    a.n_paths = n_paths;
+    a.n_way = n_way;
+    a.resolution = dm->ctx->p.resolution;
+    a.block_size = dm->block_size;
+    a.lim = 1 << (dm->depth - 1);
+    for (int k = 0; k < 3; ++k) {
+        a.g0[k] = g.g0[k];
+        a.dims[k] = g.dims[k];
+    }
+    a.p = p;
+    a.cost = (uint32_t *)o.cost;
+    a.steps = o.steps;
+    a.stop = o.stop;
+    a.min_d2 = o.min_d2;
+    a.reached = o.ways;
+    a.flags = o.flags;
+    if (dm->n_blocks == 0) {
+        a.fill = ((p.obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : LA3DM_DF_FAR;
+    } else {
+        DM_RESERVE(dm->score_work, 4ull * n);
+        DM_RESERVE(dm->df_work, 4ull * n);
+        la3dm_distance_out dd;
+        dd.d2 = (uint32_t *)dm->score_work.ptr;
+        dd.dist = nullptr;
+        distance_launch(dm, g, p.obstacle_mask, la3dm_region::paths_radius(p), dm->df_work.ptr, dd);
+        a.d2 = dd.d2;
+    }
+    // (at most 2^18 workgroups; 16 bytes of LDS per waypoint and wave: at most 64 KB)
+    hipLaunchKernelGGL(dm_paths_walk, dim3(cdiv(n_paths, kPathsWaves)), dim3(64 * kPathsWaves), 16ull * kPathsWaves * n_way, st, a);
+    DM_TRY(hipGetLastError());
+    return LA3DM_OK;
+}
+
+static int paths_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const float *ways3,
+                       uint32_t n_paths, uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *out,
+                       la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::paths_check(params, n_paths, n_way, ways3 != nullptr, out != nullptr, out && out->cost, "->")));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kPaths, true, true, who, g));   // lo, dims, the limit and the range: before any buffer
+    if (info) *info = g.info;
+    if (n_paths == 0) return LA3DM_OK;
+    la3dm_paths_out o = *out;
+    Stage s(dm, host);
+    s.in(ways3, 3ull * n_paths * n_way);
+    s.out(o.cost, n_paths);
+    s.out(o.steps, n_paths);
+    s.out(o.stop, n_paths);
+    s.out(o.min_d2, n_paths);
+    s.out(o.ways, n_paths);
+    s.out(o.flags, n_paths);
+    DM_OK(s.reserve());
+    DM_OK(paths_launch(dm, g, ways3, n_paths, n_way, *params, o));
+    DM_OK(s.download());
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_score_paths_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_ways3, uint32_t n_paths,
+                                    uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *d_out,
+                                    la3dm_region_info *info) {
+    return paths_query(dm, false, "la3dm_devmap_score_paths_device", lo3, dims3, d_ways3, n_paths, n_way, params, d_out, info);
+}
+
+int la3dm_devmap_score_paths_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *ways3, uint32_t n_paths,
+                                  uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *out, la3dm_region_info *info) {
+    return paths_query(dm, true, "la3dm_devmap_score_paths_host", lo3, dims3, ways3, n_paths, n_way, params, out, info);
 }
 
 // ---- reach: hop distance from seeds through the passable voxels of a region (devmap_reach.h) -------------------------

@@ -1762,6 +1762,86 @@ void BGKOctoMap::score_poses(const float *lo3, const uint32_t *dims3, const floa
     }
 }
 
+// ---- score_paths.  The host form below is the definition; the device kernel (csrc/devmap_paths.h) compiles the same
+// waypoint, walk, move and entry inlines (region_contract.h) and reproduces it exactly: everything after the waypoint
+// voxels is integers.
+void BGKOctoMap::score_paths(const float *lo3, const uint32_t *dims3, const float *ways3, uint32_t n_paths, uint32_t n_way,
+                             const la3dm_paths_params *params, const la3dm_paths_out &out, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_score_paths_host(dmap, lo3, dims3, ways3, n_paths, n_way, params, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::score_paths: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::score_paths";
+    const std::string refusal = la3dm_region::paths_check(params, n_paths, n_way, ways3 != nullptr, true, out.cost != nullptr, ".");
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kPaths, true, "score_paths", g0, inf);
+    if (info) *info = inf;
+    if (n_paths == 0) return;
+    const la3dm_paths_params &p = *params;
+    std::vector<uint32_t> d2((size_t)dims3[0] * dims3[1] * dims3[2]);
+    la3dm_distance_out dd;
+    dd.d2 = d2.data();
+    dd.dist = nullptr;
+    distance_field(lo3, dims3, p.obstacle_mask, la3dm_region::paths_radius(p), dd, nullptr);
+    const int lim = 1 << (block_depth - 1);
+#pragma omp parallel for schedule(dynamic, 16)
+    for (uint32_t path = 0; path < n_paths; ++path) {
+        const float *W = ways3 + 3 * (size_t)path * n_way;
+        std::vector<long long> G(3 * (size_t)n_way);
+        bool valid = true;
+        for (uint32_t k = 0; k < n_way; ++k) valid = la3dm_region::path_waypoint(W + 3 * k, resolution, block_size, lim, &G[3 * k]) && valid;
+        uint64_t cost = 0, o = 0;   // o: the ordinal of the voxel at hand
+        uint32_t L = 0, stop = LA3DM_PATH_NONE, min_d2 = LA3DM_DF_FAR, ways = 0, flags = valid ? 0u : LA3DM_PATH_INVALID;
+        // the voxel v of ordinal o, entered by a move with nz components (0: the first): true where the walk stops
+        auto visit = [&](const long long *v, uint32_t nz) {
+            uint32_t f = 0;
+            if (!la3dm_region::path_inside(v, g0, dims3, f)) {
+                flags |= LA3DM_PATH_LEFT;
+            } else if (la3dm_region::path_blocked(p.clearance, d2[f])) {
+                flags |= LA3DM_PATH_BLOCKED;
+            } else {
+                if (nz > 0) cost += la3dm_region::path_entry(p, nz, d2[f]);
+                min_d2 = std::min(min_d2, d2[f]);
+                ++L;
+                return false;
+            }
+            stop = (uint32_t)o;
+            return true;
+        };
+        if (valid) {
+            bool stopped = visit(&G[0], 0);
+            if (!stopped) ways = 1;
+            long long last[3] = {G[0], G[1], G[2]};
+            for (uint32_t k = 1; k < n_way && !stopped && !(flags & LA3DM_PATH_TRUNCATED); ++k) {
+                const long long *A = &G[3 * (k - 1)], *B = &G[3 * k];
+                const long long n = la3dm_region::path_segment(A, B);
+                for (long long s = 1; s <= n && !stopped; ++s) {
+                    if (o == p.max_steps) {   // T > max_steps, and no stop in [0, E]
+                        flags |= LA3DM_PATH_TRUNCATED;
+                        break;
+                    }
+                    ++o;
+                    long long v[3];
+                    for (int c = 0; c < 3; ++c) v[c] = la3dm_region::path_sample(A[c], B[c] - A[c], n, s);
+                    stopped = visit(v, la3dm_region::path_move(last, v));
+                    for (int c = 0; c < 3; ++c) last[c] = v[c];
+                }
+                if (!stopped && !(flags & LA3DM_PATH_TRUNCATED)) ++ways;   // off[k] < L: waypoint k is reached
+            }
+        }
+        out.cost[path] = cost;
+        if (out.steps) out.steps[path] = L;
+        if (out.stop) out.stop[path] = stop;
+        if (out.min_d2) out.min_d2[path] = min_d2;
+        if (out.ways) out.ways[path] = ways;
+        if (out.flags) out.flags[path] = (uint8_t)flags;
+    }
+}
+
 namespace {
 // heightMapColor, include/common/markerarray_pub.h:21-76 (s = v = 1)
 void height_map_color(double h, float *rgba) {

@@ -482,6 +482,16 @@ public:
     void score_poses(const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points, const float *poses12,
                      uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out &out,
                      la3dm_region_info *info = nullptr) const;
+    /// Cost and clearance of many candidate trajectories (contract: include/la3dm_hip.h, la3dm_devmap_score_paths_host):
+    /// every path of ways3 (n_paths x n_way x 3 floats, world frame) is walked voxel by voxel from waypoint to waypoint
+    /// through box's region against d2 = distance_field(lo, dims, obstacle_mask, max(1, clearance, soft_radius)); the walk
+    /// stops where it leaves the region (LA3DM_PATH_LEFT) or meets a voxel within `clearance` of an obstacle
+    /// (LA3DM_PATH_BLOCKED), and after max_steps moves (LA3DM_PATH_TRUNCATED).  out.cost[p] = travel's cost of the walk up to
+    /// the stop; steps, stop, min_d2, ways (waypoints reached) and flags are optional.  Bad arguments throw
+    /// std::invalid_argument.  A device-resident map runs the query on the device pool (no mirror refresh); a host-mode
+    /// map runs its own distance_field and a plain loop: that form is the definition, and both give the same integers.
+    void score_paths(const float *lo3, const uint32_t *dims3, const float *ways3, uint32_t n_paths, uint32_t n_way,
+                     const la3dm_paths_params *params, const la3dm_paths_out &out, la3dm_region_info *info = nullptr) const;
     /// Reach over box's region (contract: include/la3dm_hip.h, la3dm_devmap_reach_host): steps[v] = the least number of
     /// moves (connectivity 6, 18 or 26) from any seed to v through passable voxels of the region — class (box's cls) in
     /// `pass_mask` and, with clearance > 0, distance_field(obstacle_mask, radius = clearance) FAR — LA3DM_REACH_NONE where

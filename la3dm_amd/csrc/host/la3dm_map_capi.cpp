@@ -423,6 +423,15 @@ int la3dm_map_score_poses(const la3dm_map *m, const float *lo3, const uint32_t *
         return 0;)
 }
 
+int la3dm_map_score_paths(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *ways3, uint32_t n_paths,
+                          uint32_t n_way, const la3dm_paths_params *params, const la3dm_paths_out *out, la3dm_region_info *info) {
+    GUARD(
+        la3dm_paths_out none;
+        memset(&none, 0, sizeof(none));
+        m->map->score_paths(lo3, dims3, ways3, n_paths, n_way, params, out ? *out : none, info);
+        return 0;)
+}
+
 int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                     uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
                     const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,

@@ -1,7 +1,7 @@
 // region_contract.h — what a valid region query is (include/la3dm_hip.h "Region"), once for the device library
 // (devmap.hip) and the host map (bgkoctomap.cpp): the limits of each query, their order, their texts and the anchor
 // arithmetic.  Host code, but for the inlines marked LA3DM_HD, which the device kernels compile as well (score_poses:
-// csrc/devmap_score.h).  A check answers with the text of the refusal, without the caller's prefix, or with an empty
+// csrc/devmap_score.h; score_paths: csrc/devmap_paths.h).  A check answers with the text of the refusal, without the caller's prefix, or with an empty
 // string; how a refusal is reported (an error code and a stored text, an exception) is the caller's business.
 #ifndef LA3DM_REGION_CONTRACT_H
 #define LA3DM_REGION_CONTRACT_H
@@ -260,10 +260,96 @@ inline std::string travel_check(const la3dm_travel_params *p, uint32_t n_seeds, 
 // d2 = distance_field's word (LA3DM_DF_FAR without a distance transform).  One definition for the host form; the device
 // kernel (csrc/devmap_travel.h, tv_entry) is its twin.
 constexpr uint32_t kTravelBlocked = 0xFFFFFFFFu;
+// pen(v): falls linearly in the squared distance from just under `penalty` next to an obstacle to 0 at soft_radius
+LA3DM_HD inline uint32_t travel_pen(uint32_t soft_radius, uint32_t penalty, uint32_t d2) {
+    const uint32_t s2 = soft_radius * soft_radius;
+    return s2 > 0 && d2 <= s2 ? (uint32_t)((uint64_t)penalty * (s2 - d2) / s2) : 0u;
+}
 inline uint32_t travel_entry(const la3dm_travel_params &p, uint32_t d2) {
     if (p.clearance > 0 && d2 != LA3DM_DF_FAR && d2 <= p.clearance * p.clearance) return kTravelBlocked;
-    const uint32_t s2 = p.soft_radius * p.soft_radius;
-    return s2 > 0 && d2 <= s2 ? (uint32_t)((uint64_t)p.penalty * (s2 - d2) / s2) : 0u;
+    return travel_pen(p.soft_radius, p.penalty, d2);
+}
+
+// ---- score_paths (contract: include/la3dm_hip.h, la3dm_devmap_score_paths_host) ----
+constexpr Query kPaths = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, ""};
+
+// the checks of score_paths' own arguments and buffers, all before the region's (`member` as in resolve)
+inline std::string paths_check(const la3dm_paths_params *p, uint32_t n_paths, uint32_t n_way, bool has_ways, bool has_out, bool has_cost,
+                               const char *member) {
+    if (!p) return "params is NULL";
+    if (p->obstacle_mask == 0 || (p->obstacle_mask & ~0x1Fu)) return "obstacle_mask must hold at least one of the bits 0x1F and no other";
+    if (p->clearance > LA3DM_DF_MAX_RADIUS) return "clearance must not exceed LA3DM_DF_MAX_RADIUS (1024)";
+    if (p->soft_radius > LA3DM_DF_MAX_RADIUS) return "soft_radius must not exceed LA3DM_DF_MAX_RADIUS (1024)";
+    if (p->soft_radius > 0 && p->penalty == 0) return "penalty must be >= 1 with soft_radius > 0";
+    if (p->penalty > LA3DM_TRAVEL_MAX_PENALTY) return "penalty must not exceed LA3DM_TRAVEL_MAX_PENALTY (2^16)";
+    for (int k = 0; k < 3; ++k)
+        if (p->move_cost[k] == 0 || p->move_cost[k] > LA3DM_TRAVEL_MAX_MOVE) return "move_cost: every entry must lie in [1, LA3DM_TRAVEL_MAX_MOVE (2^16)]";
+    if (p->max_steps == 0 || p->max_steps > LA3DM_PATHS_MAX_STEPS) return "max_steps must lie in [1, LA3DM_PATHS_MAX_STEPS (2^20)]";
+    if (n_way == 0 || n_way > LA3DM_PATHS_MAX_WAY) return "n_way must lie in [1, LA3DM_PATHS_MAX_WAY (1024)]";
+    if (n_paths > LA3DM_PATHS_MAX_PATHS) return "n_paths: more than LA3DM_PATHS_MAX_PATHS (2^20) paths";
+    if ((uint64_t)n_paths * n_way > LA3DM_PATHS_MAX_WAYPOINTS) return "n_paths * n_way: more than LA3DM_PATHS_MAX_WAYPOINTS (2^26) waypoints";
+    if (n_paths == 0) return "";
+    if (!has_ways) return "ways3 is NULL";
+    if (!has_out) return "out is NULL";
+    if (!has_cost) return std::string("out") + member + "cost must not be NULL";
+    return "";
+}
+
+// the radius of score_paths' distance transform
+inline uint32_t paths_radius(const la3dm_paths_params &p) { return std::max(1u, std::max(p.clearance, p.soft_radius)); }
+
+// The voxel of a waypoint: G[c] = b * lim + cell per axis (axis_voxel), false where a coordinate fails the range test
+// (the path is then INVALID).  For lim <= 32 (block_depth <= 6), -2^30 < G[c] < 2^30 + 2^25: every G fits 32 bits signed
+// and every difference of two 33.
+LA3DM_HD inline bool path_waypoint(const float *w3, float resolution, float block_size, int lim, long long *G) {
+    for (int c = 0; c < 3; ++c)
+        if (!axis_in_range(w3[c], resolution)) return false;
+    for (int c = 0; c < 3; ++c) {
+        const AxisVoxel v = axis_voxel(w3[c], resolution, block_size, lim);
+        G[c] = v.b * lim + v.cell;
+    }
+    return true;
+}
+
+// the length of the segment from voxel A to voxel B: the largest |B[c] - A[c]|
+LA3DM_HD inline long long path_segment(const long long *A, const long long *B) {
+    long long n = 0;
+    for (int c = 0; c < 3; ++c) {
+        const long long d = B[c] - A[c], m = d < 0 ? -d : d;
+        n = m > n ? m : n;
+    }
+    return n;
+}
+
+// One axis of the voxel at step s of a segment of length n >= 1 that starts at a and moves by d: a + floor((2 s d + n) /
+// (2 n)).  0 <= s <= min(n, 2^20 + 1) and |d| <= n < 2^33 (path_waypoint's range): |2 s d + n| < 2^56, no overflow.
+LA3DM_HD inline long long path_sample(long long a, long long d, long long n, long long s) {
+    const long long num = 2 * s * d + n, den = 2 * n;
+    long long q = num / den;
+    if (num % den < 0) --q;   // floor, not truncation
+    return a + q;
+}
+
+// the move from voxel u to voxel v of a walk: the number of their non-zero differences, 1 ... 3
+LA3DM_HD inline uint32_t path_move(const long long *u, const long long *v) { return (uint32_t)(u[0] != v[0]) + (u[1] != v[1]) + (u[2] != v[2]); }
+
+// The voxel v against the region: false where it is outside, else f = its flat index.
+LA3DM_HD inline bool path_inside(const long long *v, const uint32_t *g0, const uint32_t *dims, uint32_t &f) {
+    uint32_t at[3];
+    for (int c = 0; c < 3; ++c) {
+        const long long q = v[c] - (long long)g0[c];
+        if (q < 0 || q >= (long long)dims[c]) return false;
+        at[c] = (uint32_t)q;
+    }
+    f = (at[0] * dims[1] + at[1]) * dims[2] + at[2];
+    return true;
+}
+
+// the entry of a voxel with distance word d2: blocked, or what entering it adds to the move
+LA3DM_HD inline bool path_blocked(uint32_t clearance, uint32_t d2) { return d2 != LA3DM_DF_FAR && d2 <= clearance * clearance; }
+LA3DM_HD inline uint32_t path_entry(const la3dm_paths_params &p, uint32_t nz, uint32_t d2) {
+    const uint32_t move = nz == 1u ? p.move_cost[0] : (nz == 2u ? p.move_cost[1] : p.move_cost[2]);   // (no runtime-indexed array: registers)
+    return move + travel_pen(p.soft_radius, p.penalty, d2);
 }
 
 // the checks of clusters' own arguments and buffers, all before the region's; `out` may be null
