@@ -335,6 +335,27 @@ static int exclusive_scan(la3dm_devmap *dm, const uint32_t *in, uint32_t *out, u
     return LA3DM_OK;
 }
 
+// what pack, pack_region, erase_region, unpack and merge answer on a poisoned map
+constexpr const char *kPoisonedText = "the map is poisoned (a failed insert left its block table unreconciled)";
+
+// A scan whose total the host needs before it can go on: the scan over n >= 1 elements, *total = out[n - 1] (callers close
+// `in` with an entry of its own, so that is the sum of the rest) and the error word read back, one synchronisation.  A scan
+// that found its state in use poisons the map.
+static int scan_total(la3dm_devmap *dm, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total) {
+    hipStream_t st = dm->ctx->stream;
+    int rc = exclusive_scan(dm, in, out, n);
+    if (rc != LA3DM_OK) return rc;
+    uint32_t err = 0;
+    DM_TRY(hipMemcpyAsync(total, out + n - 1, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    if (err & kScanErrStuck) {
+        dm->poisoned = true;
+        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
+    }
+    return LA3DM_OK;
+}
+
 // Segments of a sorted key array (invalid keys last), one launch: head flags, their exclusive scan, the segment starts
 // (+ keys), d_cnt[seg_slot] = segments, d_cnt[valid_slot] = valid keys, seg_start[segments] = valid keys;
 // zero_slot >= 0: d_cnt[zero_slot] = 0 on the way.
@@ -563,6 +584,22 @@ static int grow_pool(la3dm_devmap *dm, size_t want_blocks) {
     return LA3DM_OK;
 }
 
+// the block table (tab_key, tab_val; `cap` entries) built again from the keys of pool slots 0 .. n_blocks - 1
+static int table_rebuild(la3dm_devmap *dm, long long *tab_key, uint32_t *tab_val, uint32_t cap, uint32_t n_blocks) {
+    hipStream_t st = dm->ctx->stream;
+    DM_TRY(hipMemsetAsync(tab_key, 0xFF, 8ull * cap, st));
+    if (n_blocks) {
+        hipLaunchKernelGGL(dm_table_rebuild, dim3(cdiv(n_blocks, 256)), dim3(256), 0, st, dm->blk_key, n_blocks, tab_key, tab_val, cap - 1);
+        DM_TRY(hipGetLastError());
+    }
+    return LA3DM_OK;
+}
+
+// the pool as a kernel's argument (devmap_pool.h)
+static PoolView pool_view(const la3dm_devmap *dm) {
+    return PoolView{dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->A, dm->B, dm->S, dm->npb, dm->depth, dm->init_A, dm->init_B};
+}
+
 static int grow_table(la3dm_devmap *dm, size_t want_blocks) {
     if (dm->tab_cap >= 2 * want_blocks && dm->tab_cap) return LA3DM_OK;
     hipStream_t st = dm->ctx->stream;
@@ -574,10 +611,8 @@ static int grow_table(la3dm_devmap *dm, size_t want_blocks) {
         if (tk) (void)hipFree(tk);
         return dm_fail(dm, LA3DM_ERR_OOM, "devmap: block table allocation failed");
     }
-    DM_TRY(hipMemsetAsync(tk, 0xFF, 8ull * cap, st));
-    if (dm->n_blocks)
-        hipLaunchKernelGGL(dm_table_rebuild, dim3(cdiv(dm->n_blocks, 256)), dim3(256), 0, st, dm->blk_key, dm->n_blocks, tk, tv,
-                           cap - 1);
+    int rc = table_rebuild(dm, tk, tv, cap, dm->n_blocks);   // (into the new arrays, installed below)
+    if (rc != LA3DM_OK) return rc;
     DM_TRY(hipStreamSynchronize(st));
     if (dm->tab_key) (void)hipFree(dm->tab_key);
     if (dm->tab_val) (void)hipFree(dm->tab_val);
@@ -2387,26 +2422,19 @@ static int pack_blocks(la3dm_devmap *dm, const char *who, uint64_t nb, const Pac
     if (!pl) DM_RESERVE(dm->pack_counts, 4ull * (nb + 1));
     uint8_t *arena = (uint8_t *)dm->pack_stream.ptr;
     uint32_t *counts = pl ? pl->counts : (uint32_t *)dm->pack_counts.ptr, *leaf_off = (uint32_t *)(arena + worst.leaf_off), *mask = (uint32_t *)(arena + worst.mask);
+    const uint32_t *list = pl ? pl->list : nullptr;   // the kernels' switch: the listed slots, or the pool in order
+    const auto count_kernel = pl ? dm_pack_count<true> : dm_pack_count<false>;
+    const auto emit_kernel = pl ? dm_pack_emit<true> : dm_pack_emit<false>;
     if (pl) {
         hipLaunchKernelGGL(dm_evict_list, dim3(cdiv(pl->n_pool, 256)), dim3(256), 0, st, (const long long *)dm->blk_key, pl->n_pool, pl->flag, pl->rank,
                            pl->list, (long long *)(arena + worst.keys));
         DM_TRY(hipGetLastError());
-        hipLaunchKernelGGL(dm_pack_count<true>, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
-                           (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask, (const uint32_t *)pl->list);
-    } else {
-        hipLaunchKernelGGL(dm_pack_count<false>, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
-                           (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask, (const uint32_t *)nullptr);
     }
+    hipLaunchKernelGGL(count_kernel, dim3(cdiv(nb + 1, kPackWaves)), dim3(64 * kPackWaves), kPackWaves * pack_lds_stride(npb), st,
+                       (const uint8_t *)dm->S, (uint32_t)nb, npb, dm->depth, counts, mask, list);
     DM_TRY(hipGetLastError());
-    DM_OK(exclusive_scan(dm, counts, leaf_off, (uint32_t)nb + 1u));
-    uint32_t n_leaves = 0, err = 0;
-    DM_TRY(hipMemcpyAsync(&n_leaves, leaf_off + nb, 4, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (err & kScanErrStuck) {
-        dm->poisoned = true;
-        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
-    }
+    uint32_t n_leaves = 0;
+    DM_OK(scan_total(dm, counts, leaf_off, (uint32_t)nb + 1u, &n_leaves));
     if (n_leaves < nb || n_leaves > nb * dm->ncell) return dm_fail(dm, LA3DM_ERR_HIP, std::string(who) + ": the pool's leaves do not tile its blocks (internal error)");
     const la3dm_pack::Layout l = la3dm_pack::layout(nb, n_leaves, npb);
     *size = l.total;
@@ -2422,14 +2450,9 @@ static int pack_blocks(la3dm_devmap *dm, const char *who, uint64_t nb, const Pac
         gaps.at[g] = ends[g][0];
         gaps.len[g] = (uint32_t)(ends[g][1] - ends[g][0]);
     }
-    if (pl)
-        hipLaunchKernelGGL(dm_pack_emit<true>, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
-                           (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
-                           (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps, (const uint32_t *)pl->list);
-    else
-        hipLaunchKernelGGL(dm_pack_emit<false>, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
-                           (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
-                           (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps, (const uint32_t *)nullptr);
+    hipLaunchKernelGGL(emit_kernel, dim3(cdiv(nb, kPackWaves)), dim3(64 * kPackWaves), 0, st, (const float *)dm->A, (const float *)dm->B,
+                       (const uint8_t *)dm->S, (uint32_t)nb, npb, (const uint32_t *)leaf_off, (const uint32_t *)mask, arena + l.state,
+                       (float *)(arena + l.A), (float *)(arena + l.B), arena, gaps, list);
     DM_TRY(hipGetLastError());
     DM_TRY(hipMemcpyAsync(buf, arena, l.total, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
@@ -2440,7 +2463,7 @@ int la3dm_devmap_pack_host(la3dm_devmap *dm, void *buf, uint64_t cap, uint64_t *
     if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
     if (!dm || !size) return LA3DM_ERR_ARG;
     const char *who = "la3dm_devmap_pack_host";
-    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    if (dm->poisoned) return refuse(dm, who, kPoisonedText);
     return pack_blocks(dm, who, dm->n_blocks, nullptr, buf, cap, size);
 }
 
@@ -2455,7 +2478,7 @@ static int evict_select(la3dm_devmap *dm, const char *who, const int32_t *klo, c
     if (!bad.empty()) return refuse(dm, who, bad);
     if (inside != 0 && inside != 1) return refuse(dm, who, "inside is neither 0 nor 1");
     box.inside = inside;
-    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
+    if (dm->poisoned) return refuse(dm, who, kPoisonedText);
     *n_sel = 0;
     const uint32_t n = dm->n_blocks;
     if (n == 0) return LA3DM_OK;
@@ -2468,15 +2491,7 @@ static int evict_select(la3dm_devmap *dm, const char *who, const int32_t *klo, c
     hipLaunchKernelGGL(dm_evict_select, dim3(cdiv(n + 1, 256)), dim3(256), 0, st, (const long long *)dm->blk_key, n, box, *flag);
     DM_TRY(hipGetLastError());
     dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
-    DM_OK(exclusive_scan(dm, *flag, *rank, n + 1u));
-    uint32_t err = 0;
-    DM_TRY(hipMemcpyAsync(n_sel, *rank + n, 4, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));
-    if (err & kScanErrStuck) {
-        dm->poisoned = true;
-        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
-    }
+    DM_OK(scan_total(dm, *flag, *rank, n + 1u, n_sel));
     if (*n_sel > n) return dm_fail(dm, LA3DM_ERR_HIP, std::string(who) + ": more blocks selected than the pool has (internal error)");
     return LA3DM_OK;
 }
@@ -2524,13 +2539,7 @@ int la3dm_devmap_erase_region_host(la3dm_devmap *dm, const int32_t klo[3], const
     // from the first launch that writes the map on, the block count is the new one: a failure below leaves a map that says so
     dm->n_blocks = n_new;
     dm->counters_clean = false;
-    if (dm->tab_cap) {
-        DM_TRY(hipMemsetAsync(dm->tab_key, 0xFF, 8ull * dm->tab_cap, st));
-        if (n_new) {
-            hipLaunchKernelGGL(dm_table_rebuild, dim3(cdiv(n_new, 256)), dim3(256), 0, st, dm->blk_key, n_new, dm->tab_key, dm->tab_val, dm->tab_cap - 1);
-            DM_TRY(hipGetLastError());
-        }
-    }
+    if (dm->tab_cap) DM_OK(table_rebuild(dm, dm->tab_key, dm->tab_val, dm->tab_cap, n_new));
     DM_TRY(hipStreamSynchronize(st));
     if (stats) {
         stats->n_removed = n_removed;
@@ -2538,6 +2547,15 @@ int la3dm_devmap_erase_region_host(la3dm_devmap *dm, const int32_t klo[3], const
         stats->n_blocks = n_new;
     }
     return LA3DM_OK;
+}
+
+// Whether a stream may enter this map (unpack, merge): a poisoned map takes none, the stream must be well formed
+// (host/pack_format.h) and its header must describe a map like this one.  *h = the stream's header.
+static int admit_stream(la3dm_devmap *dm, const char *who, const void *buf, uint64_t size, la3dm_pack_header *h) {
+    if (dm->poisoned) return refuse(dm, who, kPoisonedText);
+    const std::string bad = la3dm_pack::validate(buf, size, h);
+    if (!bad.empty()) return refuse(dm, who, bad);
+    return refuse(dm, who, la3dm_pack::mismatch(*h, la3dm_pack::make_header(dm->ctx->p, dm->lv_original_size, nullptr, 0, 0)));
 }
 
 // The stream into an empty map: validate (host, before anything is allocated or launched), upload, dm_unpack_expand (the
@@ -2549,12 +2567,8 @@ int la3dm_devmap_unpack_host(la3dm_devmap *dm, const void *buf, uint64_t size) {
     const char *who = "la3dm_devmap_unpack_host";
     la3dm_ctx *ctx = dm->ctx;
     if (dm->n_blocks != 0) return refuse(dm, who, "the map already holds blocks (a stream is loaded into an empty map)");
-    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
     la3dm_pack_header h;
-    const std::string bad = la3dm_pack::validate(buf, size, &h);
-    if (!bad.empty()) return refuse(dm, who, bad);
-    const std::string other = la3dm_pack::mismatch(h, la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, 0, 0));
-    if (!other.empty()) return refuse(dm, who, other);
+    DM_OK(admit_stream(dm, who, buf, size, &h));
     const bool lv_original_size = h.variant == 2u ? (h.flags & LA3DM_PACK_FLAG_LV_ORIGINAL_SIZE) != 0 : dm->lv_original_size;
     if (h.n_blocks == 0) {
         dm->lv_original_size = lv_original_size;
@@ -2575,10 +2589,7 @@ int la3dm_devmap_unpack_host(la3dm_devmap *dm, const void *buf, uint64_t size) {
                        (const uint8_t *)(arena + l.state), (const float *)(arena + l.A), (const float *)(arena + l.B), dm->init_A, dm->init_B);
     DM_TRY(hipGetLastError());
     DM_TRY(hipMemcpyAsync(dm->blk_key, arena + l.keys, 8ull * nb, hipMemcpyDeviceToDevice, st));
-    DM_TRY(hipMemsetAsync(dm->tab_key, 0xFF, 8ull * dm->tab_cap, st));
-    hipLaunchKernelGGL(dm_table_rebuild, dim3(cdiv(nb, 256)), dim3(256), 0, st, dm->blk_key, (uint32_t)nb, dm->tab_key, dm->tab_val,
-                       dm->tab_cap - 1);
-    DM_TRY(hipGetLastError());
+    DM_OK(table_rebuild(dm, dm->tab_key, dm->tab_val, dm->tab_cap, (uint32_t)nb));
     DM_TRY(hipStreamSynchronize(st));   // (buf is the caller's again)
     dm->n_blocks = (uint32_t)nb;
     dm->lv_original_size = lv_original_size;
@@ -2600,12 +2611,8 @@ int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la
     if (stats) memset(stats, 0, sizeof(*stats));
     if (ctx->p.variant != 0 && ctx->p.variant != 3)
         return refuse(dm, who, "merge is defined for BGKOctoMap (variant 0) and BGKLOctoMap (variant 3) maps; GPOctoMap and BGKLVOctoMap fuse by other rules");
-    if (dm->poisoned) return refuse(dm, who, "the map is poisoned (a failed insert left its block table unreconciled)");
     la3dm_pack_header h;
-    const std::string bad = la3dm_pack::validate(buf, size, &h);
-    if (!bad.empty()) return refuse(dm, who, bad);
-    const std::string other = la3dm_pack::mismatch(h, la3dm_pack::make_header(ctx->p, dm->lv_original_size, nullptr, 0, 0));
-    if (!other.empty()) return refuse(dm, who, other);
+    DM_OK(admit_stream(dm, who, buf, size, &h));
     if (!merge_lds_fits(dm->depth))
         return refuse(dm, who, "block_depth " + std::to_string(dm->depth) + " needs " + std::to_string(kPackWaves * merge_lds_stride(dm->depth)) +
                                    " bytes of LDS per workgroup, a compute unit has " + std::to_string(kMergeLdsPerCu) + " (merge runs at block_depth 1 to 4)");
@@ -2624,19 +2631,11 @@ int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la
     const long long *keys = (const long long *)(arena + l.keys);
     DM_TRY(hipMemcpyAsync(arena, buf, l.total, hipMemcpyHostToDevice, st));
     DM_TRY(hipMemsetAsync(cells, 0, 8ull * kMergeCntWords, st));
-    const PoolView pool{dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->A, dm->B, dm->S, npb, dm->depth, dm->init_A, dm->init_B};
-    hipLaunchKernelGGL(dm_merge_find, dim3(cdiv(nb + 1, 256)), dim3(256), 0, st, keys, (uint32_t)nb, pool, n_old && dm->tab_cap ? 1u : 0u, slot, flag);
+    hipLaunchKernelGGL(dm_merge_find, dim3(cdiv(nb + 1, 256)), dim3(256), 0, st, keys, (uint32_t)nb, pool_view(dm), n_old && dm->tab_cap ? 1u : 0u, slot, flag);
     DM_TRY(hipGetLastError());
     dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
-    DM_OK(exclusive_scan(dm, flag, off, (uint32_t)nb + 1u));
-    uint32_t created = 0, err = 0;
-    DM_TRY(hipMemcpyAsync(&created, off + nb, 4, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
-    DM_TRY(hipStreamSynchronize(st));   // (buf is the caller's again)
-    if (err & kScanErrStuck) {
-        dm->poisoned = true;
-        return dm_fail(dm, LA3DM_ERR_HIP, "devmap: a prefix-sum launch found its state in use (internal error)");
-    }
+    uint32_t created = 0;
+    DM_OK(scan_total(dm, flag, off, (uint32_t)nb + 1u, &created));   // (synchronised: buf is the caller's again)
     if (created > nb) return dm_fail(dm, LA3DM_ERR_HIP, "la3dm_devmap_merge_host: more blocks created than the stream has (internal error)");
     if ((uint64_t)n_old + created > cap_max) return refuse(dm, who, too_big);
     DM_OK(grow_pool(dm, (size_t)n_old + created));
@@ -2725,11 +2724,6 @@ static int raycast_check(la3dm_devmap *dm, const float *rays6, uint32_t n, uint3
     if (!rays6) return refuse(dm, who, "rays6 is NULL");
     if (!out || !out->steps || !out->flags) return refuse(dm, who, "out, out->steps and out->flags must not be NULL");
     return LA3DM_OK;
-}
-
-// the pool as a query kernel's argument (devmap_pool.h)
-static PoolView pool_view(const la3dm_devmap *dm) {
-    return PoolView{dm->tab_key, dm->tab_val, dm->tab_cap - 1, dm->A, dm->B, dm->S, dm->npb, dm->depth, dm->init_A, dm->init_B};
 }
 
 static void raycast_launch(la3dm_devmap *dm, const float *d_rays6, uint32_t n, uint32_t stop_mask, uint32_t max_steps,
@@ -3015,6 +3009,23 @@ static void distance_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t obst
     df_pass_launch(st, y_pass, p.n_lt * p.n_ct, rows, p);
 }
 
+// The obstacle field a query built on distance_field sees (reach, travel, score_poses, score_paths), decided here alone:
+// radius 0 asks for no field, every voxel is FAR; an empty map has the uniform answer of distance_empty and no launch;
+// otherwise the transform's chain runs into d2 — n words the caller has reserved in an arena of its own — with df_work
+// as its working storage.
+static int obstacle_field(la3dm_devmap *dm, const RegionGeom &g, uint32_t obstacle_mask, uint32_t radius, uint32_t *d2, ObstacleField &field) {
+    field = ObstacleField{nullptr, LA3DM_DF_FAR};
+    if (radius == 0) return LA3DM_OK;
+    if (dm->n_blocks == 0) {
+        if ((obstacle_mask >> LA3DM_RAY_MISSING) & 1u) field.fill = 0u;
+        return LA3DM_OK;
+    }
+    DM_RESERVE(dm->df_work, 4ull * (size_t)g.total);
+    distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, la3dm_distance_out{d2, nullptr});
+    field.d2 = d2;
+    return LA3DM_OK;
+}
+
 // empty map: every voxel is MISSING — all obstacles (0 everywhere) or none (FAR, +inf)
 static int distance_empty(const Fill &f, size_t n, uint32_t obstacle_mask, const la3dm_distance_out &o) {
     const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
@@ -3058,6 +3069,10 @@ int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_
 
 // ---- frontier of a region (devmap_frontier.h) -----------------------------------------------------------------
 
+// the instantiation of a kernel template <int kConn> for a connectivity that the query's check has found to be 6, 18 or 26
+#define DM_BY_CONNECTIVITY(kernel, connectivity) \
+    ((connectivity) == 6 ? kernel<6> : (connectivity) == 18 ? kernel<18> : kernel<26>)
+
 // Bits, stencil, scan and (cap > 0) emit on the map's stream; o's arrays are device memory.  d_total: where the launches
 // leave the number of frontier voxels (a word of the query's working storage).
 static int frontier_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity,
@@ -3094,19 +3109,13 @@ static int frontier_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t open_
     if (o.score) DM_TRY(hipMemsetAsync(o.score, 0, (size_t)g.total, st));
     hipLaunchKernelGGL(dm_fr_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, open_mask, unknown_mask, f.open, base + stride);
     const dim3 wgrid(cdiv(n_words + 1, 256));
-    struct Kernels {
-        void (*stencil)(FrontierArgs), (*emit)(FrontierArgs);
-    };
-    const Kernels kn = connectivity == 6    ? Kernels{dm_fr_stencil<6>, dm_fr_emit<6>}
-                       : connectivity == 18 ? Kernels{dm_fr_stencil<18>, dm_fr_emit<18>}
-                                            : Kernels{dm_fr_stencil<26>, dm_fr_emit<26>};
-    hipLaunchKernelGGL(kn.stencil, wgrid, dim3(256), 0, st, f);
+    hipLaunchKernelGGL(DM_BY_CONNECTIVITY(dm_fr_stencil, connectivity), wgrid, dim3(256), 0, st, f);
     DM_TRY(hipGetLastError());
     dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
     int rc = exclusive_scan(dm, f.count, base + 3 * stride, n_words + 1);
     if (rc != LA3DM_OK) return rc;
     if (cap) {
-        hipLaunchKernelGGL(kn.emit, wgrid, dim3(256), 0, st, f);
+        hipLaunchKernelGGL(DM_BY_CONNECTIVITY(dm_fr_emit, connectivity), wgrid, dim3(256), 0, st, f);
         DM_TRY(hipGetLastError());
     }
     d_total = f.offset + n_words;
@@ -3293,8 +3302,7 @@ int la3dm_devmap_gain_host(la3dm_devmap *dm, const float *lo3, const uint32_t *d
 
 // ---- score_poses: one scan under many poses against the distance field of a region (devmap_score.h) ----------------
 
-// Stage 1 (distance_field into working storage) and stage 2 on the map's stream; every pointer is device memory.  An
-// empty map has no stage 1: every voxel costs 0 or FAR.
+// Stage 1 (the obstacle field, into working storage) and stage 2 on the map's stream; every pointer is device memory.
 static int score_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_points3, uint32_t n_points, const float *d_poses12,
                         uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out &o) {
     hipStream_t st = dm->ctx->stream;
@@ -3321,16 +3329,7 @@ static int score_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_po
     a.partial = (uint32_t *)((char *)dm->score_work.ptr + d2_bytes);
     a.sum_d2 = (uint32_t *)o.sum_d2;
     a.counts = o.counts;
-    if (dm->n_blocks == 0) {
-        a.fill = ((obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : LA3DM_DF_FAR;
-    } else {
-        DM_RESERVE(dm->df_work, 4ull * n);
-        la3dm_distance_out dd;
-        dd.d2 = (uint32_t *)dm->score_work.ptr;
-        dd.dist = nullptr;
-        distance_launch(dm, g, obstacle_mask, radius, dm->df_work.ptr, dd);
-        a.cost = dd.d2;
-    }
+    DM_OK(obstacle_field(dm, g, obstacle_mask, radius, (uint32_t *)dm->score_work.ptr, a.cost));
     // (n_poses chunks <= 2^20 + 1024 workgroups)
     hipLaunchKernelGGL(dm_score_pairs, dim3(n_poses * a.chunks), dim3(256), 0, st, a);
     if (a.chunks > 1) hipLaunchKernelGGL(dm_score_fold, dim3(n_poses), dim3(64), 0, st, a);
@@ -3384,12 +3383,10 @@ int la3dm_devmap_score_poses_host(la3dm_devmap *dm, const float *lo3, const uint
 
 // ---- score_paths: many polylines walked through the distance field of a region (devmap_paths.h) --------------------
 
-// Stage 1 (distance_field into working storage, score_poses' arena) and stage 2 on the map's stream; every pointer is
-// device memory.  An empty map has no stage 1: every voxel has the distance word 0 or FAR.
+// Stage 1 (the obstacle field, into score_poses' arena) and stage 2 on the map's stream; every pointer is device memory.
 static int paths_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_ways3, uint32_t n_paths, uint32_t n_way,
                         const la3dm_paths_params &p, const la3dm_paths_out &o) {
     hipStream_t st = dm->ctx->stream;
-    const size_t n = (size_t)g.total;
     PathsArgs a;
     memset(&a, 0, sizeof(a));
     a.ways = d_ways3;
@@ -3409,17 +3406,8 @@ static int paths_launch(la3dm_devmap *dm, const RegionGeom &g, const float *d_wa
     a.min_d2 = o.min_d2;
     a.reached = o.ways;
     a.flags = o.flags;
-    if (dm->n_blocks == 0) {
-        a.fill = ((p.obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : LA3DM_DF_FAR;
-    } else {
-        DM_RESERVE(dm->score_work, 4ull * n);
-        DM_RESERVE(dm->df_work, 4ull * n);
-        la3dm_distance_out dd;
-        dd.d2 = (uint32_t *)dm->score_work.ptr;
-        dd.dist = nullptr;
-        distance_launch(dm, g, p.obstacle_mask, la3dm_region::paths_radius(p), dm->df_work.ptr, dd);
-        a.d2 = dd.d2;
-    }
+    if (dm->n_blocks) DM_RESERVE(dm->score_work, 4ull * (size_t)g.total);   // (an empty map has no transform to hold)
+    DM_OK(obstacle_field(dm, g, p.obstacle_mask, la3dm_region::paths_radius(p), (uint32_t *)dm->score_work.ptr, a.field));
     // (at most 2^18 workgroups; 16 bytes of LDS per waypoint and wave: at most 64 KB)
     hipLaunchKernelGGL(dm_paths_walk, dim3(cdiv(n_paths, kPathsWaves)), dim3(64 * kPathsWaves), 16ull * kPathsWaves * n_way, st, a);
     DM_TRY(hipGetLastError());
@@ -3494,20 +3482,11 @@ static int reach_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d
     a.reached = base + stride;
     a.count = base + 4 * stride;
     const bool empty = dm->n_blocks == 0;   // every voxel MISSING: the pool is not read
-    const uint32_t *d2 = nullptr;
-    if (clearance > 0 && !empty) {
-        DM_RESERVE(dm->df_work, 4ull * n);
-        la3dm_distance_out dd;
-        dd.d2 = cells;
-        dd.dist = nullptr;
-        distance_launch(dm, g, obstacle_mask, clearance, dm->df_work.ptr, dd);
-        d2 = cells;
-    }
-    // (an empty map with a clearance: all voxels are obstacles, d2 = 0 everywhere, or none is)
-    const uint32_t mask = empty && clearance > 0 && ((obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : pass_mask;
+    ObstacleField field;   // a voxel passes where its word is FAR: everywhere without a clearance
+    DM_OK(obstacle_field(dm, g, obstacle_mask, clearance, cells, field));
     DM_TRY(hipMemsetAsync(a.reached, 0, 4ull * (3 * stride + n_count), st));   // reached, both fronts, the counts
     RegionArgs r = region_args(dm, g);
-    hipLaunchKernelGGL(dm_rc_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, r, a, mask, empty ? 0u : 1u, d2, pass);
+    hipLaunchKernelGGL(dm_rc_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, r, a, pass_mask, empty ? 0u : 1u, field, pass);
     DM_TRY(hipGetLastError());
     a.steps = o.steps ? o.steps : cells;   // (cells held d2 until dm_rc_bits read it)
     DM_TRY(hipMemsetAsync(a.steps, 0xFF, 4ull * n, st));
@@ -3515,8 +3494,7 @@ static int reach_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d
     if (n_seeds) {
         hipLaunchKernelGGL(dm_rc_seed, dim3(cdiv(n_seeds, 256)), dim3(256), 0, st, a, d_seeds, n_seeds, front[0]);
         DM_TRY(hipGetLastError());
-        void (*level_kernel)(ReachArgs, const uint32_t *, uint32_t *, uint32_t) =
-            connectivity == 6 ? dm_rc_level<6> : connectivity == 18 ? dm_rc_level<18> : dm_rc_level<26>;
+        const auto level_kernel = DM_BY_CONNECTIVITY(dm_rc_level, connectivity);
         const dim3 wgrid(cdiv(a.n_words, 256));
         uint32_t h_count[LA3DM_REACH_BATCH + 1];
         uint32_t level = 1, turn = 0;
@@ -3686,31 +3664,20 @@ static int travel_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *
     int rc = brick_layout(dm, dm->travel_work, g, 1, transform ? n : 0, a.g, a.totals, own);
     if (rc != LA3DM_OK) return rc;
     a.E = a.g.val[1] + (size_t)a.g.n_bricks * 512;
-    const uint32_t *d2 = nullptr;
-    uint32_t d2_fill = LA3DM_DF_FAR;
-    if (transform) {
-        DM_RESERVE(dm->df_work, 4ull * n);
-        la3dm_distance_out dd;
-        dd.d2 = own;
-        dd.dist = nullptr;
-        distance_launch(dm, g, p.obstacle_mask, R, dm->df_work.ptr, dd);
-        d2 = dd.d2;
-    } else if (R > 0 && ((p.obstacle_mask >> LA3DM_RAY_MISSING) & 1u)) {
-        d2_fill = 0u;   // (the empty map with MISSING as an obstacle: every voxel is one)
-    }
+    ObstacleField field;
+    DM_OK(obstacle_field(dm, g, p.obstacle_mask, R, own, field));
     DM_TRY(hipMemsetAsync(a.g.side[0], 0, 4ull * (own - a.g.side[0]), st));
     RegionArgs r = region_args(dm, g);
-    hipLaunchKernelGGL(dm_tv_enter, dim3(a.g.n_bricks * 2u), dim3(256), 0, st, r, a, p.pass_mask, empty ? 0u : 1u, d2, d2_fill, p.clearance,
+    hipLaunchKernelGGL(dm_tv_enter, dim3(a.g.n_bricks * 2u), dim3(256), 0, st, r, a, p.pass_mask, empty ? 0u : 1u, field, p.clearance,
                        p.soft_radius * p.soft_radius, p.penalty);
     DM_TRY(hipGetLastError());
     memset(&stats, 0, sizeof(stats));
     uint32_t queued = 0;
     if (n_seeds) {
         hipLaunchKernelGGL(dm_tv_seed, dim3(cdiv(n_seeds, 256)), dim3(256), 0, st, a, d_seeds, n_seeds,
-                           p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3);
+                           la3dm_region::move_reach(p.connectivity));
         DM_TRY(hipGetLastError());
-        void (*round_kernel)(TravelArgs, uint32_t, uint32_t) =
-            p.connectivity == 6 ? dm_tv_round<6> : p.connectivity == 18 ? dm_tv_round<18> : dm_tv_round<26>;
+        const auto round_kernel = DM_BY_CONNECTIVITY(dm_tv_round, p.connectivity);
         rc = brick_rounds<LA3DM_TRAVEL_BATCH>(
             dm, a.g, [&](uint32_t turn, uint32_t slot) { hipLaunchKernelGGL(round_kernel, dim3(a.g.n_bricks), dim3(512), 0, st, a, turn, slot); },
             LA3DM_TRAVEL_MAX_ROUNDS, "la3dm_devmap_travel: no fixed point after LA3DM_TRAVEL_MAX_ROUNDS (2^16) rounds; the outputs are unspecified",
@@ -3718,9 +3685,7 @@ static int travel_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *
         if (rc != LA3DM_OK) return rc;
     }
     const uint32_t *side = a.g.side[queued & 1u];
-    void (*finish_kernel)(TravelArgs, const uint32_t *, uint32_t *, uint8_t *) =
-        p.connectivity == 6 ? dm_tv_finish<6> : p.connectivity == 18 ? dm_tv_finish<18> : dm_tv_finish<26>;
-    hipLaunchKernelGGL(finish_kernel, dim3(cdiv(a.g.n_cells, 256)), dim3(256), 0, st, a, side, o.cost, o.parent);
+    hipLaunchKernelGGL(DM_BY_CONNECTIVITY(dm_tv_finish, p.connectivity), dim3(cdiv(a.g.n_cells, 256)), dim3(256), 0, st, a, side, o.cost, o.parent);
     DM_TRY(hipGetLastError());
     if (n_targets) {
         hipLaunchKernelGGL(dm_tv_gather, dim3(cdiv(n_targets, 256)), dim3(256), 0, st, a, side, d_targets, n_targets, o.target_cost);
@@ -3807,8 +3772,7 @@ static int clusters_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_cl
     rec.m = 0;
     uint32_t queued = 0;
     if (!p.from_list || p.n_members) {
-        void (*round_kernel)(ClustersArgs, uint32_t, uint32_t) =
-            p.connectivity == 6 ? dm_cl_round<6> : p.connectivity == 18 ? dm_cl_round<18> : dm_cl_round<26>;
+        const auto round_kernel = DM_BY_CONNECTIVITY(dm_cl_round, p.connectivity);
         rc = brick_rounds<LA3DM_CLUSTERS_BATCH>(
             dm, a.g, [&](uint32_t turn, uint32_t slot) { hipLaunchKernelGGL(round_kernel, dim3(n_bricks), dim3(512), 0, st, a, turn, slot); },
             LA3DM_CLUSTERS_MAX_ROUNDS, "la3dm_devmap_clusters: no fixed point after LA3DM_CLUSTERS_MAX_ROUNDS (2^16) rounds; the outputs are unspecified",

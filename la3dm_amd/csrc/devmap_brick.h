@@ -52,6 +52,7 @@
 
 #include "devmap_pool.h"
 #include "devmap_region.h"
+#include "host/region_contract.h"
 
 namespace la3dm_dev {
 
@@ -99,7 +100,7 @@ __device__ __forceinline__ T brick_pick(T const (&pair)[2], uint32_t which) {
 template <int kConn>
 __device__ __forceinline__ constexpr bool brick_allowed(int di, int dj, int dk) {
     const int m = (di ? 1 : 0) + (dj ? 1 : 0) + (dk ? 1 : 0);
-    return m >= 1 && m <= (kConn == 6 ? 1 : kConn == 18 ? 2 : 3);
+    return m >= 1 && m <= la3dm_region::move_reach(kConn);
 }
 
 // does voxel (li, lj, lk) of a brick lie on the face, edge or corner towards the neighbour brick at (di, dj, dk)?

@@ -34,6 +34,16 @@ constexpr uint32_t kDfRows = 32;              // rows of a line per workgroup
 constexpr uint32_t kDfWaveRows = kDfRows / 4; // consecutive rows per wave, all in flight together
 constexpr uint32_t kDfLdsBytes = 64u << 10;   // staging limit of dm_df_pass<.., true>
 
+// The obstacle field a query on top of distance_field sees (reach, travel, score_poses, score_paths), as a kernel argument:
+// the transform's d2 words by flat voxel index, or — d2 null — the same word `fill` at every voxel.  That is LA3DM_DF_FAR
+// where the query asked for no transform (radius 0), and the empty map's uniform answer, 0 or FAR, of which no transform
+// runs.  Built in one place, obstacle_field (devmap.hip).
+struct ObstacleField {
+    const uint32_t *d2;   // [nx ny nz] or null
+    uint32_t fill;
+    __device__ __forceinline__ uint32_t at(uint32_t f) const { return d2 ? d2[f] : fill; }
+};
+
 // ---- stage 1: obstacle bits ------------------------------------------------------------------------------------
 // a.total voxels -> ceil(total / 32) words; bit f of the stream = voxel f is an obstacle.  The grid covers whole waves:
 // lanes beyond `total` vote 0, so the bits past the end of the last word are clear.

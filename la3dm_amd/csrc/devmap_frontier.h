@@ -31,6 +31,7 @@
 #define LA3DM_DEVMAP_FRONTIER_H
 
 #include "devmap_region.h"
+#include "host/region_contract.h"
 
 namespace la3dm_dev {
 
@@ -92,7 +93,7 @@ __device__ __forceinline__ void fr_count(const FrontierArgs &a, uint32_t w, uint
 #pragma unroll
             for (int dk = -1; dk <= 1; ++dk) {
                 const int manhattan = (di ? 1 : 0) + (dj ? 1 : 0) + (dk ? 1 : 0);
-                if (manhattan == 0 || manhattan > (kConn == 6 ? 1 : kConn == 18 ? 2 : 3)) continue;
+                if (manhattan == 0 || manhattan > la3dm_region::move_reach(kConn)) continue;
                 uint32_t carry = fr_window(a.unknown, a.n_words, base + di * sx + dj * sy + dk);
 #pragma unroll
                 for (uint32_t q = 0; q < kFrPlanes; ++q) {   // a chain of half adders

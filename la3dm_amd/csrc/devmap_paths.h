@@ -22,8 +22,9 @@
 //                  n_way alone, so every wave of a workgroup — also one past the last path, and one whose path is INVALID —
 //                  meets each of them.
 //
-// cost is written as two 32-bit words: a device pointer need only be 4-byte aligned.  d2 = null stands for the empty map:
-// every voxel has the distance word `fill`, and the pool is not read.
+// cost is written as two 32-bit words: a device pointer need only be 4-byte aligned.  The distance word of a voxel is read
+// through ObstacleField (devmap_distance.h): on the empty map it has no array, every voxel has its `fill`, and the pool
+// is not read.
 #ifndef LA3DM_DEVMAP_PATHS_H
 #define LA3DM_DEVMAP_PATHS_H
 
@@ -41,8 +42,7 @@ struct PathsArgs {
     int lim;                // cells of a block per axis
     uint32_t g0[3], dims[3];
     la3dm_paths_params p;
-    const uint32_t *d2;     // [nx ny nz] distance_field's d2, or null: `fill` everywhere
-    uint32_t fill;
+    ObstacleField field;    // the d2 word of a voxel (devmap_distance.h)
     uint32_t *cost;         // [2 n_paths]: low word, high word
     uint32_t *steps, *stop, *min_d2, *reached;   // [n_paths] or null
     uint8_t *flags;         // [n_paths] or null
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(64 * kPathsWaves) void dm_paths_walk(PathsArgs a) {
                 if (!la3dm_region::path_inside(V, a.g0, a.dims, f)) {
                     halt = left = true;
                 } else {
-                    word = a.d2 ? a.d2[f] : a.fill;
+                    word = a.field.at(f);
                     if (la3dm_region::path_blocked(a.p.clearance, word))
                         halt = true;
                     else if (o > 0u)

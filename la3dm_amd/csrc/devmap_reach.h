@@ -8,7 +8,8 @@
 // p + di PY PZ + dj PZ + dk with no test at the faces and the wave cannot leave the region.
 //
 // dm_rc_bits    one probe per padded voxel of the region's interior and one ballot: the PASS stream (class in pass_mask,
-//               and with a clearance d2 == FAR at the unpadded index; d2 is distance_field's, computed before).
+//               and the word FAR at the unpadded index of the ObstacleField, devmap_distance.h: distance_field's d2 at
+//               radius = clearance, computed before, or FAR everywhere without a clearance).
 // dm_rc_seed    one lane per seed: range test, pass bit, then an atomic OR into the REACHED and the FRONT word.  The old
 //               value of the reached word tells whether the voxel is new: only then steps = 0 is written and the seed
 //               counted, so n_seeded counts a voxel once however often it is listed.
@@ -32,7 +33,9 @@
 #ifndef LA3DM_DEVMAP_REACH_H
 #define LA3DM_DEVMAP_REACH_H
 
+#include "devmap_distance.h"
 #include "devmap_frontier.h"
+#include "host/region_contract.h"
 
 namespace la3dm_dev {
 
@@ -67,8 +70,9 @@ __device__ __forceinline__ uint32_t rc_unpadded(const ReachArgs &a, uint32_t p) 
 // ---- stage 1: the pass stream ------------------------------------------------------------------------------------
 // `r` describes the UNPADDED region (g0, dims, pool).  The grid covers whole waves of the padded box: lanes beyond
 // a.total vote 0, so the bits past the end of the last word are clear.  `probe` = 0: the map has no block, every voxel is
-// MISSING and the table is not read.  d2 null: no clearance.
-__global__ __launch_bounds__(256) void dm_rc_bits(RegionArgs r, ReachArgs a, uint32_t pass_mask, uint32_t probe, const uint32_t *d2,
+// MISSING and the table is not read.  `field` (ObstacleField, devmap_distance.h): a voxel within the clearance of an
+// obstacle has a word other than FAR there and does not pass; without a clearance every word is FAR.
+__global__ __launch_bounds__(256) void dm_rc_bits(RegionArgs r, ReachArgs a, uint32_t pass_mask, uint32_t probe, ObstacleField field,
                                                   uint32_t *pass) {
     const uint32_t p = blockIdx.x * 256u + threadIdx.x;   // total <= 2^28: no overflow
     bool ok = false;
@@ -78,7 +82,7 @@ __global__ __launch_bounds__(256) void dm_rc_bits(RegionArgs r, ReachArgs a, uin
         if (k >= 1u && k <= a.nz && j >= 1u && j <= a.ny && i >= 1u && i <= a.nx) {   // pad cells are never passable and not probed
             const uint32_t cls = probe ? pool_class_at(r.pool, r.g0[0] + i - 1u, r.g0[1] + j - 1u, r.g0[2] + k - 1u) : kClsMissing;
             ok = (pass_mask >> cls) & 1u;
-            if (ok && d2) ok = d2[((i - 1u) * a.ny + (j - 1u)) * a.nz + (k - 1u)] == LA3DM_DF_FAR;
+            if (ok) ok = field.at(((i - 1u) * a.ny + (j - 1u)) * a.nz + (k - 1u)) == LA3DM_DF_FAR;
         }
     }
     pool_store_ballot(pass, p, a.total, ok);
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(256) void dm_rc_level(ReachArgs a, const uint32_t *
 #pragma unroll
                     for (int dk = -1; dk <= 1; ++dk) {
                         const int manhattan = (di ? 1 : 0) + (dj ? 1 : 0) + (dk ? 1 : 0);
-                        if (manhattan == 0 || manhattan > (kConn == 6 ? 1 : kConn == 18 ? 2 : 3)) continue;
+                        if (manhattan == 0 || manhattan > la3dm_region::move_reach(kConn)) continue;
                         fresh |= fr_window(front_in, a.n_words, base + di * sx + dj * sy + dk);
                     }
             fresh &= p;

@@ -15,8 +15,9 @@
 // dm_score_fold    chunks > 1 (few poses, the machine filled by chunks of the cloud instead): one wave per pose adds the
 //                  pose's partial records and writes the outputs.
 //
-// sum_d2 is written as two 32-bit words: a device pointer need only be 4-byte aligned.  cost = null stands for the empty
-// map: every voxel has the cost `fill`, and the pool is not read.  Every loop is bounded by an argument.
+// sum_d2 is written as two 32-bit words: a device pointer need only be 4-byte aligned.  The cost of a voxel is read through
+// ObstacleField (devmap_distance.h): on the empty map it has no array, every voxel costs its `fill`, and the pool is not
+// read.  Every loop is bounded by an argument.
 #ifndef LA3DM_DEVMAP_SCORE_H
 #define LA3DM_DEVMAP_SCORE_H
 
@@ -36,8 +37,7 @@ struct ScoreArgs {
     float resolution, block_size;
     int lim;                // cells of a block per axis
     uint32_t g0[3], dims[3];
-    const uint32_t *cost;   // [nx ny nz] distance_field's d2, or null: `fill` everywhere
-    uint32_t fill;
+    ObstacleField cost;     // the cost of a voxel: its d2 word (devmap_distance.h)
     uint32_t *partial;      // [n_poses chunks kScoreWords], chunks > 1
     uint32_t *sum_d2;       // [2 n_poses]: low word, high word
     uint32_t *counts;       // [5 n_poses] or null
@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void dm_score_pairs(ScoreArgs a) {
         uint32_t f = 0;
         uint32_t cls = la3dm_region::score_voxel(T, q[0], q[1], q[2], a.resolution, a.block_size, a.lim, a.g0, a.dims, f);
         if (cls == LA3DM_SCORE_HIT) {
-            const uint32_t v = a.cost ? a.cost[f] : a.fill;
+            const uint32_t v = a.cost.at(f);
             cls = la3dm_region::score_class(v);
             sum += cls != LA3DM_SCORE_FAR ? v : 0u;
         }

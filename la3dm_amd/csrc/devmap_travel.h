@@ -25,6 +25,7 @@
 #define LA3DM_DEVMAP_TRAVEL_H
 
 #include "devmap_brick.h"
+#include "devmap_distance.h"
 
 namespace la3dm_dev {
 
@@ -47,16 +48,16 @@ __device__ __forceinline__ uint32_t tv_entry(uint32_t d2, uint32_t clearance, ui
 
 // ---- stage 1: the entry words ------------------------------------------------------------------------------------------
 // `r` describes the region (g0, dims, pool).  `probe` = 0: the map has no block, every voxel is MISSING and the table is
-// not read.  d2 null: every voxel has d2 = d2_fill (no distance transform, or the empty map's uniform answer).
-__global__ __launch_bounds__(256) void dm_tv_enter(RegionArgs r, TravelArgs a, uint32_t pass_mask, uint32_t probe, const uint32_t *d2,
-                                                   uint32_t d2_fill, uint32_t clearance, uint32_t s2, uint32_t penalty) {
+// not read.  `field`: the d2 word of every voxel (ObstacleField, devmap_distance.h).
+__global__ __launch_bounds__(256) void dm_tv_enter(RegionArgs r, TravelArgs a, uint32_t pass_mask, uint32_t probe, ObstacleField field,
+                                                   uint32_t clearance, uint32_t s2, uint32_t penalty) {
     const uint32_t c = blockIdx.x * 256u + threadIdx.x;   // n_bricks * 512 <= 2^28: no overflow; the grid covers the cells exactly
     uint32_t i, j, k;
     brick_coords(a.g, c >> 9, c & 511u, i, j, k);
     uint32_t e = kTvBlocked;
     if (i < a.g.nx && j < a.g.ny && k < a.g.nz) {
         const uint32_t cls = probe ? pool_class_at(r.pool, r.g0[0] + i, r.g0[1] + j, r.g0[2] + k) : kClsMissing;
-        if ((pass_mask >> cls) & 1u) e = tv_entry(d2 ? d2[(i * a.g.ny + j) * a.g.nz + k] : d2_fill, clearance, s2, penalty);
+        if ((pass_mask >> cls) & 1u) e = tv_entry(field.at((i * a.g.ny + j) * a.g.nz + k), clearance, s2, penalty);
     }
     a.E[c] = e;
     a.g.val[0][c] = kTvNone;

@@ -1147,6 +1147,39 @@ void df_min_plus(const uint32_t *in, uint32_t *out, size_t planes, size_t L, siz
             }
         }
 }
+
+// the classes of a region's voxels, as box reads them
+std::vector<uint8_t> region_classes(const BGKOctoMap &map, const float *lo3, const uint32_t *dims3) {
+    std::vector<uint8_t> cls((size_t)dims3[0] * dims3[1] * dims3[2]);
+    map.box(lo3, dims3, la3dm_box_out{cls.data(), nullptr, nullptr, nullptr}, nullptr);
+    return cls;
+}
+
+// the obstacle field of a region: distance_field's d2 words
+std::vector<uint32_t> region_d2(const BGKOctoMap &map, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius) {
+    std::vector<uint32_t> d2((size_t)dims3[0] * dims3[1] * dims3[2]);
+    map.distance_field(lo3, dims3, obstacle_mask, radius, la3dm_distance_out{d2.data(), nullptr}, nullptr);
+    return d2;
+}
+
+// The moves of a connectivity in ascending order of their code (di + 1) * 9 + (dj + 1) * 3 + (dk + 1): the order in which
+// every host form tries its neighbours, and so the order its ties are broken in.  len = the non-zero components.
+struct Move {
+    int d[3], len;
+    uint32_t code;
+    ptrdiff_t offset(ptrdiff_t sx, ptrdiff_t sy) const { return d[0] * sx + d[1] * sy + d[2]; }   // in an array with these strides
+};
+std::vector<Move> connectivity_moves(uint32_t connectivity) {
+    std::vector<Move> moves;
+    for (int di = -1; di <= 1; ++di)
+        for (int dj = -1; dj <= 1; ++dj)
+            for (int dk = -1; dk <= 1; ++dk) {
+                const int len = std::abs(di) + std::abs(dj) + std::abs(dk);
+                if (len >= 1 && len <= la3dm_region::move_reach(connectivity))
+                    moves.push_back(Move{{di, dj, dk}, len, (uint32_t)((di + 1) * 9 + (dj + 1) * 3 + (dk + 1))});
+            }
+    return moves;
+}
 }  // namespace
 
 void BGKOctoMap::distance_field(const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
@@ -1164,12 +1197,7 @@ void BGKOctoMap::distance_field(const float *lo3, const uint32_t *dims3, uint32_
     region_anchor(lo3, dims3, la3dm_region::kDistance, out.d2 != nullptr || out.dist != nullptr, "distance_field", g0, inf);
     if (info) *info = inf;
     const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2], n = nx * ny * nz;
-    std::vector<uint8_t> cls(n);
-    la3dm_box_out bo;
-    bo.cls = cls.data();
-    bo.leaf_depth = nullptr;
-    bo.A = bo.B = nullptr;
-    box(lo3, dims3, bo, nullptr);
+    const std::vector<uint8_t> cls = region_classes(*this, lo3, dims3);
     std::vector<uint32_t> f(n), g(n);
     const uint32_t sat = radius + 1u;
 #pragma omp parallel for schedule(static)
@@ -1237,13 +1265,7 @@ void BGKOctoMap::frontier(const float *lo3, const uint32_t *dims3, uint32_t open
         }
     }
     std::vector<ptrdiff_t> offs;
-    const unsigned reach = connectivity == 6 ? 1u : connectivity == 18 ? 2u : 3u;
-    for (int di = -1; di <= 1; ++di)
-        for (int dj = -1; dj <= 1; ++dj)
-            for (int dk = -1; dk <= 1; ++dk) {
-                const unsigned s = (unsigned)(std::abs(di) + std::abs(dj) + std::abs(dk));
-                if (s >= 1 && s <= reach) offs.push_back(((ptrdiff_t)di * (ptrdiff_t)PY + dj) * (ptrdiff_t)PZ + dk);
-            }
+    for (const Move &m : connectivity_moves(connectivity)) offs.push_back(m.offset((ptrdiff_t)(PY * PZ), (ptrdiff_t)PZ));
     // per (i, j) row of the region: its scores and how many of them reach min_neighbours; then the rows' places in the list
     std::vector<uint8_t> own_score;
     uint8_t *score = out.score;
@@ -1304,20 +1326,9 @@ void BGKOctoMap::reach(const float *lo3, const uint32_t *dims3, const uint32_t *
     if (info) *info = inf;
     const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2], n = nx * ny * nz;
     const size_t PY = ny + 2, PZ = nz + 2;
-    std::vector<uint8_t> cls(n);
-    la3dm_box_out bo;
-    bo.cls = cls.data();
-    bo.leaf_depth = nullptr;
-    bo.A = bo.B = nullptr;
-    box(lo3, dims3, bo, nullptr);
+    const std::vector<uint8_t> cls = region_classes(*this, lo3, dims3);
     std::vector<uint32_t> d2;
-    if (clearance > 0) {
-        d2.resize(n);
-        la3dm_distance_out dd;
-        dd.d2 = d2.data();
-        dd.dist = nullptr;
-        distance_field(lo3, dims3, obstacle_mask, clearance, dd, nullptr);
-    }
+    if (clearance > 0) d2 = region_d2(*this, lo3, dims3, obstacle_mask, clearance);
     // open[p] = 1: padded voxel p is passable and not reached yet
     std::vector<uint8_t> open((nx + 2) * PY * PZ, 0);
     const auto padded = [&](size_t f) { return ((f / (ny * nz) + 1) * PY + (f / nz) % ny + 1) * PZ + f % nz + 1; };
@@ -1325,13 +1336,7 @@ void BGKOctoMap::reach(const float *lo3, const uint32_t *dims3, const uint32_t *
     for (size_t f = 0; f < n; ++f)
         open[padded(f)] = ((pass_mask >> cls[f]) & 1u) && (clearance == 0 || d2[f] == LA3DM_DF_FAR) ? 1 : 0;
     std::vector<ptrdiff_t> offs;
-    const unsigned far = connectivity == 6 ? 1u : connectivity == 18 ? 2u : 3u;
-    for (int di = -1; di <= 1; ++di)
-        for (int dj = -1; dj <= 1; ++dj)
-            for (int dk = -1; dk <= 1; ++dk) {
-                const unsigned s = (unsigned)(std::abs(di) + std::abs(dj) + std::abs(dk));
-                if (s >= 1 && s <= far) offs.push_back(((ptrdiff_t)di * (ptrdiff_t)PY + dj) * (ptrdiff_t)PZ + dk);
-            }
+    for (const Move &m : connectivity_moves(connectivity)) offs.push_back(m.offset((ptrdiff_t)(PY * PZ), (ptrdiff_t)PZ));
     std::vector<uint32_t> own_steps;
     uint32_t *steps = out.steps;
     if (steps == nullptr) {
@@ -1393,36 +1398,14 @@ void BGKOctoMap::travel(const float *lo3, const uint32_t *dims3, const uint32_t 
     if (info) *info = inf;
     const uint32_t nx = dims3[0], ny = dims3[1], nz = dims3[2];
     const size_t n = (size_t)nx * ny * nz;
-    std::vector<uint8_t> cls(n);
-    la3dm_box_out bo;
-    bo.cls = cls.data();
-    bo.leaf_depth = nullptr;
-    bo.A = bo.B = nullptr;
-    box(lo3, dims3, bo, nullptr);
+    const std::vector<uint8_t> cls = region_classes(*this, lo3, dims3);
     const uint32_t R = std::max(p.clearance, p.soft_radius);
     std::vector<uint32_t> d2;
-    if (R > 0) {
-        d2.resize(n);
-        la3dm_distance_out dd;
-        dd.d2 = d2.data();
-        dd.dist = nullptr;
-        distance_field(lo3, dims3, p.obstacle_mask, R, dd, nullptr);
-    }
+    if (R > 0) d2 = region_d2(*this, lo3, dims3, p.obstacle_mask, R);
     std::vector<uint32_t> entry(n);   // pen(v), or blocked
     for (size_t f = 0; f < n; ++f)
         entry[f] = ((p.pass_mask >> cls[f]) & 1u) ? la3dm_region::travel_entry(p, R > 0 ? d2[f] : LA3DM_DF_FAR) : la3dm_region::kTravelBlocked;
-    struct Move {
-        int d[3];
-        uint32_t cost, code;
-    };
-    std::vector<Move> moves;   // in the order of the code q
-    const int far = p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3;
-    for (int di = -1; di <= 1; ++di)
-        for (int dj = -1; dj <= 1; ++dj)
-            for (int dk = -1; dk <= 1; ++dk) {
-                const int s = std::abs(di) + std::abs(dj) + std::abs(dk);
-                if (s >= 1 && s <= far) moves.push_back(Move{{di, dj, dk}, p.move_cost[s - 1], (uint32_t)((di + 1) * 9 + (dj + 1) * 3 + (dk + 1))});
-            }
+    const std::vector<Move> moves = connectivity_moves(p.connectivity);   // in the order of the code q
     std::vector<uint32_t> own_cost;
     uint32_t *cost = out.cost;
     if (cost == nullptr) {
@@ -1455,7 +1438,7 @@ void BGKOctoMap::travel(const float *lo3, const uint32_t *dims3, const uint32_t 
         for (const Move &m : moves) {
             const size_t v = neighbour(i, j, k, m);
             if (v == n || entry[v] == la3dm_region::kTravelBlocked) continue;
-            const uint32_t cand = top.first + m.cost + entry[v];   // <= 2^31 + 2^17
+            const uint32_t cand = top.first + p.move_cost[m.len - 1] + entry[v];   // <= 2^31 + 2^17
             if (cand > p.max_cost || cand >= cost[v]) continue;
             cost[v] = cand;
             heap.push(Item(cand, (uint32_t)v));
@@ -1472,7 +1455,7 @@ void BGKOctoMap::travel(const float *lo3, const uint32_t *dims3, const uint32_t 
             const uint32_t k = (uint32_t)(f % nz), j = (uint32_t)((f / nz) % ny), i = (uint32_t)(f / ((size_t)nz * ny));
             for (const Move &m : moves) {
                 const size_t u = neighbour(i, j, k, m);
-                if (u != n && cost[u] != LA3DM_TRAVEL_NONE && cost[u] + m.cost + entry[f] == cost[f]) {
+                if (u != n && cost[u] != LA3DM_TRAVEL_NONE && cost[u] + p.move_cost[m.len - 1] + entry[f] == cost[f]) {
                     code = (uint8_t)m.code;
                     break;
                 }
@@ -1509,12 +1492,7 @@ void BGKOctoMap::clusters(const float *lo3, const uint32_t *dims3, const la3dm_c
     if (out) o = *out;
     const uint32_t nx = dims3[0], ny = dims3[1], nz = dims3[2];
     const size_t n = (size_t)nx * ny * nz;
-    std::vector<uint8_t> cls(n);
-    la3dm_box_out bo;
-    bo.cls = cls.data();
-    bo.leaf_depth = nullptr;
-    bo.A = bo.B = nullptr;
-    box(lo3, dims3, bo, nullptr);
+    const std::vector<uint8_t> cls = region_classes(*this, lo3, dims3);
     const uint32_t n_list = p.from_list ? p.n_members : 0;
     std::vector<uint8_t> member(n, 0);
     if (p.from_list) {
@@ -1523,14 +1501,7 @@ void BGKOctoMap::clusters(const float *lo3, const uint32_t *dims3, const la3dm_c
     } else {
         for (size_t f = 0; f < n; ++f) member[f] = (p.member_mask >> cls[f]) & 1u;
     }
-    const int far = p.connectivity == 6 ? 1 : p.connectivity == 18 ? 2 : 3;
-    int offs[26][3], n_offs = 0;
-    for (int di = -1; di <= 1; ++di)
-        for (int dj = -1; dj <= 1; ++dj)
-            for (int dk = -1; dk <= 1; ++dk) {
-                const int s = std::abs(di) + std::abs(dj) + std::abs(dk);
-                if (s >= 1 && s <= far) offs[n_offs][0] = di, offs[n_offs][1] = dj, offs[n_offs++][2] = dk;
-            }
+    const std::vector<Move> moves = connectivity_moves(p.connectivity);
     const uint32_t tile = p.tile ? p.tile : 0xFFFFFFFFu;   // (untiled: every voxel in tile 0)
     // the flood fill: comp[f] = the cluster's number among ALL clusters, in ascending order of their smallest index
     std::vector<uint32_t> comp(n, LA3DM_CLUSTERS_NONE), sizes, stack;
@@ -1547,8 +1518,8 @@ void BGKOctoMap::clusters(const float *lo3, const uint32_t *dims3, const la3dm_c
             stack.pop_back();
             ++count;
             const uint32_t k = f % nz, j = (f / nz) % ny, i = f / (nz * ny);
-            for (int q = 0; q < n_offs; ++q) {
-                const uint32_t ui = i + (uint32_t)offs[q][0], uj = j + (uint32_t)offs[q][1], uk = k + (uint32_t)offs[q][2];   // (0 - 1 wraps above nx)
+            for (const Move &mv : moves) {
+                const uint32_t ui = i + (uint32_t)mv.d[0], uj = j + (uint32_t)mv.d[1], uk = k + (uint32_t)mv.d[2];   // (0 - 1 wraps above nx)
                 if (ui >= nx || uj >= ny || uk >= nz || ui / tile != i / tile || uj / tile != j / tile || uk / tile != k / tile) continue;
                 const size_t u = ((size_t)ui * ny + uj) * nz + uk;
                 if (!member[u] || comp[u] != LA3DM_CLUSTERS_NONE) continue;
@@ -1734,13 +1705,7 @@ void BGKOctoMap::score_poses(const float *lo3, const uint32_t *dims3, const floa
     if (info) *info = inf;
     if (n_poses == 0) return;
     std::vector<uint32_t> d2;
-    if (n_points > 0) {
-        d2.resize((size_t)dims3[0] * dims3[1] * dims3[2]);
-        la3dm_distance_out dd;
-        dd.d2 = d2.data();
-        dd.dist = nullptr;
-        distance_field(lo3, dims3, obstacle_mask, radius, dd, nullptr);
-    }
+    if (n_points > 0) d2 = region_d2(*this, lo3, dims3, obstacle_mask, radius);
     const int lim = 1 << (block_depth - 1);
 #pragma omp parallel for schedule(static)
     for (uint32_t p = 0; p < n_poses; ++p) {
@@ -1782,11 +1747,7 @@ void BGKOctoMap::score_paths(const float *lo3, const uint32_t *dims3, const floa
     if (info) *info = inf;
     if (n_paths == 0) return;
     const la3dm_paths_params &p = *params;
-    std::vector<uint32_t> d2((size_t)dims3[0] * dims3[1] * dims3[2]);
-    la3dm_distance_out dd;
-    dd.d2 = d2.data();
-    dd.dist = nullptr;
-    distance_field(lo3, dims3, p.obstacle_mask, la3dm_region::paths_radius(p), dd, nullptr);
+    const std::vector<uint32_t> d2 = region_d2(*this, lo3, dims3, p.obstacle_mask, la3dm_region::paths_radius(p));
     const int lim = 1 << (block_depth - 1);
 #pragma omp parallel for schedule(dynamic, 16)
     for (uint32_t path = 0; path < n_paths; ++path) {

@@ -133,6 +133,10 @@ inline std::string frontier_check(uint32_t open_mask, uint32_t unknown_mask, uin
     return "";
 }
 
+// The neighbourhood of a connectivity (6, 18 or 26): the moves (di, dj, dk) in {-1, 0, 1}^3 with 1 to move_reach non-zero
+// components — faces, then edges, then corners.
+LA3DM_HD constexpr inline int move_reach(uint32_t connectivity) { return connectivity == 6 ? 1 : connectivity == 18 ? 2 : 3; }
+
 // the checks of gain's own arguments, before the region's
 inline std::string gain_check(uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps, uint32_t n, uint32_t m) {
     if (count_mask == 0 || (count_mask & ~0x1Fu)) return "count_mask must hold at least one of the bits 0x1F and no other";

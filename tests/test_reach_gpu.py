@@ -127,7 +127,8 @@ def test_word_and_row_boundaries(built):
 def test_batch_boundaries(built):
     """GPU test 3: lines 100 m from the scans of a non-empty map (every voxel MISSING, pass = MISSING: the probes and all
     kernels run) whose length puts the end of the wave before, on and after the end of a batch of level launches;
-    max_steps round a batch boundary; 3000 levels; steps and levels are the closed form; the empty map answers the same"""
+    max_steps round a batch boundary; 3000 levels; steps and levels are the closed form; the empty map answers the same, and with a
+    clearance as the host-mode empty map does"""
     import la3dm_amd
     md, mh = _bgk_pair()
     empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=0)
@@ -158,6 +159,19 @@ def test_batch_boundaries(built):
                 g = m.reach(lo, dims, [Q.flat(seed, dims)], passable=Q.MISS_M, connectivity=c)
                 want = Q.closed_form(dims, seed, c)
                 assert (g["steps"] == want).all() and g["levels"] == int(want.max()) >= 2999 and g["n_reached"] == want.size, (dims, c)
+    # a clearance on the empty map (the obstacle field is the same word everywhere, no transform runs), two bricks along x
+    # with a ragged edge: OCCUPIED as the obstacle leaves the box open, MISSING closes it (tests/test_reach_cpu.py's closed
+    # forms); the device-resident map == the host-mode one
+    host_empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=-1)
+    dims, n = (9, 5, 3), 9 * 5 * 3
+    for obstacles in (Q.OCC_M, Q.MISS_M):
+        gh = _compare(empty, host_empty, R.recipe_lo(), dims, [0], "empty map", targets=np.array([0, n - 1, n + 1], np.uint32),
+                      passable=Q.MISS_M, obstacles=obstacles, clearance=2)
+        if obstacles == Q.MISS_M:
+            assert (gh["steps"] == Q.NONE).all() and gh["n_seeded"] == gh["n_reached"] == gh["levels"] == 0
+        else:
+            want = Q.closed_form(dims, (0, 0, 0), 6)
+            assert (gh["steps"] == want).all() and gh["n_seeded"] == 1 and gh["n_reached"] == n and gh["levels"] == int(want.max())
     assert md.mirror_syncs() == syncs and empty.mirror_syncs() == 0
     # the host-mode map agrees where the line crosses a batch boundary
     _compare(md, mh, lo, (1, B + 2, 1), [0], "far line", passable=Q.MISS_M)

@@ -164,7 +164,8 @@ def test_batch_boundaries(built):
     kernels run) of 8 B k + {-1, 0, 1, 2} voxels, k = 1, 2, B = LA3DM_TRAVEL_BATCH, along each axis and from both ends: the
     wave crosses one brick per round, so it ends before, on and after the end of a batch of rounds (rounds, brick runs and
     capped runs as the helper's model counts them); cost = a |d|; max_cost
-    round the cost of the first voxel of the brick reached at a batch boundary; the empty map answers the same"""
+    round the cost of the first voxel of the brick reached at a batch boundary; the empty map answers the same, and with an
+    obstacle field as the host-mode empty map does"""
     import la3dm_amd
     md, mh, _ = _bgk_pair()
     empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=0)
@@ -202,6 +203,21 @@ def test_batch_boundaries(built):
             assert (g["cost"].reshape(-1) == np.where(want <= cut, want, T.NONE)).all(), cut
             assert g["max_cost"] == cut // 10 * 10 and g["n_reached"] == cut // 10 + 1, (cut, g["max_cost"])
     assert {B, B + 1, 2 * B, 2 * B + 1} <= rounds_seen, rounds_seen
+    # an obstacle field on the empty map (the same word everywhere, no transform runs), two bricks along x with a ragged
+    # edge: OCCUPIED as the obstacle leaves the box open and free of charge, MISSING closes it (clearance) or charges every
+    # step the whole penalty (soft radius alone: d2 = 0; the seed's own is not charged) — tests/test_travel_cpu.py's closed
+    # forms; the device-resident map == the host-mode one
+    host_empty = la3dm_amd.BGKOctoMap(**dict(la3dm_amd.BGK_YAML, block_depth=3), device=-1)
+    dims, n = (9, 5, 3), 9 * 5 * 3
+    for obstacles in (T.OCC_M, T.MISS_M):
+        for field in (dict(clearance=2), dict(clearance=0, soft_radius=3, penalty=50)):
+            _, gh = _compare(empty, host_empty, R.recipe_lo(), dims, [0], "empty map", targets=np.array([0, n - 1, n + 1], np.uint32),
+                             passable=T.MISS_M, obstacles=obstacles, connectivity=6, move_cost=(10, 10, 10), **field)
+            if obstacles == T.MISS_M and field["clearance"]:
+                assert (gh["cost"] == T.NONE).all() and (gh["parent"] == 255).all() and gh["n_seeded"] == gh["n_reached"] == gh["max_cost"] == 0
+            else:
+                want = T.closed_form(dims, (0, 0, 0), 6, (10 + (50 if obstacles == T.MISS_M else 0),) * 3)
+                assert (gh["cost"] == want).all() and gh["n_seeded"] == 1 and gh["n_reached"] == n and gh["max_cost"] == int(want.max())
     assert md.mirror_syncs() == syncs and empty.mirror_syncs() == 0
     # the host-mode map agrees where the line crosses a batch boundary
     _compare(md, mh, lo, (1, 8 * B + 2, 1), [0], "far line", passable=T.MISS_M)
