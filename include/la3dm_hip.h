@@ -502,6 +502,69 @@ typedef struct la3dm_merge_stats {
     uint64_t cells_kept, cells_copied, cells_fused;
 } la3dm_merge_stats;
 int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la3dm_merge_stats *stats /* may be NULL */);
+/* Diff: the finest-layer cells whose class differs between the live map (NOW) and a map stream (THEN), on the GPU
+ * (csrc/devmap_diff.h; the rule per block on flat arrays, which the host-mode map runs, is csrc/host/diff_block.h — both
+ * give the same lists and counts).  merge's read-only sibling; all four map classes.
+ *
+ *   The stream is a pack / pack_region / evict of this or another map.  It is validated and compared with the context
+ *   exactly as la3dm_devmap_unpack_host and merge do: variant, block_depth, nodes_per_block and, by bit pattern, resolution,
+ *   init_A, init_B.  The map is never modified.
+ *   COMPARED BLOCKS.  Every block the stream names, in STREAM ORDER.  With params->map_only != 0 also every block the map
+ *     holds that the stream does not name, after the stream's, in the order pack would write them: ascending pool slot on
+ *     the device pool, ascending key on a host-mode map.  No other block is read.
+ *   PER FINEST-LAYER CELL c of a compared block (c = the finest-layer index as Block::get_node builds it, 0 .. 8^(block_depth
+ *     - 1) - 1): then = the class of the stream's covering leaf of c, now = the class of the map's covering leaf of c.  The
+ *     class is S & 7 of that leaf as box reports it — FREE 0, OCCUPIED 1, UNKNOWN 2, and 4 for an UNCERTAIN leaf of a BGK-LV
+ *     map — and LA3DM_RAY_MISSING (3) on the side that has no such block (a covering leaf is never PRUNED, so 3 is
+ *     unambiguous).  The cell is VALUE-CHANGED when then == now and A or B of the two covering leaves differ bit for bit.
+ *   STATS (optional, always complete whatever cap is): n_stream_blocks; n_map_only_blocks (0 when map_only is 0);
+ *     n_missing_now = the stream blocks the map lacks; pairs[5 * then + now] = the compared cells with that pair;
+ *     value_changed[cls] = the value-changed cells of that class — counted, for all five classes, when params->value_mask
+ *     is not 0; with value_mask 0 no A or B is read and the five counts are 0.
+ *   SELECTION.  A cell is listed when bit 5 * then + now of params->pair_mask is set, or when it is value-changed and bit
+ *     now of params->value_mask is set.  LA3DM_DIFF_PAIRS_CHANGED = the 20 off-diagonal pairs.  The list follows the block
+ *     order above and, within a block, ascending c.  *n_found = the number selected, whatever cap is; the first
+ *     min(*n_found, cap) entries are written, nothing past them.  cap = 0 with out NULL only counts (frontier's convention).
+ *   OUTPUTS (la3dm_diff_out, every pointer optional, host memory): block_key; cell = c; code = then | now << 4; centre = the
+ *     cell's centre as la3dm_devmap_export_cells / la3dm_map_dump_leaves compute a finest leaf's location: the LUT entry of
+ *     node layer_base(block_depth - 1) + c plus axis_center of the key's field, in fp32, those two operands in that order;
+ *     A, B = the NOW covering leaf's values, init_A, init_B where now is MISSING.
+ *   An empty stream with map_only 0 is a no-op (*n_found = 0, zero stats, no launch); an empty map compares every stream
+ *     block against MISSING.
+ *   Refusals — LA3DM_ERR_ARG, the text through la3dm_last_error, NOTHING written (not *n_found, not stats, no buffer): a
+ *     stream the validator rejects; a mismatch with the context; a poisoned map; params or n_found NULL; pair_mask bits
+ *     above bit 24 or value_mask bits above bit 4; cap > 0 with out NULL; a block_depth whose four waves' staging — the
+ *     mask words, their prefixes and the block's S bytes per wave — does not fit a compute unit's LDS (that is block_depth 6,
+ *     which la3dm_devmap_create does not accept today: every depth a device map can have, 1 to 5, runs); more compared blocks than 2^32 - 2; more than 2^32 - 1 selected cells, which is known once they are counted.
+ *   Launch chain: one upload of the stream, dm_merge_find (the pool slot per stream block); with map_only a scatter of
+ *     marks, a select over the pool's slots, the map's one-launch scan and a list of the unmarked slots; dm_diff_count (one
+ *     wave per compared block: both trees climbed per finest cell, 64 cells at a time, the counters from ballots), the scan
+ *     over the blocks' counts, ONE read-back of the counters and *n_found; with cap > 0 dm_diff_emit and ONE copy of the
+ *     list.  No download of the pool, no host pass over cells; the host mirror is neither refreshed nor marked stale.
+ *     Measured on a 44 k-block map: 2.2 ms to count, 2.3 ms with the list of 91 k changed cells, of which
+ *     the launches are 0.1 ms and the host-side validation and upload of the stream the rest; pack() alone takes 0.8 ms,
+ *     pack() plus a host pass over both streams 28 ms. */
+#define LA3DM_DIFF_PAIRS_CHANGED 0x0FBEFBEu
+typedef struct la3dm_diff_params {
+    uint32_t pair_mask;    /* bit 5 * then + now */
+    uint32_t value_mask;   /* bit now */
+    uint32_t map_only;     /* != 0: the map's blocks the stream does not name are compared too (then = MISSING) */
+} la3dm_diff_params;
+typedef struct la3dm_diff_out {
+    int64_t *block_key;   /* [cap] or NULL */
+    uint32_t *cell;       /* [cap] or NULL */
+    uint8_t *code;        /* [cap] or NULL */
+    float *centre;        /* [3 cap] or NULL */
+    float *A, *B;         /* [cap] or NULL */
+} la3dm_diff_out;
+typedef struct la3dm_diff_stats {
+    uint64_t n_stream_blocks, n_map_only_blocks, n_missing_now;
+    uint64_t pairs[25];
+    uint64_t value_changed[5];
+} la3dm_diff_stats;
+int la3dm_devmap_diff_host(la3dm_devmap *dm, const void *buf, uint64_t size, const la3dm_diff_params *params, uint64_t cap,
+                           const la3dm_diff_out *out /* may be NULL with cap 0 */, uint64_t *n_found,
+                           la3dm_diff_stats *stats /* may be NULL */);
 /* The map as a rolling window: the stream of SOME blocks, and blocks leaving the map (csrc/devmap_evict.h; the region test,
  * shared with the host-mode map: csrc/host/region_blocks.h).  All four map classes, every block_depth pack accepts.
  *

@@ -228,6 +228,17 @@ int la3dm_map_load(la3dm_map *m, const char *path);
  * the map as it was (-1, la3dm_map_last_error). */
 int la3dm_map_merge(la3dm_map *m, const void *buf, uint64_t size, la3dm_merge_stats *stats);
 int la3dm_map_merge_file(la3dm_map *m, const char *path, la3dm_merge_stats *stats);
+/* BGKOctoMap::diff, all four classes: the finest cells whose class — or, with params->value_mask, whose A or B — differs
+ * between the map (now) and a stream (then), as a list and as 5 x 5 pair counts (the compared blocks, the classes, the
+ * selection, the outputs and the refusals: include/la3dm_hip.h, la3dm_devmap_diff_host).  The map is not changed.  A
+ * device-resident map compares on the GPU pool (no mirror refresh, the mirror not marked stale), a host-mode map runs
+ * csrc/host/diff_block.h over its blocks (map-only blocks in ascending key order); both give the same list and counts.
+ * cap = 0 with out NULL only counts; stats may be NULL.  diff_file reads path and compares with it.  A refusal (-1,
+ * la3dm_map_last_error) writes nothing. */
+int la3dm_map_diff(const la3dm_map *m, const void *buf, uint64_t size, const la3dm_diff_params *params, uint64_t cap,
+                   const la3dm_diff_out *out, uint64_t *n_found, la3dm_diff_stats *stats);
+int la3dm_map_diff_file(const la3dm_map *m, const char *path, const la3dm_diff_params *params, uint64_t cap, const la3dm_diff_out *out,
+                        uint64_t *n_found, la3dm_diff_stats *stats);
 /* BGKOctoMap::pack_region / erase_region / evict / evict_file, all four classes: the map as a rolling window (the region,
  * the stream, the pool after an erase and the refusals: include/la3dm_hip.h, la3dm_devmap_pack_region_host).  The region is
  * given by two world points lo3, hi3: the box of blocks from the block that holds lo3 to the block that holds hi3

@@ -1,7 +1,7 @@
 """la3dm_amd — MI355X-native (gfx950) implementation of la3dm's per-scan occupancy-inference
 hot path behind the reference's BGKOctoMap interface.  See DESIGN.md / INTEGRATION.md."""
 from .bgkoctomap import BGKOctoMap, GPOctoMap, BGKLVOctoMap, BGKLOctoMap, PackedScan, FREE, OCCUPIED, UNKNOWN, PRUNED  # noqa: F401
-from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR_MAX_CELLS  # noqa: F401
+from .bgkoctomap import MISSING, RAY_HIT, RAY_TRUNCATED, RAY_INVALID, DF_FAR, FR_MAX_CELLS, DIFF_PAIRS_CHANGED  # noqa: F401
 from .bgkoctomap import GAIN_MAX_CELLS, GAIN_MAX_RAYS, GAIN_MAX_WORDS  # noqa: F401
 from .bgkoctomap import SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS, poses_xyz_yaw  # noqa: F401
 from .bgkoctomap import SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID  # noqa: F401

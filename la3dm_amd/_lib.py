@@ -152,6 +152,19 @@ class MergeStats(C.Structure):   # la3dm_merge_stats
     _fields_ = [(k, C.c_uint64) for k in ("n_blocks", "n_created", "cells_kept", "cells_copied", "cells_fused")]
 
 
+class DiffParams(C.Structure):   # la3dm_diff_params
+    _fields_ = [(k, C.c_uint32) for k in ("pair_mask", "value_mask", "map_only")]
+
+
+class DiffOut(C.Structure):      # la3dm_diff_out
+    _fields_ = [(k, C.c_void_p) for k in ("block_key", "cell", "code", "centre", "A", "B")]
+
+
+class DiffStats(C.Structure):    # la3dm_diff_stats
+    _fields_ = [(k, C.c_uint64) for k in ("n_stream_blocks", "n_map_only_blocks", "n_missing_now")] + \
+               [("pairs", C.c_uint64 * 25), ("value_changed", C.c_uint64 * 5)]
+
+
 class EraseStats(C.Structure):   # la3dm_erase_stats
     _fields_ = [(k, C.c_uint64) for k in ("n_removed", "n_moved", "n_blocks")]
 
@@ -185,6 +198,7 @@ HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_des
                "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device",
                "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device",
                "la3dm_devmap_pack_host", "la3dm_devmap_unpack_host", "la3dm_pack_info", "la3dm_devmap_merge_host",
+               "la3dm_devmap_diff_host",
                "la3dm_devmap_pack_region_host", "la3dm_devmap_erase_region_host"]
 MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
                "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
@@ -201,7 +215,7 @@ MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv",
                "la3dm_map_distance_field", "la3dm_map_frontier", "la3dm_map_gain", "la3dm_map_score_poses", "la3dm_map_reach",
                "la3dm_map_score_paths",
                "la3dm_map_travel", "la3dm_map_clusters", "la3dm_map_pack", "la3dm_map_unpack", "la3dm_map_save",
-               "la3dm_map_load", "la3dm_map_merge", "la3dm_map_merge_file", "la3dm_map_pack_region",
+               "la3dm_map_load", "la3dm_map_merge", "la3dm_map_merge_file", "la3dm_map_diff", "la3dm_map_diff_file", "la3dm_map_pack_region",
                "la3dm_map_erase_region", "la3dm_map_evict", "la3dm_map_evict_file"]
 
 _hip = None
@@ -326,6 +340,9 @@ def hip():
         L.la3dm_devmap_unpack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.la3dm_devmap_merge_host.restype = C.c_int
         L.la3dm_devmap_merge_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MergeStats)]
+        L.la3dm_devmap_diff_host.restype = C.c_int
+        L.la3dm_devmap_diff_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DiffParams), C.c_uint64, C.POINTER(DiffOut),
+                                             C.POINTER(C.c_uint64), C.POINTER(DiffStats)]
         L.la3dm_devmap_pack_region_host.restype = C.c_int
         L.la3dm_devmap_pack_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_uint64,
                                                     C.POINTER(C.c_uint64)]
@@ -415,6 +432,12 @@ def maplib():
         M.la3dm_map_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MergeStats)]
         M.la3dm_map_merge_file.restype = C.c_int
         M.la3dm_map_merge_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(MergeStats)]
+        M.la3dm_map_diff.restype = C.c_int
+        M.la3dm_map_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DiffParams), C.c_uint64, C.POINTER(DiffOut),
+                                     C.POINTER(C.c_uint64), C.POINTER(DiffStats)]
+        M.la3dm_map_diff_file.restype = C.c_int
+        M.la3dm_map_diff_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(DiffParams), C.c_uint64, C.POINTER(DiffOut),
+                                          C.POINTER(C.c_uint64), C.POINTER(DiffStats)]
         M.la3dm_map_pack_region.restype = C.c_int
         M.la3dm_map_pack_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         M.la3dm_map_erase_region.restype = C.c_int

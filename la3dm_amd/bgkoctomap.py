@@ -18,6 +18,7 @@ MISSING = 3
 RAY_HIT, RAY_TRUNCATED, RAY_INVALID = 1, 2, 4
 DF_FAR = 0xFFFFFFFF                 # LA3DM_DF_FAR: beyond the radius of distance_field (dist: +inf)
 FR_MAX_CELLS = 1 << 28             # LA3DM_FR_MAX_CELLS: voxels of frontier's region padded by one on every side
+DIFF_PAIRS_CHANGED = 0x0FBEFBE      # LA3DM_DIFF_PAIRS_CHANGED: the 20 (then, now) pairs with then != now, bit 5 * then + now
 GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: voxels of gain's region, n * m rays, n * W set words
 SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS = 1 << 28, 1 << 20, 1 << 20, 1 << 32, 255   # LA3DM_SCORE_MAX_*
 SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID = range(5)   # LA3DM_SCORE_*: the columns of score_poses' counts
@@ -716,6 +717,82 @@ class BGKOctoMap:
         stats = _lib.MergeStats()
         self._chk(self._M.la3dm_map_merge_file(self._h, os.fsencode(path), C.byref(stats)))
         return {k: int(getattr(stats, k)) for k, _ in _lib.MergeStats._fields_}
+
+    _DIFF_FIELDS = dict(block_key=(np.int64, 1), cell=(np.uint32, 1), code=(np.uint8, 1), centre=(np.float32, 3), A=(np.float32, 1),
+                        B=(np.float32, 1))
+
+    def _diff(self, fn, head, pairs, values, map_only, fields, cap):
+        """what diff and diff_file share: the masks, the two-call protocol, the dict"""
+        if isinstance(pairs, str):
+            if pairs != "changed":
+                raise ValueError('diff: pairs is "changed", an integer mask or an iterable of (then, now) class names')
+            pair_mask = DIFF_PAIRS_CHANGED
+        elif isinstance(pairs, (int, np.integer)):
+            pair_mask = int(pairs)
+        else:
+            pair_mask = 0
+            for then, now in pairs:
+                pair_mask |= 1 << (5 * _RAY_CLASS[then] + _RAY_CLASS[now])
+        if isinstance(values, str):
+            values = (values,)
+        value_mask = int(values) if isinstance(values, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(values))
+        if not 0 <= pair_mask < 2 ** 32 or not 0 <= value_mask < 2 ** 32:
+            raise ValueError("diff: pairs and values must fit 32 bits")
+        if isinstance(fields, str):
+            fields = (fields,)
+        bad = set(fields) - set(self._DIFF_FIELDS)
+        if bad:
+            raise ValueError(f"diff: unknown fields {sorted(bad)}")
+        if cap is not None and not 0 <= int(cap) < 2 ** 64:
+            raise ValueError("diff: cap must fit 64 bits")
+        params = _lib.DiffParams(pair_mask, value_mask, 1 if map_only else 0)
+        stats = _lib.DiffStats()
+        found = C.c_uint64(0)
+        if cap is None:   # the two-call protocol: count, then fill exactly n
+            self._chk(fn(*head, C.byref(params), 0, None, C.byref(found), C.byref(stats)))
+            k = int(found.value)
+        else:
+            k = min(int(cap), 2 ** 32 - 1)
+        out = {f: np.empty((k, w) if w > 1 else k, t) for f, (t, w) in self._DIFF_FIELDS.items() if f in fields}
+        if cap is not None or (k and out):
+            o = _lib.DiffOut(*[out[f].ctypes.data if f in out and k else None for f, _ in _lib.DiffOut._fields_])
+            self._chk(fn(*head, C.byref(params), k, C.byref(o), C.byref(found), C.byref(stats)))
+        m = min(int(found.value), k)
+        out = {f: v[:m] for f, v in out.items()}
+        out["n"] = int(found.value)
+        out["pairs"] = np.array(stats.pairs, np.uint64).reshape(5, 5)
+        out["value_changed"] = np.array(stats.value_changed, np.uint64)
+        out.update({f: int(getattr(stats, f)) for f in ("n_stream_blocks", "n_map_only_blocks", "n_missing_now")})
+        return out
+
+    def diff(self, stream_or_map, pairs="changed", values=(), map_only=True, fields=("block_key", "cell", "code"), cap=None):
+        """What changed: the finest cells whose class differs between this map (now) and a stream of pack() / pack_region() /
+        evict() — bytes, a uint8 array, or another map of this map's class, packed first — (then); contract:
+        include/la3dm_hip.h, la3dm_devmap_diff_host.  Compared are the blocks the stream names, in stream order, and with
+        map_only the map's other blocks after them (pack()'s order).  The class is that of the cell's covering leaf: free 0,
+        occupied 1, unknown 2, uncertain 4 (BGK-LV), missing 3 on the side that has no such block.  pairs selects (then, now)
+        pairs: "changed" (every pair with then != now), an integer mask (bit 5 then + now) or an iterable of pairs of class
+        names, e.g. [("free", "occupied"), ("missing", "occupied")]; values: class names (or a bit mask) for which cells of
+        unchanged class whose A or B changed bit for bit are listed too.  Returns a dict: n = the number of selected cells;
+        the arrays named in fields out of block_key, cell (the finest-layer index in the block), code (then | now << 4),
+        centre (n, 3), A, B (the map's values now); pairs (5, 5) uint64 = the compared cells per [then, now];
+        value_changed (5,) (all zero unless values is given); n_stream_blocks, n_map_only_blocks, n_missing_now.  cap=None
+        counts first and then fills exactly n entries; an integer cap fills the first min(n, cap) and n is still the total.
+        The map is not changed.  A device-resident map compares on the GPU pool (no host mirror refresh), a host-mode map
+        on the CPU: the same list and counts.  A refused stream raises RuntimeError."""
+        if isinstance(stream_or_map, BGKOctoMap):
+            if type(stream_or_map) is not type(self):
+                raise TypeError(f"diff: a {type(stream_or_map).__name__} is not compared with a {type(self).__name__}")
+            stream_or_map = stream_or_map.pack()
+        stream = stream_or_map
+        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
+                                   np.uint8).reshape(-1)
+        return self._diff(self._M.la3dm_map_diff, (self._h, buf.ctypes.data if buf.size else None, buf.size), pairs, values, map_only,
+                          fields, cap)
+
+    def diff_file(self, path, pairs="changed", values=(), map_only=True, fields=("block_key", "cell", "code"), cap=None):
+        """diff() against the file at path (a file save() or evict_file() wrote)"""
+        return self._diff(self._M.la3dm_map_diff_file, (self._h, os.fsencode(path)), pairs, values, map_only, fields, cap)
 
     @staticmethod
     def _region_points(lo, hi):

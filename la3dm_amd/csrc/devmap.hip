@@ -38,6 +38,7 @@
 #include "devmap_clusters.h"
 #include "devmap_pack.h"
 #include "devmap_merge.h"
+#include "devmap_diff.h"
 #include "devmap_evict.h"
 #include "host/pack_format.h"
 #include "host/region_blocks.h"
@@ -340,12 +341,14 @@ constexpr const char *kPoisonedText = "the map is poisoned (a failed insert left
 
 // A scan whose total the host needs before it can go on: the scan over n >= 1 elements, *total = out[n - 1] (callers close
 // `in` with an entry of its own, so that is the sum of the rest) and the error word read back, one synchronisation.  A scan
-// that found its state in use poisons the map.
-static int scan_total(la3dm_devmap *dm, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total) {
+// that found its state in use poisons the map.  also_bytes > 0: device bytes that travel with the same read-back.
+static int scan_total(la3dm_devmap *dm, const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *total, void *also_dst = nullptr,
+                      const void *also_src = nullptr, size_t also_bytes = 0) {
     hipStream_t st = dm->ctx->stream;
     int rc = exclusive_scan(dm, in, out, n);
     if (rc != LA3DM_OK) return rc;
     uint32_t err = 0;
+    if (also_bytes) DM_TRY(hipMemcpyAsync(also_dst, also_src, also_bytes, hipMemcpyDeviceToHost, st));
     DM_TRY(hipMemcpyAsync(total, out + n - 1, 4, hipMemcpyDeviceToHost, st));
     DM_TRY(hipMemcpyAsync(&err, dm->d_cnt + kCntError, 4, hipMemcpyDeviceToHost, st));
     DM_TRY(hipStreamSynchronize(st));
@@ -2682,6 +2685,156 @@ int la3dm_devmap_merge_host(la3dm_devmap *dm, const void *buf, uint64_t size, la
         stats->cells_kept = h_cells[0];
         stats->cells_copied = h_cells[1];
         stats->cells_fused = h_cells[2];
+    }
+    return LA3DM_OK;
+}
+
+// The cells whose class differs between the live map and a stream (contract: include/la3dm_hip.h; kernels: devmap_diff.h).
+// Every refusal comes before the first allocation or launch, but one: whether more than 2^32 - 1 cells are selected is known
+// only after dm_diff_count — it writes scratch alone, and nothing of the caller's is written before that check.
+// Launch chain: one upload, dm_merge_find; with map_only dm_diff_mark, dm_diff_select, the one-launch scan, dm_diff_list (the
+// number of map-only blocks stays on the device: the count launch covers n_stream + n_pool waves and reads it there);
+// dm_diff_count, the scan over the counts, ONE read-back (the counters, the total, the scan's error word); with cap > 0 and a
+// list asked for dm_diff_emit and ONE copy of the list.  Nothing of the map is written, on the device or on the host.
+int la3dm_devmap_diff_host(la3dm_devmap *dm, const void *buf, uint64_t size, const la3dm_diff_params *params, uint64_t cap,
+                           const la3dm_diff_out *out, uint64_t *n_found, la3dm_diff_stats *stats) {
+    if (dm) dm->mailbox_pending = 0;   // (left behind by a call that failed between a publishing launch and its read_counters)
+    if (!dm) return LA3DM_ERR_ARG;
+    const char *who = "la3dm_devmap_diff_host";
+    la3dm_ctx *ctx = dm->ctx;
+    la3dm_pack_header h;
+    DM_OK(admit_stream(dm, who, buf, size, &h));
+    if (!params) return refuse(dm, who, "params is NULL");
+    if (!n_found) return refuse(dm, who, "n_found is NULL");
+    if (params->pair_mask >> 25) return refuse(dm, who, "pair_mask has bits above bit 24 (25 pairs, bit 5 * then + now)");
+    if (params->value_mask >> 5) return refuse(dm, who, "value_mask has bits above bit 4 (5 classes)");
+    if (cap > 0 && !out) return refuse(dm, who, "out is NULL with cap > 0");
+    if (!diff_lds_fits(dm->depth))
+        return refuse(dm, who, "block_depth " + std::to_string(dm->depth) + " needs " + std::to_string(kPackWaves * diff_lds_stride(dm->depth)) +
+                                   " bytes of LDS per workgroup, a compute unit has " + std::to_string(kMergeLdsPerCu) + " (diff runs at block_depth 1 to 5)");
+    la3dm_diff_out o;
+    memset(&o, 0, sizeof(o));
+    if (out) o = *out;
+    const bool want_list = cap > 0 && (o.block_key || o.cell || o.code || o.centre || o.A || o.B);
+    if (want_list && o.centre && dm->npb > ctx->lut_count) return refuse(dm, who, "the context's voxel LUT does not reach the finest layer");
+    const uint64_t nb = h.n_blocks;
+    const uint32_t n_pool = params->map_only ? dm->n_blocks : 0u, npb = dm->npb;
+    if (nb + n_pool > 0xFFFFFFFEull) return refuse(dm, who, "more than 2^32 - 2 blocks to compare");
+    la3dm_diff_stats S;
+    memset(&S, 0, sizeof(S));
+    if (nb + n_pool == 0) {   // nothing to compare: no launch
+        *n_found = 0;
+        if (stats) *stats = S;
+        return LA3DM_OK;
+    }
+    DM_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t n_grid = (uint32_t)(nb + n_pool);
+    const la3dm_pack::Layout l = la3dm_pack::layout(nb, h.n_leaves, npb);
+    if (nb) DM_RESERVE(dm->pack_stream, l.total);
+    // scratch: slot[nb], mark[n_pool], flag[n_pool + 1], rank[n_pool + 1], only[n_pool], counts[n_grid + 1], offset[n_grid + 1], the counters
+    DM_RESERVE(dm->pack_counts, 4ull * (nb + 4ull * n_pool + 2 + 2ull * n_grid + 2) + 8 + 8ull * kDiffCntWords);
+    uint8_t *arena = (uint8_t *)dm->pack_stream.ptr;
+    uint32_t *slot = (uint32_t *)dm->pack_counts.ptr, *mark = slot + nb, *flag = mark + n_pool, *rank = flag + n_pool + 1, *only = rank + n_pool + 1;
+    uint32_t *counts = only + n_pool, *offset = counts + n_grid + 1;
+    unsigned long long *cnt = (unsigned long long *)(((uintptr_t)(offset + n_grid + 1) + 7u) & ~(uintptr_t)7u);
+    DM_TRY(hipMemsetAsync(cnt, 0, 8ull * kDiffCntWords, st));
+    if (nb) {
+        DM_TRY(hipMemcpyAsync(arena, buf, l.total, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(dm_merge_find, dim3(cdiv(nb + 1, 256)), dim3(256), 0, st, (const long long *)(arena + l.keys), (uint32_t)nb, pool_view(dm),
+                           dm->n_blocks && dm->tab_cap ? 1u : 0u, slot, counts);   // (its "new" flags land in counts, which dm_diff_count overwrites)
+        DM_TRY(hipGetLastError());
+    }
+    dm->counters_clean = false;   // (the scans may flag a dirty state in the counter block)
+    if (n_pool) {
+        DM_TRY(hipMemsetAsync(mark, 0, 4ull * n_pool, st));
+        if (nb) {
+            hipLaunchKernelGGL(dm_diff_mark, dim3(cdiv(nb, 256)), dim3(256), 0, st, (const uint32_t *)slot, (uint32_t)nb, mark);
+            DM_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(dm_diff_select, dim3(cdiv(n_pool + 1, 256)), dim3(256), 0, st, (const uint32_t *)mark, n_pool, flag);
+        DM_TRY(hipGetLastError());
+        DM_OK(exclusive_scan(dm, flag, rank, n_pool + 1u));
+        hipLaunchKernelGGL(dm_diff_list, dim3(cdiv(n_pool, 256)), dim3(256), 0, st, n_pool, (const uint32_t *)flag, (const uint32_t *)rank, only);
+        DM_TRY(hipGetLastError());
+    }
+    DiffArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = dm->A;
+    a.B = dm->B;
+    a.S = dm->S;
+    a.blk_key = (const long long *)dm->blk_key;
+    a.npb = npb;
+    a.block_depth = dm->depth;
+    a.n_stream = (uint32_t)nb;
+    a.n_grid = n_grid;
+    a.n_only = n_pool ? rank + n_pool : nullptr;
+    a.slot = slot;
+    a.only = only;
+    if (nb) {   // (no stream block: no wave reads a section)
+        a.keys = (const long long *)(arena + l.keys);
+        a.leaf_off = (const uint32_t *)(arena + l.leaf_off);
+        a.mask = (const uint32_t *)(arena + l.mask);
+        a.i_state = arena + l.state;
+        a.i_A = (const float *)(arena + l.A);
+        a.i_B = (const float *)(arena + l.B);
+    }
+    a.a0 = dm->init_A;
+    a.b0 = dm->init_B;
+    a.pair_mask = params->pair_mask;
+    a.value_mask = params->value_mask;
+    a.counts = counts;
+    a.cnt = cnt;
+    const uint32_t lds = kPackWaves * diff_lds_stride(dm->depth);
+    hipLaunchKernelGGL(params->value_mask ? dm_diff_count<true> : dm_diff_count<false>, dim3(cdiv(n_grid + 1, kPackWaves)), dim3(64 * kPackWaves), lds, st, a);
+    DM_TRY(hipGetLastError());
+    std::vector<unsigned long long> lines(kDiffCntWords);
+    uint32_t total = 0;
+    DM_OK(scan_total(dm, counts, offset, n_grid + 1u, &total, lines.data(), cnt, 8ull * kDiffCntWords));   // (synchronised: buf is the caller's again)
+    unsigned long long sum[kDiffCnt];
+    for (uint32_t k = 0; k < kDiffCnt; ++k) {
+        sum[k] = 0;
+        for (uint32_t s = 0; s < kDiffCntSlots; ++s) sum[k] += lines[(size_t)(kDiffCnt * s + k) * kMergeCntStride];
+    }
+    const unsigned long long selected = sum[kDiffCntSelected], n_only = sum[kDiffCntOnly];
+    if (selected > 0xFFFFFFFFull) return refuse(dm, who, "more than 2^32 - 1 cells are selected (" + std::to_string(selected) + ")");
+    if (selected != total || n_only > n_pool || sum[kDiffCntMissing] > nb)
+        return dm_fail(dm, LA3DM_ERR_HIP, "la3dm_devmap_diff_host: the counters and the scan disagree (internal error)");
+    const uint64_t m = std::min<uint64_t>(cap, selected);
+    if (want_list && m) {
+        Stage s(dm, true);
+        s.out(o.block_key, m);
+        s.out(o.cell, m);
+        s.out(o.code, m);
+        s.out(o.centre, 3 * m);
+        s.out(o.A, m);
+        s.out(o.B, m);
+        DM_OK(s.reserve());
+        a.n_grid = (uint32_t)(nb + n_only);
+        a.offset = offset;
+        a.cap = (uint32_t)m;
+        a.lut = ctx->d_lut;
+        a.block_size = dm->block_size;
+        a.o_key = (long long *)o.block_key;
+        a.o_cell = o.cell;
+        a.o_code = o.code;
+        a.o_centre = o.centre;
+        a.o_A = o.A;
+        a.o_B = o.B;
+        hipLaunchKernelGGL(params->value_mask || o.A || o.B ? dm_diff_emit<true> : dm_diff_emit<false>, dim3(cdiv(a.n_grid, kPackWaves)),
+                           dim3(64 * kPackWaves), lds, st, a);
+        DM_TRY(hipGetLastError());
+        DM_OK(s.download());
+        DM_TRY(hipStreamSynchronize(st));
+    }
+    *n_found = selected;
+    if (stats) {
+        S.n_stream_blocks = nb;
+        S.n_map_only_blocks = n_only;
+        S.n_missing_now = sum[kDiffCntMissing];
+        for (int k = 0; k < 25; ++k) S.pairs[k] = sum[k];
+        for (int k = 0; k < 5; ++k) S.value_changed[k] = sum[25 + k];
+        *stats = S;
     }
     return LA3DM_OK;
 }

@@ -13,6 +13,7 @@
 //   Occupancy                          src/bgkoctomap/bgkoctree_node.cpp:15-44
 #include "bgkoctomap.h"
 #include "region_contract.h"
+#include "diff_block.h"
 #include "merge_block.h"
 #include "region_blocks.h"
 #include "pack_format.h"
@@ -851,6 +852,108 @@ la3dm_merge_stats BGKOctoMap::merge_file(const std::string &path) {
     in.seekg(0);
     if (!bytes.empty() && !in.read((char *)bytes.data(), size)) throw std::runtime_error("BGKOctoMap::merge_file: cannot read " + path);
     return merge(bytes.data(), bytes.size());
+}
+
+// ---- diff (include/la3dm_hip.h, la3dm_devmap_diff_host; the rule per block: diff_block.h) ----
+void BGKOctoMap::diff(const void *stream, size_t size, const la3dm_diff_params &p, uint64_t cap, const la3dm_diff_out *out,
+                      uint64_t *n_found, la3dm_diff_stats *stats) const {
+    bind();
+    if (dmap != nullptr) {   // on the pool; the mirror is not touched
+        if (la3dm_devmap_diff_host(dmap, stream, size, &p, cap, out, n_found, stats) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::diff: ") + la3dm_last_error(ctx));
+        return;
+    }
+    la3dm_pack_header h;
+    const la3dm_pack_header my = la3dm_pack::make_header(stream_params(create_params, resolution, block_depth), mine.original_size, nullptr, 0, 0);
+    std::string bad = la3dm_pack::validate(stream, size, &h);
+    if (bad.empty()) bad = la3dm_pack::mismatch(h, my);
+    if (bad.empty() && n_found == nullptr) bad = "n_found is NULL";
+    if (bad.empty() && (p.pair_mask >> 25)) bad = "pair_mask has bits above bit 24 (25 pairs, bit 5 * then + now)";
+    if (bad.empty() && (p.value_mask >> 5)) bad = "value_mask has bits above bit 4 (5 classes)";
+    if (bad.empty() && cap > 0 && out == nullptr) bad = "out is NULL with cap > 0";
+    if (!bad.empty()) throw std::runtime_error("BGKOctoMap::diff: " + bad);
+    const la3dm_pack::Layout l = la3dm_pack::layout(h.n_blocks, h.n_leaves, h.nodes_per_block);
+    const uint8_t *bytes = (const uint8_t *)stream;
+    const uint32_t npb = h.nodes_per_block, fine = la3dm_diff::layer_base(h.block_depth - 1u);
+    const la3dm_diff::Rule rule = {h.block_depth, my.init_A, my.init_B, p.pair_mask, p.value_mask};
+    la3dm_diff::Counts cells;
+    la3dm_diff::List list;
+    list.cap = cap;
+    std::vector<int64_t> key_of;   // per listed entry
+    std::vector<float> A(npb), B(npb);
+    std::vector<uint8_t> S(npb);
+    la3dm_diff_stats st;
+    std::memset(&st, 0, sizeof(st));
+    const auto compare = [&](int64_t key, const la3dm_diff::StreamBlock *then, const Block *blk) {
+        la3dm_diff::MapBlock now = {S.data(), A.data(), B.data()};
+        if (blk != nullptr)
+            for (uint32_t n = 0; n < npb; ++n) {
+                A[n] = blk->slab[n].m_A;
+                B[n] = blk->slab[n].m_B;
+                S[n] = (uint8_t)((uint8_t)blk->slab[n].state | (blk->slab[n].classified ? 0x80u : 0u));
+            }
+        la3dm_diff::diff_block(rule, then, blk != nullptr ? &now : nullptr, cells, list);
+        key_of.resize(list.cell.size(), key);
+    };
+    std::vector<int64_t> named(h.n_blocks);
+    for (uint64_t b = 0; b < h.n_blocks; ++b) {
+        std::memcpy(&named[b], bytes + l.keys + 8 * b, 8);
+        const la3dm_diff::StreamBlock then = {bytes + l.mask + 4ull * b * l.W, la3dm_diff::word_at(bytes + l.leaf_off, b), bytes + l.state, bytes + l.A,
+                                              bytes + l.B};
+        const auto it = block_arr.find(named[b]);
+        st.n_missing_now += it == block_arr.end();
+        compare(named[b], &then, it == block_arr.end() ? nullptr : it->second);
+    }
+    if (p.map_only) {   // the map's other blocks, in the order pack() writes them
+        std::sort(named.begin(), named.end());
+        std::vector<int64_t> rest;
+        for (const auto &kv : block_arr)
+            if (!std::binary_search(named.begin(), named.end(), kv.first)) rest.push_back(kv.first);
+        std::sort(rest.begin(), rest.end());
+        for (const int64_t key : rest) compare(key, nullptr, block_arr.find(key)->second);
+        st.n_map_only_blocks = rest.size();
+    }
+    if (cells.selected > 0xFFFFFFFFull)
+        throw std::runtime_error("BGKOctoMap::diff: more than 2^32 - 1 cells are selected (" + std::to_string(cells.selected) + ")");
+    const size_t m = list.cell.size();
+    if (out != nullptr && m) {
+        if (out->block_key) std::memcpy(out->block_key, key_of.data(), 8 * m);
+        if (out->cell) std::memcpy(out->cell, list.cell.data(), 4 * m);
+        if (out->code) std::memcpy(out->code, list.code.data(), m);
+        if (out->A) std::memcpy(out->A, list.A.data(), 4 * m);
+        if (out->B) std::memcpy(out->B, list.B.data(), 4 * m);
+        if (out->centre)   // Block::get_loc of the finest node: the LUT entry + the block's centre
+            for (size_t t = 0; t < m; ++t) {
+                const point3f c = Block::key_loc_map[fine + list.cell[t]] + hash_key_to_block(key_of[t]);
+                out->centre[3 * t] = c.x();
+                out->centre[3 * t + 1] = c.y();
+                out->centre[3 * t + 2] = c.z();
+            }
+    }
+    *n_found = cells.selected;
+    if (stats != nullptr) {
+        st.n_stream_blocks = h.n_blocks;
+        std::memcpy(st.pairs, cells.pairs, sizeof(st.pairs));
+        std::memcpy(st.value_changed, cells.value_changed, sizeof(st.value_changed));
+        *stats = st;
+    }
+}
+
+void BGKOctoMap::diff(const BGKOctoMap &then, const la3dm_diff_params &p, uint64_t cap, const la3dm_diff_out *out, uint64_t *n_found,
+                      la3dm_diff_stats *stats) const {
+    const std::vector<uint8_t> bytes = then.pack();   // (binds the other map; diff() binds this one again)
+    diff(bytes.data(), bytes.size(), p, cap, out, n_found, stats);
+}
+
+void BGKOctoMap::diff_file(const std::string &path, const la3dm_diff_params &p, uint64_t cap, const la3dm_diff_out *out, uint64_t *n_found,
+                           la3dm_diff_stats *stats) const {
+    std::ifstream in(path, std::ios::binary | std::ios::ate);
+    if (!in) throw std::runtime_error("BGKOctoMap::diff_file: cannot open " + path);
+    const std::streamsize size = in.tellg();
+    std::vector<uint8_t> bytes((size_t)std::max<std::streamsize>(size, 0));
+    in.seekg(0);
+    if (!bytes.empty() && !in.read((char *)bytes.data(), size)) throw std::runtime_error("BGKOctoMap::diff_file: cannot read " + path);
+    diff(bytes.data(), bytes.size(), p, cap, out, n_found, stats);
 }
 
 // ---- pack_region / erase_region / evict (include/la3dm_hip.h, la3dm_devmap_pack_region_host; the region: region_blocks.h) ----

@@ -551,6 +551,19 @@ public:
     la3dm_merge_stats merge(const void *stream, size_t size);
     la3dm_merge_stats merge(const BGKOctoMap &other);
     la3dm_merge_stats merge_file(const std::string &path);
+    /// Diff (contract: include/la3dm_hip.h, la3dm_devmap_diff_host), all four classes: the finest cells whose class — or,
+    /// with p.value_mask, whose A or B — differs between this map (now) and a stream, or another map of the same class
+    /// packed first (then): the blocks the stream names in stream order, with p.map_only then the map's other blocks in
+    /// pack()'s order; the selected cells as a list (the first min(*n_found, cap) entries; cap 0 with out null only counts)
+    /// and the 5 x 5 pair counts in stats (may be null).  The map is not changed: a device-resident map compares on the GPU
+    /// pool (no mirror refresh, the mirror not marked stale), a host-mode map runs host/diff_block.h over its blocks — the
+    /// same list and counts.  A refusal throws std::runtime_error before anything is written.
+    void diff(const void *stream, size_t size, const la3dm_diff_params &p, uint64_t cap, const la3dm_diff_out *out, uint64_t *n_found,
+              la3dm_diff_stats *stats = nullptr) const;
+    void diff(const BGKOctoMap &then, const la3dm_diff_params &p, uint64_t cap, const la3dm_diff_out *out, uint64_t *n_found,
+              la3dm_diff_stats *stats = nullptr) const;
+    void diff_file(const std::string &path, const la3dm_diff_params &p, uint64_t cap, const la3dm_diff_out *out, uint64_t *n_found,
+                   la3dm_diff_stats *stats = nullptr) const;
     /// The map as a rolling window (contract: include/la3dm_hip.h, la3dm_devmap_pack_region_host), all four classes.  The
     /// region is the box of blocks from the block that holds lo3 to the block that holds hi3 (block_to_hash_key, on the
     /// host; a box whose first block lies past its second on an axis is refused); inside selects the blocks in the box, !inside every other block.  pack_region: the

@@ -502,6 +502,23 @@ int la3dm_map_merge_file(la3dm_map *m, const char *path, la3dm_merge_stats *stat
         return 0;)
 }
 
+int la3dm_map_diff(const la3dm_map *m, const void *buf, uint64_t size, const la3dm_diff_params *params, uint64_t cap,
+                   const la3dm_diff_out *out, uint64_t *n_found, la3dm_diff_stats *stats) {
+    GUARD(
+        if (params == nullptr) throw std::invalid_argument("BGKOctoMap::diff: params is NULL");
+        m->map->diff(buf, (size_t)size, *params, cap, out, n_found, stats);
+        return 0;)
+}
+
+int la3dm_map_diff_file(const la3dm_map *m, const char *path, const la3dm_diff_params *params, uint64_t cap, const la3dm_diff_out *out,
+                        uint64_t *n_found, la3dm_diff_stats *stats) {
+    GUARD(
+        if (path == nullptr) throw std::invalid_argument("BGKOctoMap::diff_file: path is NULL");
+        if (params == nullptr) throw std::invalid_argument("BGKOctoMap::diff_file: params is NULL");
+        m->map->diff_file(path, *params, cap, out, n_found, stats);
+        return 0;)
+}
+
 int la3dm_map_pack_region(const la3dm_map *m, const float *lo3, const float *hi3, int inside, void *buf, uint64_t cap, uint64_t *size) {
     GUARD(
         if (size == nullptr) throw std::invalid_argument("BGKOctoMap::pack_region: size is NULL");
