@@ -54,17 +54,21 @@ class BgkCounters(C.Structure):
     _fields_ = [("n_tiles", C.c_uint64), ("scratch_bytes", C.c_uint64)]
 
 
-class ScanStats(C.Structure):
-    _fields_ = [(n, C.c_uint64) for n in ("n_hits", "n_frees", "n_bbox_blocks", "n_train_blocks", "n_test_blocks",
-                                           "voxel_updates", "train_reads", "pair_evals", "n_tiles")] + \
-               [(n, C.c_double) for n in ("t_frontend", "t_partition", "t_pack", "t_device", "t_commit", "t_prune",
-                                          "t_total", "t_gather")]
+class _Stats(C.Structure):
+    """what the statistics structures share"""
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
-class DevmapStats(C.Structure):
+class ScanStats(_Stats):
+    _fields_ = [(n, C.c_uint64) for n in ("n_hits", "n_frees", "n_bbox_blocks", "n_train_blocks", "n_test_blocks",
+                                           "voxel_updates", "train_reads", "pair_evals", "n_tiles")] + \
+               [(n, C.c_double) for n in ("t_frontend", "t_partition", "t_pack", "t_device", "t_commit", "t_prune",
+                                          "t_total", "t_gather")]
+
+
+class DevmapStats(_Stats):
     """la3dm_devmap_stats (include/la3dm_hip.h)"""
     _fields_ = [(k, C.c_uint64) for k in ("n_hits", "n_frees", "n_train_blocks", "n_test_blocks", "n_bbox_blocks",
                                           "voxel_updates", "train_reads", "pair_evals", "n_blocks")] + \
@@ -114,7 +118,7 @@ class ReachOut(C.Structure):     # la3dm_reach_out
     _fields_ = [(k, C.c_void_p) for k in ("steps", "target_steps")]
 
 
-class ReachStats(C.Structure):   # la3dm_reach_stats
+class ReachStats(_Stats):   # la3dm_reach_stats
     _fields_ = [(k, C.c_uint32) for k in ("n_seeded", "n_reached", "levels")]
 
 
@@ -127,7 +131,7 @@ class TravelOut(C.Structure):    # la3dm_travel_out
     _fields_ = [(k, C.c_void_p) for k in ("cost", "target_cost", "parent")]
 
 
-class TravelStats(C.Structure):  # la3dm_travel_stats
+class TravelStats(_Stats):  # la3dm_travel_stats
     _fields_ = [(k, C.c_uint32) for k in ("n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")]
 
 
@@ -140,7 +144,7 @@ class ClustersOut(C.Structure):    # la3dm_clusters_out
     _fields_ = [(k, C.c_void_p) for k in ("label", "of_member", "first", "size", "lo", "hi", "sum", "rep")]
 
 
-class ClustersStats(C.Structure):  # la3dm_clusters_stats
+class ClustersStats(_Stats):  # la3dm_clusters_stats
     _fields_ = [(k, C.c_uint32) for k in ("n_members", "n_clusters", "n_dropped", "largest", "rounds", "brick_runs", "capped")]
 
 
@@ -148,7 +152,7 @@ class RegionInfo(C.Structure):   # la3dm_region_info
     _fields_ = [("block_key", C.c_int64), ("cell", C.c_int32 * 3), ("origin", C.c_float * 3)]
 
 
-class MergeStats(C.Structure):   # la3dm_merge_stats
+class MergeStats(_Stats):   # la3dm_merge_stats
     _fields_ = [(k, C.c_uint64) for k in ("n_blocks", "n_created", "cells_kept", "cells_copied", "cells_fused")]
 
 
@@ -160,12 +164,12 @@ class DiffOut(C.Structure):      # la3dm_diff_out
     _fields_ = [(k, C.c_void_p) for k in ("block_key", "cell", "code", "centre", "A", "B")]
 
 
-class DiffStats(C.Structure):    # la3dm_diff_stats
+class DiffStats(_Stats):    # la3dm_diff_stats
     _fields_ = [(k, C.c_uint64) for k in ("n_stream_blocks", "n_map_only_blocks", "n_missing_now")] + \
                [("pairs", C.c_uint64 * 25), ("value_changed", C.c_uint64 * 5)]
 
 
-class EraseStats(C.Structure):   # la3dm_erase_stats
+class EraseStats(_Stats):   # la3dm_erase_stats
     _fields_ = [(k, C.c_uint64) for k in ("n_removed", "n_moved", "n_blocks")]
 
 
@@ -178,45 +182,158 @@ class PackHeader(C.Structure):   # la3dm_pack_header: the first 128 bytes of a m
                [("reserved", C.c_uint8 * 8)]
 
 
-HIP_SYMBOLS = ["la3dm_device_count", "la3dm_version", "la3dm_create", "la3dm_destroy", "la3dm_last_error",
-               "la3dm_set_option", "la3dm_get_option", "la3dm_bgk_scan_host", "la3dm_bgk_scan_device", "la3dm_gp_scan_host",
-               "la3dm_gp_scan_device", "la3dm_bgklv_scan_host", "la3dm_bgklv_scan_device", "la3dm_kernel_times", "la3dm_diag_eval", "la3dm_diag_sweep",
-               "la3dm_devmap_create", "la3dm_devmap_destroy", "la3dm_devmap_insert_pointcloud_host",
-               "la3dm_devmap_insert_pointcloud_device", "la3dm_devmap_block_count", "la3dm_devmap_download",
-               "la3dm_devmap_training_data", "la3dm_devmap_diag_add_repeat", "la3dm_bgkl_scan_host",
-               "la3dm_bgkl_scan_device", "la3dm_diag_mfma_chain", "la3dm_devmap_search_host",
-               "la3dm_devmap_export_cells", "la3dm_devmap_key_bounds",
-               "la3dm_devmap_insert_training_data_host", "la3dm_devmap_set_shard", "la3dm_devmap_wait_event",
-               "la3dm_devmap_lv_stats_get", "la3dm_devmap_lv_set_original_size", "la3dm_devmap_lv_training",
-               "la3dm_devmap_diag_scan", "la3dm_devmap_diag_sort", "la3dm_devmap_raycast_host",
-               "la3dm_devmap_raycast_device", "la3dm_devmap_box_host", "la3dm_devmap_box_device",
-               "la3dm_devmap_columns_host", "la3dm_devmap_columns_device", "la3dm_devmap_distance_host",
-               "la3dm_devmap_distance_device", "la3dm_devmap_frontier_host", "la3dm_devmap_frontier_device",
-               "la3dm_devmap_gain_host", "la3dm_devmap_gain_device", "la3dm_devmap_score_poses_host",
-               "la3dm_devmap_score_poses_device", "la3dm_devmap_score_paths_host", "la3dm_devmap_score_paths_device",
-               "la3dm_devmap_reach_host",
-               "la3dm_devmap_reach_device", "la3dm_devmap_travel_host", "la3dm_devmap_travel_device",
-               "la3dm_devmap_clusters_host", "la3dm_devmap_clusters_device",
-               "la3dm_devmap_pack_host", "la3dm_devmap_unpack_host", "la3dm_pack_info", "la3dm_devmap_merge_host",
-               "la3dm_devmap_diff_host",
-               "la3dm_devmap_pack_region_host", "la3dm_devmap_erase_region_host"]
-MAP_SYMBOLS = ["la3dm_map_create", "la3dm_map_create_gp", "la3dm_map_create_lv", "la3dm_map_lv_training",
-               "la3dm_map_lv_stats", "la3dm_map_lv_prepare", "la3dm_map_lv_packed", "la3dm_map_lv_commit", "la3dm_map_destroy", "la3dm_map_last_error", "la3dm_map_insert_pointcloud", "la3dm_map_insert_pointcloud_device",
-               "la3dm_map_insert_training_data", "la3dm_map_prepare", "la3dm_map_prepare_training_data",
-               "la3dm_map_packed", "la3dm_map_commit", "la3dm_map_ctx", "la3dm_map_stats", "la3dm_map_training_size",
-               "la3dm_map_training_data", "la3dm_map_block_size", "la3dm_map_block_count", "la3dm_map_leaf_count",
-               "la3dm_map_dump_leaves", "la3dm_map_search", "la3dm_map_get_bbox", "la3dm_map_block_to_hash_key",
-               "la3dm_map_hash_key_to_block", "la3dm_map_extended_block", "la3dm_map_lut",
-               "la3dm_map_set_device_resident", "la3dm_map_is_device_resident", "la3dm_map_raycast",
-               "la3dm_map_block_grid", "la3dm_map_create_l", "la3dm_map_l_training",
-               "la3dm_map_search_many", "la3dm_map_export_cells", "la3dm_map_set_shard", "la3dm_map_resolution",
-               "la3dm_map_block_depth", "la3dm_map_set_resolution", "la3dm_map_set_block_depth",
-               "la3dm_map_raycast_many", "la3dm_map_mirror_syncs", "la3dm_map_box", "la3dm_map_columns",
-               "la3dm_map_distance_field", "la3dm_map_frontier", "la3dm_map_gain", "la3dm_map_score_poses", "la3dm_map_reach",
-               "la3dm_map_score_paths",
-               "la3dm_map_travel", "la3dm_map_clusters", "la3dm_map_pack", "la3dm_map_unpack", "la3dm_map_save",
-               "la3dm_map_load", "la3dm_map_merge", "la3dm_map_merge_file", "la3dm_map_diff", "la3dm_map_diff_file", "la3dm_map_pack_region",
-               "la3dm_map_erase_region", "la3dm_map_evict", "la3dm_map_evict_file"]
+# -- the signatures: one table per library, name -> (restype, argtypes), from include/la3dm_hip.h and include/la3dm_map.h --
+cint, u32, u64, i64, f32, vp, P = C.c_int, C.c_uint32, C.c_uint64, C.c_int64, C.c_float, C.c_void_p, C.POINTER
+f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
+_INFO = P(RegionInfo)
+
+# A query is served by la3dm_map_<view> and by la3dm_devmap_<stem>_host / _device, with one argument list after the handle:
+# stem -> (view, the device map's pointer forms, that list)
+QUERIES = {
+    "raycast": ("raycast_many", ("host", "device"), [vp, u32, u32, u32, P(RaycastOut)]),
+    "box": ("box", ("host", "device"), [vp, vp, P(BoxOut), _INFO]),
+    "columns": ("columns", ("host", "device"), [vp, vp, P(ColumnsOut), _INFO]),
+    "distance": ("distance_field", ("host", "device"), [vp, vp, u32, u32, P(DistanceOut), _INFO]),
+    "frontier": ("frontier", ("host", "device"), [vp, vp] + [u32] * 4 + [u64, P(FrontierOut), P(u64), _INFO]),
+    "gain": ("gain", ("host", "device"), [vp, vp, vp, u32, vp] + [u32] * 4 + [P(GainOut), _INFO]),
+    "score_poses": ("score_poses", ("host", "device"), [vp, vp, vp, u32, vp] + [u32] * 3 + [P(ScoreOut), _INFO]),
+    "score_paths": ("score_paths", ("host", "device"), [vp, vp, vp, u32, u32, P(PathsParams), P(PathsOut), _INFO]),
+    "reach": ("reach", ("host", "device"), [vp, vp, vp] + [u32] * 6 + [vp, u32, P(ReachOut), P(ReachStats), _INFO]),
+    "travel": ("travel", ("host", "device"), [vp, vp, vp, u32, P(TravelParams), vp, u32, P(TravelOut), P(TravelStats), _INFO]),
+    "clusters": ("clusters", ("host", "device"), [vp, vp, P(ClustersParams), P(ClustersOut), P(u32), P(ClustersStats), _INFO]),
+    "pack": ("pack", ("host",), [vp, u64, P(u64)]),
+    "unpack": ("unpack", ("host",), [vp, u64]),
+    "merge": ("merge", ("host",), [vp, u64, P(MergeStats)]),
+    "diff": ("diff", ("host",), [vp, u64, P(DiffParams), u64, P(DiffOut), P(u64), P(DiffStats)]),
+    "pack_region": ("pack_region", ("host",), [vp, vp, cint, vp, u64, P(u64)]),
+    "erase_region": ("erase_region", ("host",), [vp, vp, cint, P(EraseStats)]),
+}
+# ... except at these entries, which take something else after the handle
+QUERY_DIFFERS = {
+    "la3dm_map_raycast_many": [f32p, u64, u32, u32, P(RaycastOut)],   # the rays as a numpy array, their number in 64 bits
+    # the device map takes the box of block keys (int32 klo[3], khi[3]) that the map view derives from its two world points
+    "la3dm_devmap_pack_region_host": [P(C.c_int32), P(C.c_int32), cint, vp, u64, P(u64)],
+    "la3dm_devmap_erase_region_host": [P(C.c_int32), P(C.c_int32), cint, P(EraseStats)],
+}
+
+
+def _query_entries(of_map):
+    """the queries' entries of one library's table"""
+    out = {}
+    for stem, (view, forms, args) in QUERIES.items():
+        for n in [f"la3dm_map_{view}"] if of_map else [f"la3dm_devmap_{stem}_{f}" for f in forms]:
+            out[n] = (cint, [vp] + QUERY_DIFFERS.get(n, args))
+    return out
+
+
+HIP_API = {
+    "la3dm_device_count": (cint, []),
+    "la3dm_version": (C.c_char_p, []),
+    "la3dm_create": (cint, [P(Params), P(vp)]),
+    "la3dm_destroy": (None, [vp]),
+    "la3dm_last_error": (C.c_char_p, [vp]),
+    "la3dm_set_option": (cint, [vp, C.c_char_p, cint]),
+    "la3dm_get_option": (cint, [vp, C.c_char_p, P(cint)]),
+    **{f"la3dm_{kind}_scan_{form}": (cint, [vp, P(scan)] + stream + [P(BgkCounters)])
+       for kind, scan in (("bgk", BgkScan), ("bgkl", BgkScan), ("gp", BgkScan), ("bgklv", LvScan))
+       for form, stream in (("host", []), ("device", [vp]))},
+    "la3dm_kernel_times": (cint, [vp, vp, u32, P(u32)]),
+    "la3dm_diag_eval": (cint, [vp, cint, vp, u32, vp]),
+    "la3dm_diag_sweep": (cint, [vp, cint, u32, u32, P(u64)]),
+    "la3dm_diag_mfma_chain": (cint, [vp, vp, vp, cint, P(u32)]),
+    "la3dm_pack_info": (cint, [vp, u64, P(PackHeader)]),
+    "la3dm_devmap_create": (cint, [vp, P(vp)]),
+    "la3dm_devmap_destroy": (None, [vp]),
+    "la3dm_devmap_insert_pointcloud_host": (cint, [vp, vp, u32, u32, vp, f32, f32, f32, P(DevmapStats)]),
+    "la3dm_devmap_insert_pointcloud_device": (cint, [vp, vp, u32, vp, f32, f32, f32, P(DevmapStats)]),
+    "la3dm_devmap_insert_training_data_host": (cint, [vp, vp, u32, P(DevmapStats)]),
+    "la3dm_devmap_wait_event": (cint, [vp, vp]),
+    "la3dm_devmap_set_shard": (cint, [vp, u32, u32, ALLGATHER_FN, vp]),
+    "la3dm_devmap_lv_stats_get": (cint, [vp, vp]),   # (la3dm_devmap_lv_stats has no Structure here: nothing in Python reads it)
+    "la3dm_devmap_lv_set_original_size": (cint, [vp, cint]),
+    "la3dm_devmap_lv_training": (cint, [vp, vp, u32, vp, u32, P(u32), P(u32)]),
+    "la3dm_devmap_block_count": (cint, [vp, P(u32), P(u32)]),
+    "la3dm_devmap_download": (cint, [vp] * 5),
+    "la3dm_devmap_training_data": (cint, [vp, vp, u32, P(u32)]),
+    "la3dm_devmap_export_cells": (cint, [vp, cint, cint, f32, f32, vp, vp, vp, u64, P(u64)]),
+    "la3dm_devmap_key_bounds": (cint, [vp, P(C.c_int32), P(C.c_int32)]),
+    "la3dm_devmap_search_host": (cint, [vp, vp, u32] + [vp] * 4),
+    "la3dm_devmap_diag_add_repeat": (cint, [vp] * 4 + [u32] + [vp] * 2),
+    "la3dm_devmap_diag_scan": (cint, [vp, cint, vp, u32, vp, vp]),
+    "la3dm_devmap_diag_sort": (cint, [vp, vp, vp, u32, cint, vp, vp]),
+    **_query_entries(of_map=False),
+}
+
+_CREATE = [f32, cint] + [f32] * 7 + [cint]       # resolution, block_depth, seven parameters, device
+_CLOUD = [vp, f32p, u64, f32p, f32, f32, f32]    # xyz, n, origin, ds_resolution, free_res, max_range
+MAP_API = {
+    "la3dm_map_create": (vp, _CREATE),
+    "la3dm_map_create_l": (vp, _CREATE),
+    "la3dm_map_create_gp": (vp, [f32, cint] + [f32] * 9 + [cint]),
+    "la3dm_map_create_lv": (vp, [f32, cint] + [f32] * 7 + [cint, f32, cint]),
+    "la3dm_map_destroy": (None, [vp]),
+    "la3dm_map_last_error": (C.c_char_p, []),
+    "la3dm_map_l_training": (u64, [vp, vp, u64, vp, u64, P(u64)]),
+    "la3dm_map_lv_training": (u64, [vp, vp, u64, vp, u64, P(u64)]),
+    "la3dm_map_lv_stats": (cint, [vp, np.ctypeslib.ndpointer(np.float64)]),
+    "la3dm_map_lv_prepare": (cint, _CLOUD),
+    "la3dm_map_lv_packed": (cint, [vp, P(LvScan)]),
+    "la3dm_map_lv_commit": (cint, [vp]),
+    "la3dm_map_insert_pointcloud": (cint, _CLOUD),
+    "la3dm_map_insert_pointcloud_device": (cint, [vp, vp, u64, f32p, f32, f32, f32]),
+    "la3dm_map_insert_training_data": (cint, [vp, f32p, u64]),
+    "la3dm_map_prepare": (cint, _CLOUD),
+    "la3dm_map_prepare_training_data": (cint, [vp, f32p, u64, cint]),
+    "la3dm_map_packed": (cint, [vp, P(BgkScan)]),
+    "la3dm_map_commit": (cint, [vp]),
+    "la3dm_map_ctx": (vp, [vp]),
+    "la3dm_map_set_device_resident": (cint, [vp, cint]),
+    "la3dm_map_is_device_resident": (cint, [vp]),
+    "la3dm_map_set_shard": (cint, [vp, u32, u32, ALLGATHER_FN, vp]),
+    "la3dm_map_mirror_syncs": (u64, [vp]),
+    "la3dm_map_stats": (cint, [vp, P(ScanStats)]),
+    "la3dm_map_training_size": (u64, [vp]),
+    "la3dm_map_training_data": (cint, [vp, f32p, u64]),
+    "la3dm_map_block_size": (f32, [vp]),
+    "la3dm_map_resolution": (f32, [vp]),
+    "la3dm_map_block_depth": (cint, [vp]),
+    "la3dm_map_set_resolution": (cint, [vp, f32]),
+    "la3dm_map_set_block_depth": (cint, [vp, cint]),
+    "la3dm_map_block_count": (u64, [vp]),
+    "la3dm_map_leaf_count": (u64, [vp]),
+    "la3dm_map_dump_leaves": (u64, [vp] * 9 + [u64]),
+    "la3dm_map_search": (cint, [vp, f32, f32, f32, P(f32), P(f32), P(C.c_uint8)]),
+    "la3dm_map_search_many": (cint, [vp, f32p, u64] + [vp] * 4),
+    "la3dm_map_raycast": (u64, [vp, f32p, f32p] + [vp] * 7 + [u64]),
+    "la3dm_map_export_cells": (cint, [vp, cint, cint, f32, f32, vp, vp, vp, u64, P(u64)]),
+    "la3dm_map_get_bbox": (cint, [vp, f32p, f32p]),
+    "la3dm_map_block_grid": (None, [vp, f32p, f32p, np.ctypeslib.ndpointer(np.int32), P(C.c_int32), f32p]),
+    "la3dm_map_block_to_hash_key": (i64, [vp, f32, f32, f32]),
+    "la3dm_map_hash_key_to_block": (None, [vp, i64, f32p]),
+    "la3dm_map_extended_block": (None, [vp, i64, np.ctypeslib.ndpointer(np.int64)]),
+    "la3dm_map_lut": (u32, [vp, vp, u32]),
+    "la3dm_map_save": (cint, [vp, C.c_char_p]),
+    "la3dm_map_load": (cint, [vp, C.c_char_p]),
+    # the file forms have no device-map counterpart: a path where the stream (or, for evict_file, the buffer) stands
+    "la3dm_map_merge_file": (cint, [vp, C.c_char_p, P(MergeStats)]),
+    "la3dm_map_diff_file": (cint, [vp, C.c_char_p] + QUERIES["diff"][2][2:]),
+    "la3dm_map_evict": (cint, [vp] + QUERIES["pack_region"][2] + [P(EraseStats)]),
+    "la3dm_map_evict_file": (cint, [vp, C.c_char_p, vp, vp, cint, P(EraseStats)]),
+    **_query_entries(of_map=True),
+}
+HIP_SYMBOLS = list(HIP_API)
+MAP_SYMBOLS = list(MAP_API)
+
+
+def _load(path, table, **kw):
+    """the library at `path` with the restype and argtypes of every entry of `table` set"""
+    L = C.CDLL(path, **kw)
+    for name, (restype, argtypes) in table.items():
+        f = getattr(L, name)
+        f.restype = restype
+        f.argtypes = argtypes
+    return L
+
 
 _hip = None
 _map = None
@@ -229,130 +346,7 @@ def hip():
         if not os.path.exists(HIP_SO):
             raise OSError(f"{HIP_SO} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(there is no fallback path)")
-        L = C.CDLL(HIP_SO, mode=C.RTLD_GLOBAL)
-        L.la3dm_device_count.restype = C.c_int
-        L.la3dm_version.restype = C.c_char_p
-        L.la3dm_create.restype = C.c_int
-        L.la3dm_create.argtypes = [C.POINTER(Params), C.POINTER(C.c_void_p)]
-        L.la3dm_destroy.argtypes = [C.c_void_p]
-        L.la3dm_last_error.restype = C.c_char_p
-        L.la3dm_last_error.argtypes = [C.c_void_p]
-        L.la3dm_set_option.restype = C.c_int
-        L.la3dm_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-        L.la3dm_get_option.restype = C.c_int
-        L.la3dm_get_option.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int)]
-        L.la3dm_bgk_scan_host.restype = C.c_int
-        L.la3dm_bgk_scan_host.argtypes = [C.c_void_p, C.POINTER(BgkScan), C.POINTER(BgkCounters)]
-        L.la3dm_bgk_scan_device.restype = C.c_int
-        L.la3dm_bgk_scan_device.argtypes = [C.c_void_p, C.POINTER(BgkScan), C.c_void_p, C.POINTER(BgkCounters)]
-        L.la3dm_diag_mfma_chain.restype = C.c_int
-        L.la3dm_diag_mfma_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint32)]
-        L.la3dm_bgkl_scan_host.restype = C.c_int
-        L.la3dm_bgkl_scan_host.argtypes = [C.c_void_p, C.POINTER(BgkScan), C.POINTER(BgkCounters)]
-        L.la3dm_bgkl_scan_device.restype = C.c_int
-        L.la3dm_bgkl_scan_device.argtypes = [C.c_void_p, C.POINTER(BgkScan), C.c_void_p, C.POINTER(BgkCounters)]
-        L.la3dm_gp_scan_host.restype = C.c_int
-        L.la3dm_gp_scan_host.argtypes = [C.c_void_p, C.POINTER(BgkScan), C.POINTER(BgkCounters)]
-        L.la3dm_gp_scan_device.restype = C.c_int
-        L.la3dm_gp_scan_device.argtypes = [C.c_void_p, C.POINTER(BgkScan), C.c_void_p, C.POINTER(BgkCounters)]
-        L.la3dm_bgklv_scan_host.restype = C.c_int
-        L.la3dm_bgklv_scan_host.argtypes = [C.c_void_p, C.POINTER(LvScan), C.POINTER(BgkCounters)]
-        L.la3dm_bgklv_scan_device.restype = C.c_int
-        L.la3dm_bgklv_scan_device.argtypes = [C.c_void_p, C.POINTER(LvScan), C.c_void_p, C.POINTER(BgkCounters)]
-        L.la3dm_kernel_times.restype = C.c_int
-        L.la3dm_kernel_times.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-        L.la3dm_diag_sweep.restype = C.c_int
-        L.la3dm_diag_sweep.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]
-        L.la3dm_diag_eval.restype = C.c_int
-        L.la3dm_diag_eval.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p]
-        L.la3dm_devmap_create.restype = C.c_int
-        L.la3dm_devmap_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-        L.la3dm_devmap_destroy.argtypes = [C.c_void_p]
-        L.la3dm_devmap_insert_pointcloud_host.restype = C.c_int
-        L.la3dm_devmap_insert_pointcloud_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                          C.c_float, C.c_float, C.c_float, C.POINTER(DevmapStats)]
-        L.la3dm_devmap_insert_pointcloud_device.restype = C.c_int
-        L.la3dm_devmap_insert_pointcloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float,
-                                                            C.c_float, C.c_float, C.POINTER(DevmapStats)]
-        L.la3dm_devmap_block_count.restype = C.c_int
-        L.la3dm_devmap_block_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
-        L.la3dm_devmap_download.restype = C.c_int
-        L.la3dm_devmap_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.la3dm_devmap_diag_add_repeat.restype = C.c_int
-        L.la3dm_devmap_diag_scan.restype = C.c_int
-        L.la3dm_devmap_diag_scan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.la3dm_devmap_diag_sort.restype = C.c_int
-        L.la3dm_devmap_diag_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
-        L.la3dm_devmap_diag_add_repeat.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 2
-        L.la3dm_devmap_search_host.restype = C.c_int
-        L.la3dm_devmap_search_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 4
-        L.la3dm_devmap_raycast_host.restype = C.c_int
-        L.la3dm_devmap_raycast_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
-        L.la3dm_devmap_raycast_device.restype = C.c_int
-        L.la3dm_devmap_raycast_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
-        for name, out in (("box", BoxOut), ("columns", ColumnsOut)):
-            for form in ("host", "device"):
-                f = getattr(L, f"la3dm_devmap_{name}_{form}")
-                f.restype = C.c_int
-                f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(out), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_distance_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DistanceOut), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_frontier_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_uint64, C.POINTER(FrontierOut),
-                                                                                   C.POINTER(C.c_uint64), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_gain_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 4 + \
-                         [C.POINTER(GainOut), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_score_poses_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 3 + \
-                         [C.POINTER(ScoreOut), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_score_paths_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PathsParams),
-                          C.POINTER(PathsOut), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_reach_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + \
-                         [C.c_void_p, C.c_uint32, C.POINTER(ReachOut), C.POINTER(ReachStats), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_travel_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TravelParams), C.c_void_p, C.c_uint32,
-                          C.POINTER(TravelOut), C.POINTER(TravelStats), C.POINTER(RegionInfo)]
-        for form in ("host", "device"):
-            f = getattr(L, f"la3dm_devmap_clusters_{form}")
-            f.restype = C.c_int
-            f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClustersParams), C.POINTER(ClustersOut), C.POINTER(C.c_uint32),
-                          C.POINTER(ClustersStats), C.POINTER(RegionInfo)]
-        L.la3dm_devmap_pack_host.restype = C.c_int
-        L.la3dm_devmap_pack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        L.la3dm_devmap_unpack_host.restype = C.c_int
-        L.la3dm_devmap_unpack_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-        L.la3dm_devmap_merge_host.restype = C.c_int
-        L.la3dm_devmap_merge_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MergeStats)]
-        L.la3dm_devmap_diff_host.restype = C.c_int
-        L.la3dm_devmap_diff_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DiffParams), C.c_uint64, C.POINTER(DiffOut),
-                                             C.POINTER(C.c_uint64), C.POINTER(DiffStats)]
-        L.la3dm_devmap_pack_region_host.restype = C.c_int
-        L.la3dm_devmap_pack_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_uint64,
-                                                    C.POINTER(C.c_uint64)]
-        L.la3dm_devmap_erase_region_host.restype = C.c_int
-        L.la3dm_devmap_erase_region_host.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(EraseStats)]
-        L.la3dm_pack_info.restype = C.c_int
-        L.la3dm_pack_info.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(PackHeader)]
-        L.la3dm_devmap_training_data.restype = C.c_int
-        L.la3dm_devmap_training_data.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-        _hip = L
+        _hip = _load(HIP_SO, HIP_API, mode=C.RTLD_GLOBAL)
     return _hip
 
 
@@ -362,143 +356,5 @@ def maplib():
         hip()
         if not os.path.exists(MAP_SO):
             raise OSError(f"{MAP_SO} is missing: build it first (no fallback path)")
-        M = C.CDLL(MAP_SO)
-        f32p = np.ctypeslib.ndpointer(np.float32, flags="C_CONTIGUOUS")
-        M.la3dm_map_create.restype = C.c_void_p
-        M.la3dm_map_create.argtypes = [C.c_float, C.c_int] + [C.c_float] * 7 + [C.c_int]
-        M.la3dm_map_create_l.restype = C.c_void_p
-        M.la3dm_map_create_l.argtypes = [C.c_float, C.c_int] + [C.c_float] * 7 + [C.c_int]
-        M.la3dm_map_l_training.restype = C.c_uint64
-        M.la3dm_map_l_training.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        M.la3dm_map_create_gp.restype = C.c_void_p
-        M.la3dm_map_create_gp.argtypes = [C.c_float, C.c_int] + [C.c_float] * 9 + [C.c_int]
-        M.la3dm_map_create_lv.restype = C.c_void_p
-        M.la3dm_map_create_lv.argtypes = [C.c_float, C.c_int] + [C.c_float] * 7 + [C.c_int, C.c_float, C.c_int]
-        M.la3dm_map_lv_training.restype = C.c_uint64
-        M.la3dm_map_lv_training.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        M.la3dm_map_lv_stats.argtypes = [C.c_void_p, np.ctypeslib.ndpointer(np.float64)]
-        M.la3dm_map_lv_prepare.restype = C.c_int
-        M.la3dm_map_lv_prepare.argtypes = [C.c_void_p, f32p, C.c_uint64, f32p, C.c_float, C.c_float, C.c_float]
-        M.la3dm_map_lv_packed.restype = C.c_int
-        M.la3dm_map_lv_packed.argtypes = [C.c_void_p, C.POINTER(LvScan)]
-        M.la3dm_map_lv_commit.restype = C.c_int
-        M.la3dm_map_lv_commit.argtypes = [C.c_void_p]
-        M.la3dm_map_destroy.argtypes = [C.c_void_p]
-        M.la3dm_map_block_grid.argtypes = [C.c_void_p, f32p, f32p, np.ctypeslib.ndpointer(np.int32), C.POINTER(C.c_int32), f32p]
-        M.la3dm_map_search_many.restype = C.c_int
-        M.la3dm_map_search_many.argtypes = [C.c_void_p, f32p, C.c_uint64] + [C.c_void_p] * 4
-        M.la3dm_map_export_cells.restype = C.c_int
-        M.la3dm_map_export_cells.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        M.la3dm_map_raycast_many.restype = C.c_int
-        M.la3dm_map_raycast_many.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RaycastOut)]
-        M.la3dm_map_box.restype = C.c_int
-        M.la3dm_map_box.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(BoxOut), C.POINTER(RegionInfo)]
-        M.la3dm_map_columns.restype = C.c_int
-        M.la3dm_map_columns.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ColumnsOut), C.POINTER(RegionInfo)]
-        M.la3dm_map_distance_field.restype = C.c_int
-        M.la3dm_map_distance_field.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DistanceOut),
-                                               C.POINTER(RegionInfo)]
-        M.la3dm_map_frontier.restype = C.c_int
-        M.la3dm_map_frontier.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_uint64, C.POINTER(FrontierOut),
-                                                                                                  C.POINTER(C.c_uint64), C.POINTER(RegionInfo)]
-        M.la3dm_map_gain.restype = C.c_int
-        M.la3dm_map_gain.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 4 + \
-                                    [C.POINTER(GainOut), C.POINTER(RegionInfo)]
-        M.la3dm_map_score_poses.restype = C.c_int
-        M.la3dm_map_score_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p] + [C.c_uint32] * 3 + \
-                                           [C.POINTER(ScoreOut), C.POINTER(RegionInfo)]
-        M.la3dm_map_score_paths.restype = C.c_int
-        M.la3dm_map_score_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PathsParams),
-                                           C.POINTER(PathsOut), C.POINTER(RegionInfo)]
-        M.la3dm_map_reach.restype = C.c_int
-        M.la3dm_map_reach.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_uint32] * 6 + \
-                                     [C.c_void_p, C.c_uint32, C.POINTER(ReachOut), C.POINTER(ReachStats), C.POINTER(RegionInfo)]
-        M.la3dm_map_travel.restype = C.c_int
-        M.la3dm_map_travel.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(TravelParams), C.c_void_p,
-                                       C.c_uint32, C.POINTER(TravelOut), C.POINTER(TravelStats), C.POINTER(RegionInfo)]
-        M.la3dm_map_clusters.restype = C.c_int
-        M.la3dm_map_clusters.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ClustersParams), C.POINTER(ClustersOut),
-                                         C.POINTER(C.c_uint32), C.POINTER(ClustersStats), C.POINTER(RegionInfo)]
-        M.la3dm_map_pack.restype = C.c_int
-        M.la3dm_map_pack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        M.la3dm_map_unpack.restype = C.c_int
-        M.la3dm_map_unpack.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-        M.la3dm_map_save.restype = C.c_int
-        M.la3dm_map_save.argtypes = [C.c_void_p, C.c_char_p]
-        M.la3dm_map_load.restype = C.c_int
-        M.la3dm_map_load.argtypes = [C.c_void_p, C.c_char_p]
-        M.la3dm_map_merge.restype = C.c_int
-        M.la3dm_map_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(MergeStats)]
-        M.la3dm_map_merge_file.restype = C.c_int
-        M.la3dm_map_merge_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(MergeStats)]
-        M.la3dm_map_diff.restype = C.c_int
-        M.la3dm_map_diff.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(DiffParams), C.c_uint64, C.POINTER(DiffOut),
-                                     C.POINTER(C.c_uint64), C.POINTER(DiffStats)]
-        M.la3dm_map_diff_file.restype = C.c_int
-        M.la3dm_map_diff_file.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(DiffParams), C.c_uint64, C.POINTER(DiffOut),
-                                          C.POINTER(C.c_uint64), C.POINTER(DiffStats)]
-        M.la3dm_map_pack_region.restype = C.c_int
-        M.la3dm_map_pack_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
-        M.la3dm_map_erase_region.restype = C.c_int
-        M.la3dm_map_erase_region.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EraseStats)]
-        M.la3dm_map_evict.restype = C.c_int
-        M.la3dm_map_evict.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(EraseStats)]
-        M.la3dm_map_evict_file.restype = C.c_int
-        M.la3dm_map_evict_file.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(EraseStats)]
-        M.la3dm_map_mirror_syncs.restype = C.c_uint64
-        M.la3dm_map_mirror_syncs.argtypes = [C.c_void_p]
-        M.la3dm_map_raycast.restype = C.c_uint64
-        M.la3dm_map_raycast.argtypes = [C.c_void_p, f32p, f32p] + [C.c_void_p] * 7 + [C.c_uint64]
-        M.la3dm_map_set_shard.restype = C.c_int
-        M.la3dm_map_set_shard.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, ALLGATHER_FN, C.c_void_p]
-        M.la3dm_map_set_device_resident.restype = C.c_int
-        M.la3dm_map_set_device_resident.argtypes = [C.c_void_p, C.c_int]
-        M.la3dm_map_is_device_resident.restype = C.c_int
-        M.la3dm_map_is_device_resident.argtypes = [C.c_void_p]
-        M.la3dm_map_last_error.restype = C.c_char_p
-        M.la3dm_map_insert_pointcloud_device.restype = C.c_int
-        M.la3dm_map_insert_pointcloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_float, C.c_float, C.c_float]
-        M.la3dm_map_insert_pointcloud.restype = C.c_int
-        M.la3dm_map_insert_pointcloud.argtypes = [C.c_void_p, f32p, C.c_uint64, f32p, C.c_float, C.c_float, C.c_float]
-        M.la3dm_map_insert_training_data.restype = C.c_int
-        M.la3dm_map_insert_training_data.argtypes = [C.c_void_p, f32p, C.c_uint64]
-        M.la3dm_map_prepare.restype = C.c_int
-        M.la3dm_map_prepare.argtypes = [C.c_void_p, f32p, C.c_uint64, f32p, C.c_float, C.c_float, C.c_float]
-        M.la3dm_map_prepare_training_data.restype = C.c_int
-        M.la3dm_map_prepare_training_data.argtypes = [C.c_void_p, f32p, C.c_uint64, C.c_int]
-        M.la3dm_map_packed.restype = C.c_int
-        M.la3dm_map_packed.argtypes = [C.c_void_p, C.POINTER(BgkScan)]
-        M.la3dm_map_commit.restype = C.c_int
-        M.la3dm_map_commit.argtypes = [C.c_void_p]
-        M.la3dm_map_ctx.restype = C.c_void_p
-        M.la3dm_map_ctx.argtypes = [C.c_void_p]
-        M.la3dm_map_stats.argtypes = [C.c_void_p, C.POINTER(ScanStats)]
-        M.la3dm_map_training_size.restype = C.c_uint64
-        M.la3dm_map_training_size.argtypes = [C.c_void_p]
-        M.la3dm_map_training_data.argtypes = [C.c_void_p, f32p, C.c_uint64]
-        M.la3dm_map_block_size.restype = C.c_float
-        M.la3dm_map_block_size.argtypes = [C.c_void_p]
-        M.la3dm_map_resolution.restype = C.c_float
-        M.la3dm_map_resolution.argtypes = [C.c_void_p]
-        M.la3dm_map_block_depth.argtypes = [C.c_void_p]
-        M.la3dm_map_set_resolution.argtypes = [C.c_void_p, C.c_float]
-        M.la3dm_map_set_block_depth.argtypes = [C.c_void_p, C.c_int]
-        M.la3dm_map_block_count.restype = C.c_uint64
-        M.la3dm_map_block_count.argtypes = [C.c_void_p]
-        M.la3dm_map_leaf_count.restype = C.c_uint64
-        M.la3dm_map_leaf_count.argtypes = [C.c_void_p]
-        M.la3dm_map_dump_leaves.restype = C.c_uint64
-        M.la3dm_map_dump_leaves.argtypes = [C.c_void_p] + [C.c_void_p] * 8 + [C.c_uint64]
-        M.la3dm_map_search.restype = C.c_int
-        M.la3dm_map_search.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float),
-                                       C.POINTER(C.c_float), C.POINTER(C.c_uint8)]
-        M.la3dm_map_get_bbox.argtypes = [C.c_void_p, f32p, f32p]
-        M.la3dm_map_block_to_hash_key.restype = C.c_int64
-        M.la3dm_map_block_to_hash_key.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
-        M.la3dm_map_hash_key_to_block.argtypes = [C.c_void_p, C.c_int64, f32p]
-        M.la3dm_map_extended_block.argtypes = [C.c_void_p, C.c_int64, np.ctypeslib.ndpointer(np.int64)]
-        M.la3dm_map_lut.restype = C.c_uint32
-        M.la3dm_map_lut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-        _map = M
+        _map = _load(MAP_SO, MAP_API)
     return _map

@@ -39,6 +39,74 @@ CLUSTERS_BRICK, CLUSTERS_INNER, CLUSTERS_BATCH = 8, 16, 8   # LA3DM_CLUSTERS_*: 
 _RAY_CLASS = dict(free=FREE, occupied=OCCUPIED, unknown=UNKNOWN, missing=MISSING, uncertain=4)
 
 
+# -- the decisions the query methods share ---------------------------------------
+def _class_mask(x):
+    """a class name, an iterable of class names or an integer -> the bit mask (an unknown name: KeyError)"""
+    if isinstance(x, (int, np.integer)):
+        return int(x)
+    return sum(1 << _RAY_CLASS[k] for k in ({x} if isinstance(x, str) else set(x)))
+
+
+def _pair_mask(pairs):
+    """diff's `pairs` -> the mask of (then, now) pairs, bit 5 * then + now"""
+    if isinstance(pairs, str):
+        if pairs != "changed":
+            raise ValueError('diff: pairs is "changed", an integer mask or an iterable of (then, now) class names')
+        return DIFF_PAIRS_CHANGED
+    if isinstance(pairs, (int, np.integer)):
+        return int(pairs)
+    mask = 0
+    for then, now in pairs:
+        mask |= 1 << (5 * _RAY_CLASS[then] + _RAY_CLASS[now])
+    return mask
+
+
+def _want(who, fields, allowed):
+    """`fields` (one name or several) as a tuple, every name out of `allowed`"""
+    if isinstance(fields, str):
+        fields = (fields,)
+    bad = set(fields) - set(allowed)
+    if bad:
+        raise ValueError(f"{who}: unknown fields {sorted(bad)}")
+    return tuple(fields)
+
+
+def _fit(msg, values, bits=32):
+    """ValueError(msg) unless every value fits an unsigned integer of `bits` bits"""
+    for v in values:
+        if not 0 <= int(v) < 1 << bits:
+            raise ValueError(msg)
+
+
+def _addr(a):
+    """the address of an array for a C call; NULL for None and for an empty array"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _out(X, arrays, null_empty=()):
+    """the out struct X with the address of arrays[k] in field k: NULL where the key is missing, and for the keys in
+    `null_empty` also where the array is empty (elsewhere an empty array goes by its address: the C calls refuse a NULL
+    mandatory output, e.g. raycast_many's steps or gain's gain, whatever the count)"""
+    ptrs = []
+    for k, _ in X._fields_:
+        a = arrays.get(k)
+        ptrs.append(None if a is None or (not a.size and k in null_empty) else a.ctypes.data)
+    return X(*ptrs)
+
+
+def _stream(stream):
+    """a map stream (bytes or a uint8 array) as a flat uint8 array"""
+    return np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
+                                np.uint8).reshape(-1)
+
+
+def _indices(seeds, targets):
+    """reach's and travel's flat index lists: seeds, targets (or None), the number of targets"""
+    s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+    t = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
+    return s, t, 0 if t is None else t.size
+
+
 class PackedScan:
     """Host view of one prepared scan (numpy arrays aliasing the map's buffers)."""
 
@@ -220,31 +288,31 @@ class BGKOctoMap:
         e = np.ascontiguousarray(ends, np.float32).reshape(-1, 3)
         if s.shape != e.shape:
             raise ValueError("raycast_many: starts and ends differ in shape")
-        if isinstance(stop, str):
-            stop = (stop,)
-        mask = int(stop) if isinstance(stop, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(stop))
+        mask = _class_mask(stop)
         n = s.shape[0]
         rays = np.ascontiguousarray(np.hstack([s, e]))
         out = dict(steps=np.zeros(n, np.uint32), flags=np.zeros(n, np.uint8), p=np.zeros((n, 3), np.float32),
                    block_key=np.zeros(n, np.int64), node_key=np.zeros(n, np.int32), cls=np.zeros(n, np.uint8),
                    leaf_depth=np.zeros(n, np.uint8), A=np.zeros(n, np.float32), B=np.zeros(n, np.float32),
                    counts=np.zeros((n, 4), np.uint32))
-        o = _lib.RaycastOut(*[out[k].ctypes.data for k, _ in _lib.RaycastOut._fields_])
-        self._chk(self._M.la3dm_map_raycast_many(self._h, rays, n, mask, int(max_steps), C.byref(o)))
+        self._chk(self._M.la3dm_map_raycast_many(self._h, rays, n, mask, int(max_steps), C.byref(_out(_lib.RaycastOut, out))))
         return out
 
     @staticmethod
-    def _region(lo, dims, limit):
-        """(lo, dims as C arrays, dims, cells to allocate): a request over `limit` cells (or with a zero dimension) gets
-        one-element arrays — the call refuses it before it looks at a buffer, and its text is the one that is raised"""
+    def _region(lo, dims, served):
+        """(lo and dims as C arrays, dims, their product, whether the C call is expected to serve the request: served(dims)
+        and no zero dimension).  A request that is not served still goes to the C call, with one-element output arrays —
+        the call refuses it before it looks at a buffer, and its text is the one that is raised"""
         lo3 = np.ascontiguousarray(lo, np.float32).reshape(-1)
         d = [int(v) for v in np.asarray(dims).reshape(-1)]
         if lo3.shape != (3,) or len(d) != 3 or min(d) < 0 or max(d) >= 2 ** 32:
             raise ValueError("lo must be 3 floats and dims 3 integers in [0, 2^32)")
-        return lo3, np.array(d, np.uint32), d, limit(d)
+        return lo3, np.array(d, np.uint32), d, d[0] * d[1] * d[2], bool(min(d) > 0 and served(d))
 
-    @staticmethod
-    def _region_info(info):
+    def _region_call(self, fn, lo3, d3, *args):
+        """fn(handle, lo, dims, *args, info), checked -> origin, block_key and cell of voxel (0, 0, 0)"""
+        info = _lib.RegionInfo()
+        self._chk(fn(self._h, lo3.ctypes.data, d3.ctypes.data, *args, C.byref(info)))
         return dict(origin=np.array(info.origin[:], np.float32), block_key=int(info.block_key),
                     cell=np.array(info.cell[:], np.int32))
 
@@ -259,17 +327,12 @@ class BGKOctoMap:
         voxel (0, 0, 0) (the others: origin + (i, j, k) * resolution), block_key and cell of that voxel.  At most 2^30
         voxels.  A device-resident map runs one HIP launch on the device pool (no host mirror refresh); a host-mode map
         loops over its host blocks, with bit-identical results."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 2 ** 30 else 1)(d[0] * d[1] * d[2]))
-        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
-        unknown = set(fields) - {"cls", "leaf_depth", "A", "B"}
-        if unknown:
-            raise ValueError(f"box: unknown fields {sorted(unknown)}")
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= 2 ** 30)
+        shape = tuple(d) if ok else (1,)
+        fields = _want("box", fields, ("cls", "leaf_depth", "A", "B"))
         out = {k: np.empty(shape, np.float32 if k in "AB" else np.uint8) for k in ("cls", "leaf_depth", "A", "B")
                if k == "cls" or k in fields}
-        o = _lib.BoxOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.BoxOut._fields_])
-        info = _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_box(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(o), C.byref(info)))
-        out.update(self._region_info(info))
+        out.update(self._region_call(self._M.la3dm_map_box, lo3, d3, C.byref(_out(_lib.BoxOut, out))))
         return out
 
     def columns(self, lo, dims):
@@ -277,13 +340,10 @@ class BGKOctoMap:
         class FREE, OCCUPIED, UNKNOWN (with UNCERTAIN), MISSING over k = 0 .. nz - 1 (they sum to nz), low_occ / top_occ
         (nx, ny) = the smallest / largest k whose class is OCCUPIED, -1 when there is none; plus origin, block_key, cell
         as box() returns them.  The 2-D occupancy grid / height map of a height band.  At most 2^30 columns, nz <= 2^16."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 2 ** 30 and d[2] <= 2 ** 16 else 1)(d[0] * d[1]))
-        shape = (d[0], d[1]) if n == d[0] * d[1] else (n,)
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] <= 2 ** 30 and d[2] <= 2 ** 16)
+        shape = (d[0], d[1]) if ok else (1,)
         out = dict(counts=np.empty(shape + (4,), np.uint32), low_occ=np.empty(shape, np.int32), top_occ=np.empty(shape, np.int32))
-        o = _lib.ColumnsOut(*[out[k].ctypes.data for k, _ in _lib.ColumnsOut._fields_])
-        info = _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_columns(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(o), C.byref(info)))
-        out.update(self._region_info(info))
+        out.update(self._region_call(self._M.la3dm_map_columns, lo3, d3, C.byref(_out(_lib.ColumnsOut, out))))
         return out
 
     def distance_field(self, lo, dims, obstacles=("occupied",), radius=32, fields=("d2", "dist")):
@@ -297,24 +357,13 @@ class BGKOctoMap:
         `fields` names the arrays wanted (at least one).  Also returned: origin, block_key, cell as box() returns them.
         At most 2^28 voxels.  A device-resident map runs the transform on the device pool (no host mirror refresh); a
         host-mode map runs it on the CPU, with bit-identical results."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 2 ** 28 else 1)(d[0] * d[1] * d[2]))
-        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
-        if isinstance(fields, str):
-            fields = (fields,)
-        unknown = set(fields) - {"d2", "dist"}
-        if unknown:
-            raise ValueError(f"distance_field: unknown fields {sorted(unknown)}")
-        if isinstance(obstacles, str):
-            obstacles = (obstacles,)
-        mask = int(obstacles) if isinstance(obstacles, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(obstacles))
-        if not 0 <= mask < 2 ** 32 or not 0 <= int(radius) < 2 ** 32:
-            raise ValueError("distance_field: obstacles and radius must fit 32 bits")
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= 2 ** 28)
+        shape = tuple(d) if ok else (1,)
+        fields = _want("distance_field", fields, ("d2", "dist"))
+        mask = _class_mask(obstacles)
+        _fit("distance_field: obstacles and radius must fit 32 bits", (mask, radius))
         out = {k: np.empty(shape, t) for k, t in (("d2", np.uint32), ("dist", np.float32)) if k in fields}
-        o = _lib.DistanceOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.DistanceOut._fields_])
-        info = _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_distance_field(self._h, lo3.ctypes.data, d3.ctypes.data, mask, int(radius), C.byref(o),
-                                                   C.byref(info)))
-        out.update(self._region_info(info))
+        out.update(self._region_call(self._M.la3dm_map_distance_field, lo3, d3, mask, int(radius), C.byref(_out(_lib.DistanceOut, out))))
         return out
 
     def frontier(self, lo, dims, open=("free",), unknown=("unknown", "missing"), connectivity=6, min_neighbours=1,
@@ -330,49 +379,37 @@ class BGKOctoMap:
         them.  cap=None counts first and then fills exactly n entries; an integer cap fills the first min(n, cap) and n is
         still the total.  At most 2^28 voxels in the region padded by one.  A device-resident map runs the query on the
         device pool (no host mirror refresh); a host-mode map runs it on the CPU, with identical results."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and (d[0] + 2) * (d[1] + 2) * (d[2] + 2) <= 2 ** 28 else 1)(d[0] * d[1] * d[2]))
-        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - {"index", "nbrs", "score"}
-        if bad:
-            raise ValueError(f"frontier: unknown fields {sorted(bad)}")
-        masks = []
-        for m in (open, unknown):
-            if isinstance(m, str):
-                m = (m,)
-            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
-        if not all(0 <= v < 2 ** 32 for v in masks + [int(connectivity), int(min_neighbours)]):
-            raise ValueError("frontier: open, unknown, connectivity and min_neighbours must fit 32 bits")
-        if cap is not None and not 0 <= int(cap) < 2 ** 64:
-            raise ValueError("frontier: cap must fit 64 bits")
-        info = _lib.RegionInfo()
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: (d[0] + 2) * (d[1] + 2) * (d[2] + 2) <= 2 ** 28)
+        fields = _want("frontier", fields, ("index", "nbrs", "score"))
+        masks = [_class_mask(open), _class_mask(unknown)]
+        _fit("frontier: open, unknown, connectivity and min_neighbours must fit 32 bits", masks + [connectivity, min_neighbours])
+        if cap is not None:
+            _fit("frontier: cap must fit 64 bits", [cap], bits=64)
         found = C.c_uint64(0)
+        region = {}
 
-        def call(k, o):
-            self._chk(self._M.la3dm_map_frontier(self._h, lo3.ctypes.data, d3.ctypes.data, masks[0], masks[1], int(connectivity),
-                                                 int(min_neighbours), k, C.byref(o) if o is not None else None, C.byref(found),
-                                                 C.byref(info)))
+        def call(k, arrays):
+            o = _out(_lib.FrontierOut, arrays, null_empty=("index", "nbrs"))
+            region.update(self._region_call(self._M.la3dm_map_frontier, lo3, d3, masks[0], masks[1], int(connectivity), int(min_neighbours),
+                                            k, C.byref(o) if arrays else None, C.byref(found)))
             return int(found.value)
 
         out = {}
         if "score" in fields:
-            out["score"] = np.empty(shape, np.uint8)
-        score = out["score"].ctypes.data if "score" in out else None
+            out["score"] = np.empty(tuple(d) if ok else (1,), np.uint8)
         if cap is None:   # the two-call protocol: count (the dense score comes with this call), then fill exactly n
-            k = call(0, _lib.FrontierOut(None, None, score) if score else None)
-            score = None
+            k = call(0, out)
+            filled = {}
         else:
-            k = min(int(cap), n)
-        out["index"] = np.empty(k, np.uint32)
-        out["nbrs"] = np.empty(k, np.uint8)
+            k = min(int(cap), cells if ok else 1)
+            filled = dict(out)
+        filled.update(index=np.empty(k, np.uint32), nbrs=np.empty(k, np.uint8))
         total = k
         if cap is not None or k:
-            total = call(k, _lib.FrontierOut(out["index"].ctypes.data if k else None, out["nbrs"].ctypes.data if k else None, score))
+            total = call(k, filled)
         m = min(total, k)
-        out["index"], out["nbrs"] = out["index"][:m], out["nbrs"][:m]
-        out["n"] = total
-        out.update(self._region_info(info))
+        out.update(index=filled["index"][:m], nbrs=filled["nbrs"][:m], n=total)
+        out.update(region)
         return out
 
     def gain(self, lo, dims, origins, offsets, count=("unknown", "missing"), stop=("occupied",), max_steps=4096, fields=("gain",)):
@@ -388,33 +425,19 @@ class BGKOctoMap:
         ceil(nx ny nz / 32); plus origin, block_key, cell as box() returns them.  At most 2^28 voxels, n * m <= 2^28 rays
         and n * W <= 2^28 words.  A device-resident map runs the query on the device pool (no host mirror refresh); a
         host-mode map runs it on the CPU, with identical results."""
-        lo3, d3, d, cells = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= GAIN_MAX_CELLS else 0)(d[0] * d[1] * d[2]))
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= GAIN_MAX_CELLS)
         o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
         f = np.ascontiguousarray(offsets, np.float32).reshape(-1, 3)
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - {"gain", "started", "hits", "seen"}
-        if bad:
-            raise ValueError(f"gain: unknown fields {sorted(bad)}")
-        masks = []
-        for m in (count, stop):
-            if isinstance(m, str):
-                m = (m,)
-            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
-        if not all(0 <= v < 2 ** 32 for v in masks + [int(max_steps), o.shape[0], f.shape[0]]):
-            raise ValueError("gain: count, stop, max_steps and the numbers of origins and offsets must fit 32 bits")
-        n, W = o.shape[0], (cells + 31) // 32
-        # (a request the call refuses gets one-element arrays: it is refused before a buffer is looked at)
-        served = cells > 0 and f.shape[0] > 0 and n * f.shape[0] <= GAIN_MAX_RAYS and n * W <= GAIN_MAX_WORDS
-        out = {k: np.empty(n if served else 1, np.uint32) for k in ("gain", "started", "hits") if k == "gain" or k in fields}
+        fields = _want("gain", fields, ("gain", "started", "hits", "seen"))
+        masks = [_class_mask(count), _class_mask(stop)]
+        n, m, W = o.shape[0], f.shape[0], (cells + 31) // 32
+        _fit("gain: count, stop, max_steps and the numbers of origins and offsets must fit 32 bits", masks + [max_steps, n, m])
+        ok = ok and m > 0 and n * m <= GAIN_MAX_RAYS and n * W <= GAIN_MAX_WORDS
+        out = {k: np.empty(n if ok else 1, np.uint32) for k in ("gain", "started", "hits") if k == "gain" or k in fields}
         if "seen" in fields:
-            out["seen"] = np.empty((n, W) if served else (1,), np.uint32)
-        g = _lib.GainOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.GainOut._fields_])
-        info = _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_gain(self._h, lo3.ctypes.data, d3.ctypes.data, o.ctypes.data if n else None, n,
-                                         f.ctypes.data if f.shape[0] else None, f.shape[0], masks[0], masks[1], int(max_steps),
-                                         C.byref(g), C.byref(info)))
-        out.update(self._region_info(info))
+            out["seen"] = np.empty((n, W) if ok else (1,), np.uint32)
+        out.update(self._region_call(self._M.la3dm_map_gain, lo3, d3, _addr(o), n, _addr(f), m, masks[0], masks[1], int(max_steps),
+                                     C.byref(_out(_lib.GainOut, out))))
         return out
 
     def score_poses(self, lo, dims, points, poses, obstacles=("occupied",), radius=16, fields=("sum_d2", "counts")):
@@ -429,33 +452,22 @@ class BGKOctoMap:
         them; radius: 1 .. 255 voxels.  Obstacles outside the region are not seen.  At most 2^28 voxels, 2^20 points, 2^20
         poses and 2^32 pairs.  A device-resident map runs the query on the device pool (no host mirror refresh); a
         host-mode map runs it on the CPU, with identical results."""
-        lo3, d3, d, cells = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= SCORE_MAX_CELLS else 0)(d[0] * d[1] * d[2]))
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= SCORE_MAX_CELLS)
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         T = np.ascontiguousarray(poses, np.float32)
         if T.ndim < 2 or T.shape[1:] not in ((3, 4), (12,)):
             raise ValueError("score_poses: poses must have the shape (P, 3, 4) or (P, 12)")
         T = T.reshape(-1, 12)
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - {"sum_d2", "counts"}
-        if bad:
-            raise ValueError(f"score_poses: unknown fields {sorted(bad)}")
-        if isinstance(obstacles, str):
-            obstacles = (obstacles,)
-        mask = int(obstacles) if isinstance(obstacles, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(obstacles))
+        fields = _want("score_poses", fields, ("sum_d2", "counts"))
+        mask = _class_mask(obstacles)
         n, P = pts.shape[0], T.shape[0]
-        if not all(0 <= v < 2 ** 32 for v in (mask, int(radius), n, P)):
-            raise ValueError("score_poses: obstacles, radius and the numbers of points and poses must fit 32 bits")
-        # (a request the call refuses gets one-element arrays: it is refused before a buffer is looked at)
-        served = cells > 0 and n <= SCORE_MAX_POINTS and P <= SCORE_MAX_POSES and n * P <= SCORE_MAX_PAIRS
-        out = dict(sum_d2=np.empty(P if served else 1, np.uint64))
+        _fit("score_poses: obstacles, radius and the numbers of points and poses must fit 32 bits", (mask, radius, n, P))
+        ok = ok and n <= SCORE_MAX_POINTS and P <= SCORE_MAX_POSES and n * P <= SCORE_MAX_PAIRS
+        out = dict(sum_d2=np.empty(P if ok else 1, np.uint64))
         if "counts" in fields:
-            out["counts"] = np.empty((P, 5) if served else (1, 5), np.uint32)
-        o = _lib.ScoreOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.ScoreOut._fields_])
-        info = _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_score_poses(self._h, lo3.ctypes.data, d3.ctypes.data, pts.ctypes.data if n else None, n,
-                                                T.ctypes.data if P else None, P, mask, int(radius), C.byref(o), C.byref(info)))
-        out.update(self._region_info(info))
+            out["counts"] = np.empty((P, 5) if ok else (1, 5), np.uint32)
+        out.update(self._region_call(self._M.la3dm_map_score_poses, lo3, d3, _addr(pts), n, _addr(T), P, mask, int(radius),
+                                     C.byref(_out(_lib.ScoreOut, out))))
         return out
 
     _PATHS_FIELDS = dict(cost=np.uint64, steps=np.uint32, stop=np.uint32, min_d2=np.uint32, ways=np.uint32, flags=np.uint8)
@@ -476,31 +488,23 @@ class BGKOctoMap:
         radius); ways = waypoints reached; flags uint8 = the PATH_* bits; plus origin, block_key, cell as box() returns
         them.  At most 2^28 voxels, 2^20 paths, 1024 waypoints a path and 2^26 waypoints.  A device-resident map runs the
         query on the device pool (no host mirror refresh); a host-mode map runs it on the CPU, with identical results."""
-        lo3, d3, d, cells = self._region(lo, dims, lambda d: (lambda c: c if 0 < c <= 1 << 28 else 0)(d[0] * d[1] * d[2]))
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= 1 << 28)
         W = np.ascontiguousarray(paths, np.float32)
         if W.ndim != 3 or W.shape[2] != 3:
             raise ValueError("score_paths: paths must have the shape (P, W, 3)")
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - set(self._PATHS_FIELDS)
-        if bad:
-            raise ValueError(f"score_paths: unknown fields {sorted(bad)}")
-        if isinstance(obstacles, str):
-            obstacles = (obstacles,)
-        mask = int(obstacles) if isinstance(obstacles, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(obstacles))
+        fields = _want("score_paths", fields, self._PATHS_FIELDS)
+        mask = _class_mask(obstacles)
         mc = [int(v) for v in move_cost]
         P, n_way = W.shape[0], W.shape[1]
-        if len(mc) != 3 or not all(0 <= v < 2 ** 32 for v in [mask, int(clearance), int(soft_radius), int(penalty), int(max_steps), P, n_way] + mc):
-            raise ValueError("score_paths: move_cost must have three entries, and every parameter and count must fit 32 bits")
+        msg = "score_paths: move_cost must have three entries, and every parameter and count must fit 32 bits"
+        if len(mc) != 3:
+            raise ValueError(msg)
+        _fit(msg, [mask, clearance, soft_radius, penalty, max_steps, P, n_way] + mc)
         prm = _lib.PathsParams(mask, int(clearance), int(soft_radius), int(penalty), (C.c_uint32 * 3)(*mc), int(max_steps))
-        # (a request the call refuses gets one-element arrays: it is refused before a buffer is looked at)
-        served = cells > 0 and 1 <= n_way <= PATHS_MAX_WAY and P <= PATHS_MAX_PATHS and P * n_way <= PATHS_MAX_WAYPOINTS
-        out = {k: np.empty(P if served else 1, t) for k, t in self._PATHS_FIELDS.items() if k == "cost" or k in fields}
-        o = _lib.PathsOut(*[out[k].ctypes.data if k in out else None for k, _ in _lib.PathsOut._fields_])
-        info = _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_score_paths(self._h, lo3.ctypes.data, d3.ctypes.data, W.ctypes.data if W.size else None, P, n_way,
-                                                C.byref(prm), C.byref(o), C.byref(info)))
-        out.update(self._region_info(info))
+        ok = ok and 1 <= n_way <= PATHS_MAX_WAY and P <= PATHS_MAX_PATHS and P * n_way <= PATHS_MAX_WAYPOINTS
+        out = {k: np.empty(P if ok else 1, t) for k, t in self._PATHS_FIELDS.items() if k == "cost" or k in fields}
+        out.update(self._region_call(self._M.la3dm_map_score_paths, lo3, d3, _addr(W), P, n_way, C.byref(prm),
+                                     C.byref(_out(_lib.PathsOut, out))))
         return out
 
     def reach(self, lo, dims, seeds, passable=("free",), obstacles=("occupied",), clearance=0, connectivity=6, max_steps=None,
@@ -520,36 +524,22 @@ class BGKOctoMap:
         block_key, cell as box() returns them.  At most 2^28 voxels in the region padded by one.  A device-resident map runs
         the wave on the device pool, one launch per level (no host mirror refresh); a host-mode map runs a queue BFS on the
         CPU, with identical results."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and (d[0] + 2) * (d[1] + 2) * (d[2] + 2) <= REACH_MAX_CELLS else 1)(d[0] * d[1] * d[2]))
-        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - {"steps"}
-        if bad:
-            raise ValueError(f"reach: unknown fields {sorted(bad)}")
-        masks = []
-        for m in (passable, obstacles):
-            if isinstance(m, str):
-                m = (m,)
-            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
-        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
-        t = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
-        nt = 0 if t is None else t.size
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: (d[0] + 2) * (d[1] + 2) * (d[2] + 2) <= REACH_MAX_CELLS)
+        fields = _want("reach", fields, ("steps",))
+        masks = [_class_mask(passable), _class_mask(obstacles)]
+        s, t, nt = _indices(seeds, targets)
         max_steps = REACH_MAX_STEPS if max_steps is None else int(max_steps)
-        if not all(0 <= v < 2 ** 32 for v in masks + [int(clearance), int(connectivity), max_steps, s.size, nt]):
-            raise ValueError("reach: passable, obstacles, clearance, connectivity, max_steps and the numbers of seeds and targets must fit 32 bits")
+        _fit("reach: passable, obstacles, clearance, connectivity, max_steps and the numbers of seeds and targets must fit 32 bits",
+             masks + [clearance, connectivity, max_steps, s.size, nt])
         out = {}
         if "steps" in fields:
-            out["steps"] = np.empty(shape, np.uint32)
+            out["steps"] = np.empty(tuple(d) if ok else (1,), np.uint32)
         if t is not None:
             out["target_steps"] = np.empty(nt, np.uint32)
-        o = _lib.ReachOut(out["steps"].ctypes.data if "steps" in out else None, out["target_steps"].ctypes.data if nt else None)
-        stats, info = _lib.ReachStats(), _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_reach(self._h, lo3.ctypes.data, d3.ctypes.data, s.ctypes.data if s.size else None, s.size, masks[0],
-                                          masks[1], int(clearance), int(connectivity), max_steps, t.ctypes.data if nt else None, nt,
-                                          C.byref(o), C.byref(stats), C.byref(info)))
-        out.update(n_seeded=int(stats.n_seeded), n_reached=int(stats.n_reached), levels=int(stats.levels))
-        out.update(self._region_info(info))
+        stats = _lib.ReachStats()
+        region = self._region_call(self._M.la3dm_map_reach, lo3, d3, _addr(s), s.size, masks[0], masks[1], int(clearance), int(connectivity),
+                                   max_steps, _addr(t), nt, C.byref(_out(_lib.ReachOut, out, null_empty=("target_steps",))), C.byref(stats))
+        out.update(stats.as_dict(), **region)
         return out
 
     def travel(self, lo, dims, seeds, passable=("free",), obstacles=("occupied",), clearance=0, soft_radius=0, penalty=0,
@@ -570,28 +560,18 @@ class BGKOctoMap:
         brick_runs and capped (0 on a host-mode map), plus origin, block_key, cell as box() returns them.  A device-resident
         map relaxes 8 x 8 x 8 bricks of the region on the device pool (no host mirror refresh); a host-mode map runs Dijkstra
         on the CPU, with identical results."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= TRAVEL_MAX_CELLS else 1)(d[0] * d[1] * d[2]))
-        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - {"cost", "parent"}
-        if bad:
-            raise ValueError(f"travel: unknown fields {sorted(bad)}")
-        masks = []
-        for m in (passable, obstacles):
-            if isinstance(m, str):
-                m = (m,)
-            masks.append(int(m) if isinstance(m, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(m)))
-        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
-        t = None if targets is None else np.ascontiguousarray(targets, np.uint32).reshape(-1)
-        nt = 0 if t is None else t.size
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= TRAVEL_MAX_CELLS)
+        shape = tuple(d) if ok else (1,)
+        fields = _want("travel", fields, ("cost", "parent"))
+        masks = [_class_mask(passable), _class_mask(obstacles)]
+        s, t, nt = _indices(seeds, targets)
         max_cost = TRAVEL_MAX_COST if max_cost is None else int(max_cost)
         moves = [int(v) for v in move_cost]
         if len(moves) != 3:
             raise ValueError("travel: move_cost must hold three values")
         words = masks + [int(clearance), int(soft_radius), int(penalty)] + moves + [int(connectivity), max_cost]
-        if not all(0 <= v < 2 ** 32 for v in words + [s.size, nt]):
-            raise ValueError("travel: the masks, clearance, soft_radius, penalty, move_cost, connectivity, max_cost and the numbers of seeds and targets must fit 32 bits")
+        _fit("travel: the masks, clearance, soft_radius, penalty, move_cost, connectivity, max_cost and the numbers of seeds and targets must fit 32 bits",
+             words + [s.size, nt])
         p = _lib.TravelParams(words[0], words[1], words[2], words[3], words[4], (C.c_uint32 * 3)(*moves), words[8], words[9])
         out = {}
         if "cost" in fields:
@@ -600,13 +580,10 @@ class BGKOctoMap:
             out["parent"] = np.empty(shape, np.uint8)
         if t is not None:
             out["target_cost"] = np.empty(nt, np.uint32)
-        o = _lib.TravelOut(out["cost"].ctypes.data if "cost" in out else None, out["target_cost"].ctypes.data if nt else None,
-                           out["parent"].ctypes.data if "parent" in out else None)
-        stats, info = _lib.TravelStats(), _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_travel(self._h, lo3.ctypes.data, d3.ctypes.data, s.ctypes.data if s.size else None, s.size, C.byref(p),
-                                           t.ctypes.data if nt else None, nt, C.byref(o), C.byref(stats), C.byref(info)))
-        out.update({k: int(getattr(stats, k)) for k in ("n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")})
-        out.update(self._region_info(info))
+        stats = _lib.TravelStats()
+        region = self._region_call(self._M.la3dm_map_travel, lo3, d3, _addr(s), s.size, C.byref(p), _addr(t), nt,
+                                   C.byref(_out(_lib.TravelOut, out, null_empty=("target_cost",))), C.byref(stats))
+        out.update(stats.as_dict(), **region)
         return out
 
     def clusters(self, lo, dims, members=None, member=("free",), connectivity=26, tile=0, min_size=1, cap=None, fields=("label",)):
@@ -624,41 +601,28 @@ class BGKOctoMap:
         device form's diagnostics rounds, brick_runs and capped (0 on a host-mode map), plus origin, block_key, cell as
         box() returns them.  A device-resident map relaxes 8 x 8 x 8 bricks of the region on the device pool (no host mirror
         refresh); a host-mode map flood-fills on the CPU, with identical results."""
-        lo3, d3, d, n = self._region(lo, dims, lambda d: (lambda c: c if min(d) > 0 and max(d) <= CLUSTERS_MAX_AXIS and ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= CLUSTERS_MAX_CELLS else 1)(d[0] * d[1] * d[2]))
-        shape = tuple(d) if n == d[0] * d[1] * d[2] else (n,)
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - {"label", "of_member"}
-        if bad:
-            raise ValueError(f"clusters: unknown fields {sorted(bad)}")
-        if isinstance(member, str):
-            member = (member,)
-        mask = int(member) if isinstance(member, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(member))
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: max(d) <= CLUSTERS_MAX_AXIS and ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= CLUSTERS_MAX_CELLS)
+        fields = _want("clusters", fields, ("label", "of_member"))
+        mask = _class_mask(member)
         lst = None if members is None else np.ascontiguousarray(members, np.uint32).reshape(-1)
         nm = 0 if lst is None else lst.size
-        room = (nm if lst is not None else n) if cap is None else int(cap)   # (no more clusters than members)
+        room = (nm if lst is not None else (cells if ok else 1)) if cap is None else int(cap)   # (no more clusters than members)
         words = [mask, int(connectivity), int(tile), int(min_size), nm, room]
-        if not all(0 <= v < 2 ** 32 for v in words):
-            raise ValueError("clusters: the mask, connectivity, tile, min_size, cap and the number of members must fit 32 bits")
-        p = _lib.ClustersParams(mask, 0 if lst is None else 1, words[1], words[2], words[3], nm, lst.ctypes.data if nm else None, room)
+        _fit("clusters: the mask, connectivity, tile, min_size, cap and the number of members must fit 32 bits", words)
+        p = _lib.ClustersParams(mask, 0 if lst is None else 1, words[1], words[2], words[3], nm, _addr(lst), room)
         out = {}
         if "label" in fields:
-            out["label"] = np.empty(shape, np.uint32)
+            out["label"] = np.empty(tuple(d) if ok else (1,), np.uint32)
         if "of_member" in fields:
             out["of_member"] = np.empty(nm, np.uint32)
         rec = dict(first=np.empty(room, np.uint32), size=np.empty(room, np.uint32), lo=np.empty((room, 3), np.uint32),
                    hi=np.empty((room, 3), np.uint32), sum=np.empty((room, 3), np.uint64), rep=np.empty(room, np.uint32))
-        ptr = lambda a: a.ctypes.data if a is not None and a.size else None   # noqa: E731
-        o = _lib.ClustersOut(ptr(out.get("label")), out["of_member"].ctypes.data if "of_member" in out else None,
-                             *[ptr(rec[k]) for k in ("first", "size", "lo", "hi", "sum", "rep")])
-        found, stats, info = C.c_uint32(0), _lib.ClustersStats(), _lib.RegionInfo()
-        self._chk(self._M.la3dm_map_clusters(self._h, lo3.ctypes.data, d3.ctypes.data, C.byref(p), C.byref(o), C.byref(found), C.byref(stats),
-                                             C.byref(info)))
+        found, stats = C.c_uint32(0), _lib.ClustersStats()
+        region = self._region_call(self._M.la3dm_map_clusters, lo3, d3, C.byref(p), C.byref(_out(_lib.ClustersOut, {**out, **rec}, null_empty=rec)),
+                                   C.byref(found), C.byref(stats))
         m = min(int(found.value), room)
         out.update({k: v[:m].copy() for k, v in rec.items()})   # (the unused tail of the room is never touched)
-        out["n"] = int(found.value)
-        out.update({k: int(getattr(stats, k)) for k in ("n_members", "n_clusters", "n_dropped", "largest", "rounds", "brick_runs", "capped")})
-        out.update(self._region_info(info))
+        out.update(n=int(found.value), **stats.as_dict(), **region)
         return out
 
     def pack(self):
@@ -667,19 +631,22 @@ class BGKOctoMap:
         device-resident map compacts its pool on the GPU before it crosses PCIe (no host mirror refresh; blocks in pool
         order); a host-mode map writes the same stream from its blocks (ascending key).  Not in the stream: the last
         scan's training data, the statistics, the options and the shard configuration."""
+        return self._sized(lambda *buf: self._M.la3dm_map_pack(self._h, *buf))
+
+    def _sized(self, call):
+        """a stream by the size-then-fill double call: call(buf, cap, size) with no buffer sizes it, then with one fills it"""
         size = C.c_uint64(0)
-        self._chk(self._M.la3dm_map_pack(self._h, None, 0, C.byref(size)))
+        self._chk(call(None, 0, C.byref(size)))
         buf = np.empty(int(size.value), np.uint8)
-        self._chk(self._M.la3dm_map_pack(self._h, buf.ctypes.data, buf.size, C.byref(size)))
+        self._chk(call(buf.ctypes.data, buf.size, C.byref(size)))
         return buf[:int(size.value)]
 
     def unpack(self, stream):
         """Load a stream of pack() (bytes or a uint8 array, of either writer) into this EMPTY map: same class, block_depth,
         resolution and default node, the other parameters may differ.  Validated first; a refused stream raises
         RuntimeError and leaves the map as it was."""
-        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
-                                   np.uint8).reshape(-1)
-        self._chk(self._M.la3dm_map_unpack(self._h, buf.ctypes.data if buf.size else None, buf.size))
+        buf = _stream(stream)
+        self._chk(self._M.la3dm_map_unpack(self._h, _addr(buf), buf.size))
         return self
 
     def save(self, path):
@@ -705,46 +672,27 @@ class BGKOctoMap:
             if stream_or_map is self:
                 raise ValueError("merge: a map is not merged into itself")
             stream_or_map = stream_or_map.pack()
-        stream = stream_or_map
-        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
-                                   np.uint8).reshape(-1)
+        buf = _stream(stream_or_map)
         stats = _lib.MergeStats()
-        self._chk(self._M.la3dm_map_merge(self._h, buf.ctypes.data if buf.size else None, buf.size, C.byref(stats)))
-        return {k: int(getattr(stats, k)) for k, _ in _lib.MergeStats._fields_}
+        self._chk(self._M.la3dm_map_merge(self._h, _addr(buf), buf.size, C.byref(stats)))
+        return stats.as_dict()
 
     def merge_file(self, path):
         """merge() of the file at path (a file save() wrote)"""
         stats = _lib.MergeStats()
         self._chk(self._M.la3dm_map_merge_file(self._h, os.fsencode(path), C.byref(stats)))
-        return {k: int(getattr(stats, k)) for k, _ in _lib.MergeStats._fields_}
+        return stats.as_dict()
 
     _DIFF_FIELDS = dict(block_key=(np.int64, 1), cell=(np.uint32, 1), code=(np.uint8, 1), centre=(np.float32, 3), A=(np.float32, 1),
                         B=(np.float32, 1))
 
     def _diff(self, fn, head, pairs, values, map_only, fields, cap):
         """what diff and diff_file share: the masks, the two-call protocol, the dict"""
-        if isinstance(pairs, str):
-            if pairs != "changed":
-                raise ValueError('diff: pairs is "changed", an integer mask or an iterable of (then, now) class names')
-            pair_mask = DIFF_PAIRS_CHANGED
-        elif isinstance(pairs, (int, np.integer)):
-            pair_mask = int(pairs)
-        else:
-            pair_mask = 0
-            for then, now in pairs:
-                pair_mask |= 1 << (5 * _RAY_CLASS[then] + _RAY_CLASS[now])
-        if isinstance(values, str):
-            values = (values,)
-        value_mask = int(values) if isinstance(values, (int, np.integer)) else sum(1 << _RAY_CLASS[k] for k in set(values))
-        if not 0 <= pair_mask < 2 ** 32 or not 0 <= value_mask < 2 ** 32:
-            raise ValueError("diff: pairs and values must fit 32 bits")
-        if isinstance(fields, str):
-            fields = (fields,)
-        bad = set(fields) - set(self._DIFF_FIELDS)
-        if bad:
-            raise ValueError(f"diff: unknown fields {sorted(bad)}")
-        if cap is not None and not 0 <= int(cap) < 2 ** 64:
-            raise ValueError("diff: cap must fit 64 bits")
+        pair_mask, value_mask = _pair_mask(pairs), _class_mask(values)
+        _fit("diff: pairs and values must fit 32 bits", (pair_mask, value_mask))
+        fields = _want("diff", fields, self._DIFF_FIELDS)
+        if cap is not None:
+            _fit("diff: cap must fit 64 bits", [cap], bits=64)
         params = _lib.DiffParams(pair_mask, value_mask, 1 if map_only else 0)
         stats = _lib.DiffStats()
         found = C.c_uint64(0)
@@ -755,14 +703,12 @@ class BGKOctoMap:
             k = min(int(cap), 2 ** 32 - 1)
         out = {f: np.empty((k, w) if w > 1 else k, t) for f, (t, w) in self._DIFF_FIELDS.items() if f in fields}
         if cap is not None or (k and out):
-            o = _lib.DiffOut(*[out[f].ctypes.data if f in out and k else None for f, _ in _lib.DiffOut._fields_])
-            self._chk(fn(*head, C.byref(params), k, C.byref(o), C.byref(found), C.byref(stats)))
+            self._chk(fn(*head, C.byref(params), k, C.byref(_out(_lib.DiffOut, out, null_empty=out)), C.byref(found), C.byref(stats)))
         m = min(int(found.value), k)
         out = {f: v[:m] for f, v in out.items()}
-        out["n"] = int(found.value)
-        out["pairs"] = np.array(stats.pairs, np.uint64).reshape(5, 5)
-        out["value_changed"] = np.array(stats.value_changed, np.uint64)
-        out.update({f: int(getattr(stats, f)) for f in ("n_stream_blocks", "n_map_only_blocks", "n_missing_now")})
+        counts = stats.as_dict()
+        out.update(n=int(found.value), pairs=np.array(counts.pop("pairs"), np.uint64).reshape(5, 5),
+                   value_changed=np.array(counts.pop("value_changed"), np.uint64), **counts)
         return out
 
     def diff(self, stream_or_map, pairs="changed", values=(), map_only=True, fields=("block_key", "cell", "code"), cap=None):
@@ -784,11 +730,8 @@ class BGKOctoMap:
             if type(stream_or_map) is not type(self):
                 raise TypeError(f"diff: a {type(stream_or_map).__name__} is not compared with a {type(self).__name__}")
             stream_or_map = stream_or_map.pack()
-        stream = stream_or_map
-        buf = np.ascontiguousarray(np.frombuffer(stream, np.uint8) if isinstance(stream, (bytes, bytearray, memoryview)) else stream,
-                                   np.uint8).reshape(-1)
-        return self._diff(self._M.la3dm_map_diff, (self._h, buf.ctypes.data if buf.size else None, buf.size), pairs, values, map_only,
-                          fields, cap)
+        buf = _stream(stream_or_map)
+        return self._diff(self._M.la3dm_map_diff, (self._h, _addr(buf), buf.size), pairs, values, map_only, fields, cap)
 
     def diff_file(self, path, pairs="changed", values=(), map_only=True, fields=("block_key", "cell", "code"), cap=None):
         """diff() against the file at path (a file save() or evict_file() wrote)"""
@@ -808,12 +751,8 @@ class BGKOctoMap:
         stream.  A device-resident map compacts the selected blocks on the GPU (pool slot order, no mirror refresh), a
         host-mode map writes them in ascending key order.  No block selected gives the header alone."""
         lo3, hi3 = self._region_points(lo, hi)
-        size = C.c_uint64(0)
         args = (self._h, lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0)
-        self._chk(self._M.la3dm_map_pack_region(*args, None, 0, C.byref(size)))
-        buf = np.empty(int(size.value), np.uint8)
-        self._chk(self._M.la3dm_map_pack_region(*args, buf.ctypes.data, buf.size, C.byref(size)))
-        return buf[:int(size.value)]
+        return self._sized(lambda *buf: self._M.la3dm_map_pack_region(*args, *buf))
 
     def erase_region(self, lo, hi, inside=True):
         """Remove the selected blocks (the region as in pack_region): their voxels read as missing through every query,
@@ -823,19 +762,16 @@ class BGKOctoMap:
         lo3, hi3 = self._region_points(lo, hi)
         stats = _lib.EraseStats()
         self._chk(self._M.la3dm_map_erase_region(self._h, lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0, C.byref(stats)))
-        return {k: int(getattr(stats, k)) for k, _ in _lib.EraseStats._fields_}
+        return stats.as_dict()
 
     def evict(self, lo, hi, inside=True):
         """pack_region(), then erase_region() of the same region: the stream is complete on the host before the first block
         is removed, and a failure of the pack step leaves the map as it was.  Returns the stream as bytes; merge() of it
         brings the blocks back."""
         lo3, hi3 = self._region_points(lo, hi)
-        size = C.c_uint64(0)
         args = (self._h, lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0)
-        self._chk(self._M.la3dm_map_evict(*args, None, 0, C.byref(size), None))   # (sizes only: nothing is removed)
-        buf = np.empty(int(size.value), np.uint8)
-        self._chk(self._M.la3dm_map_evict(*args, buf.ctypes.data, buf.size, C.byref(size), None))
-        return buf[:int(size.value)].tobytes()
+        # (the sizing call removes nothing)
+        return self._sized(lambda *buf: self._M.la3dm_map_evict(*args, *buf, None)).tobytes()
 
     def evict_file(self, path, lo, hi, inside=True):
         """evict() into a file: the stream is written to path + ".tmp" and renamed to path before the first block is removed
@@ -843,7 +779,7 @@ class BGKOctoMap:
         lo3, hi3 = self._region_points(lo, hi)
         stats = _lib.EraseStats()
         self._chk(self._M.la3dm_map_evict_file(self._h, os.fsencode(path), lo3.ctypes.data, hi3.ctypes.data, 1 if inside else 0, C.byref(stats)))
-        return {k: int(getattr(stats, k)) for k, _ in _lib.EraseStats._fields_}
+        return stats.as_dict()
 
     def mirror_syncs(self):
         """how often the host mirror of the device-resident map was refreshed (a download of every node of every block)"""
@@ -1074,12 +1010,10 @@ def pack_info(stream_or_path):
     validation raises RuntimeError."""
     if isinstance(stream_or_path, (str, os.PathLike)):
         stream_or_path = np.fromfile(stream_or_path, np.uint8)
-    if isinstance(stream_or_path, (bytes, bytearray, memoryview)):
-        stream_or_path = np.frombuffer(stream_or_path, np.uint8)
-    buf = np.ascontiguousarray(stream_or_path, np.uint8).reshape(-1)
+    buf = _stream(stream_or_path)
     h = _lib.PackHeader()
     L = _lib.hip()
-    if L.la3dm_pack_info(buf.ctypes.data if buf.size else None, buf.size, C.byref(h)) != 0:
+    if L.la3dm_pack_info(_addr(buf), buf.size, C.byref(h)) != 0:
         raise RuntimeError(L.la3dm_last_error(None).decode())
     out = {k: getattr(h, k) for k, _ in _lib.PackHeader._fields_ if k not in ("magic", "reserved")}
     out["magic"] = bytes(h.magic)

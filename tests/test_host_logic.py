@@ -34,6 +34,23 @@ def test_abi_exports_every_declared_symbol(built):
     for n in mnames:
         assert hasattr(m, n), n
     assert sorted(mnames) == sorted(_lib.MAP_SYMBOLS)
+    # the binding: one table of signatures per library, every entry applied, the symbol lists read from the tables
+    assert _lib.HIP_SYMBOLS == list(_lib.HIP_API) and _lib.MAP_SYMBOLS == list(_lib.MAP_API)
+    for lib, symbols in ((_lib.hip(), _lib.HIP_SYMBOLS), (_lib.maplib(), _lib.MAP_SYMBOLS)):
+        for n in symbols:
+            assert getattr(lib, n).argtypes is not None, n
+    # a query's map view, host form and device form take the same arguments after the handle, except where the table says so
+    assert set(_lib.QUERY_DIFFERS) <= set(_lib.HIP_SYMBOLS + _lib.MAP_SYMBOLS)
+    checked = 0
+    for stem, (view, forms, args) in _lib.QUERIES.items():
+        entries = [(_lib.maplib(), f"la3dm_map_{view}")] + [(_lib.hip(), f"la3dm_devmap_{stem}_{f}") for f in forms]
+        for lib, n in entries:
+            if n not in _lib.QUERY_DIFFERS:
+                assert list(getattr(lib, n).argtypes)[1:] == args, n
+                checked += 1
+    assert checked == sum(1 + len(forms) for _, forms, _ in _lib.QUERIES.values()) - len(_lib.QUERY_DIFFERS)
+    assert {"raycast", "box", "columns", "distance", "frontier", "gain", "score_poses", "score_paths", "reach", "travel",
+            "clusters"} == {s for s, (_, forms, _) in _lib.QUERIES.items() if forms == ("host", "device")}
 
 
 def test_no_device_no_fallback(built):
