@@ -894,6 +894,64 @@ int la3dm_devmap_score_poses_host(la3dm_devmap *dm, const float *lo3, const uint
 int la3dm_devmap_score_poses_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_points3,
                                     uint32_t n_points, const float *d_poses12, uint32_t n_poses, uint32_t obstacle_mask,
                                     uint32_t radius, const la3dm_score_out *d_out, la3dm_region_info *info);
+/* Nearest: WHICH obstacle voxel is the nearest — the feature transform of a region, dense (nearest) and per point of a
+ * cloud (nearest_points: the correspondences of an ICP step; v - nearest(v) is the direction away from the obstacle).
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's.
+ *   Obstacles are distance_field's: voxel v is an obstacle when obstacle_mask & (1u << cls(v)) is set, bits 0 to 4.
+ *   Definition.  D(v) = the minimum over the obstacles o INSIDE THE REGION of |v - o|^2, distance_field's D with its blind
+ *     spot: obstacles outside the region are not seen; pad the region by `radius` where that matters.
+ *   nearest, per voxel v.  index[v] = the SMALLEST FLAT INDEX among the obstacles at squared distance D(v) when D(v) <=
+ *     radius^2, else LA3DM_NEAREST_NONE; an obstacle voxel answers its own index.  The smallest flat index is the
+ *     lexicographically smallest (i', j', k'): one reproducible answer on the medial axis, and a tie-break that is
+ *     separable (smaller k' in the z stage, smaller j' in the y pass, smaller i' in the x pass).  d2[v] is exactly what
+ *     distance_field(lo, dims, obstacle_mask, radius) holds in d2, LA3DM_DF_FAR included.  Either array may be NULL, not
+ *     both.
+ *   nearest_points, per point q of points3 (n_points packed xyz).  With pose12 (one row-major 3 x 4 [R | t]) w =
+ *     score_poses' transform of q, per axis c ((R[c][0] * x + R[c][1] * y) + R[c][2] * z) + t[c] in fp32, every operation
+ *     rounded on its own; with pose12 == NULL w is the point's three floats verbatim, no arithmetic.  The class of the
+ *     point is score_poses' class of the pair, by the same tests in the same order: LA3DM_SCORE_INVALID, LA3DM_SCORE_OUTSIDE,
+ *     then HIT / NEAR / FAR from d2 at the voxel search resolves for w.  Outputs, each [n_points], each optional, at least
+ *     one: cls (the class), voxel (the flat index of the point's voxel; NONE for OUTSIDE and INVALID), index (nearest's
+ *     index[voxel]; NONE for FAR, OUTSIDE and INVALID), d2 (nearest's d2[voxel]; LA3DM_DF_FAR for FAR, OUTSIDE and INVALID).
+ *   radius lies in 1 ... LA3DM_NEAREST_MAX_RADIUS (255, as for score_poses): every partial sum of the transform stays
+ *     below 2^18 and an axis offset fits 9 bits.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, no buffer touched, nothing reserved), in this
+ *     order: an obstacle_mask of 0 or with bits above 0x1F; a radius outside 1 ... LA3DM_NEAREST_MAX_RADIUS; n_points >
+ *     LA3DM_SCORE_MAX_POINTS (nearest_points); what box refuses for lo and dims; more than LA3DM_DF_MAX_CELLS voxels; then
+ *     the buffers — nearest: a NULL out, an out with both arrays NULL; nearest_points with n_points > 0: a NULL points3, a
+ *     NULL out, an out with all four arrays NULL.
+ *   nearest_points with n_points = 0 is served and writes nothing.  An empty map answers from the definition without a
+ *     launch that reads the pool: every voxel is MISSING, so with mask bit 3 index[v] = v and d2 = 0, otherwise NONE and FAR.
+ *   Working storage: per voxel 4 bytes of y-pass keys, 2 bytes of z offsets and one obstacle bit, for nearest_points also
+ *     index and d2 (8 bytes), in a grow-only arena of the devmap (released with it; a smaller request after a larger one
+ *     allocates nothing).
+ *   Everything is integers after the transform: the results equal the host form (BGKOctoMap::nearest and ::nearest_points
+ *   on a host-mode map) exactly. */
+#define LA3DM_NEAREST_NONE       0xFFFFFFFFu
+#define LA3DM_NEAREST_MAX_RADIUS 255u
+typedef struct la3dm_nearest_out {
+    uint32_t *index;   /* [nx ny nz] or NULL: flat index of the nearest obstacle, LA3DM_NEAREST_NONE beyond the radius */
+    uint32_t *d2;      /* [nx ny nz] or NULL: distance_field's d2; at least one of the two */
+} la3dm_nearest_out;
+typedef struct la3dm_nearest_points_out {   /* each [n_points] or NULL; at least one */
+    uint8_t *cls;      /* LA3DM_SCORE_HIT ... LA3DM_SCORE_INVALID */
+    uint32_t *voxel;   /* flat index of the point's voxel; LA3DM_NEAREST_NONE for OUTSIDE and INVALID */
+    uint32_t *index;   /* index[voxel]; LA3DM_NEAREST_NONE for FAR, OUTSIDE and INVALID */
+    uint32_t *d2;      /* d2[voxel]; LA3DM_DF_FAR for FAR, OUTSIDE and INVALID */
+} la3dm_nearest_points_out;
+/* host pointers: upload of the points and the pose, the launches, download, synchronise — on the map's stream */
+int la3dm_devmap_nearest_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                              uint32_t radius, const la3dm_nearest_out *out, la3dm_region_info *info);
+int la3dm_devmap_nearest_points_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *points3,
+                                     uint32_t n_points, const float *pose12, uint32_t obstacle_mask, uint32_t radius,
+                                     const la3dm_nearest_points_out *out, la3dm_region_info *info);
+/* device pointers (points3, pose12 and out's arrays already in HBM on the map's device; the 32-bit arrays 4-byte aligned;
+ * lo3, dims3 and info stay host-side); return when the results are complete */
+int la3dm_devmap_nearest_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                                uint32_t radius, const la3dm_nearest_out *d_out, la3dm_region_info *info);
+int la3dm_devmap_nearest_points_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_points3,
+                                       uint32_t n_points, const float *d_pose12, uint32_t obstacle_mask, uint32_t radius,
+                                       const la3dm_nearest_points_out *d_out, la3dm_region_info *info);
 /* Reach: the hop distance from seed voxels through the passable voxels of a region — can a goal be got to, and in how
  * many moves.  A breadth-first wave, one launch per level.
  *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; cls(v)

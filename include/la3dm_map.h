@@ -169,6 +169,19 @@ int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, 
 int la3dm_map_score_poses(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
                           const float *poses12, uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out *out,
                           la3dm_region_info *info);
+/* BGKOctoMap::nearest: which obstacle is the nearest.  Per voxel of box's region out->index = the flat index of the nearest
+ * voxel of the region whose class is in obstacle_mask (the smallest flat index among equals; LA3DM_NEAREST_NONE beyond
+ * `radius` voxels) and out->d2 = distance_field's d2; either may be NULL, not both.  BGKOctoMap::nearest_points: the same
+ * per point of points3, moved by the optional pose12 (row-major 3 x 4 [R | t]; NULL: the points as they are): out->cls =
+ * score_poses' class of the point, out->voxel = its voxel, out->index = that voxel's nearest obstacle, out->d2 = the
+ * squared distance — the correspondences of an ICP step.  Contract, limits and refusals: include/la3dm_hip.h
+ * (la3dm_devmap_nearest_host).  Device-resident maps run the queries on the device pool without a mirror refresh,
+ * host-mode maps on the CPU; the results are identical. */
+int la3dm_map_nearest(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                      const la3dm_nearest_out *out, la3dm_region_info *info);
+int la3dm_map_nearest_points(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
+                             const float *pose12, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out *out,
+                             la3dm_region_info *info);
 /* BGKOctoMap::score_paths: cost and clearance of many candidate trajectories.  Every path of ways3 (n_paths x n_way x 3
  * floats, world frame; a shorter path repeats its last waypoint) is walked voxel by voxel through box's region against d2 =
  * distance_field(lo, dims, obstacle_mask, max(1, clearance, soft_radius)); out->cost (mandatory) [n_paths] = travel's cost

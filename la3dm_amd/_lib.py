@@ -105,6 +105,14 @@ class ScoreOut(C.Structure):     # la3dm_score_out
     _fields_ = [(k, C.c_void_p) for k in ("sum_d2", "counts")]
 
 
+class NearestOut(C.Structure):   # la3dm_nearest_out
+    _fields_ = [(k, C.c_void_p) for k in ("index", "d2")]
+
+
+class NearestPointsOut(C.Structure):   # la3dm_nearest_points_out
+    _fields_ = [(k, C.c_void_p) for k in ("cls", "voxel", "index", "d2")]
+
+
 class PathsParams(C.Structure):  # la3dm_paths_params
     _fields_ = [("obstacle_mask", C.c_uint32), ("clearance", C.c_uint32), ("soft_radius", C.c_uint32), ("penalty", C.c_uint32),
                 ("move_cost", C.c_uint32 * 3), ("max_steps", C.c_uint32)]
@@ -217,6 +225,12 @@ QUERY_DIFFERS = {
 }
 
 
+# nearest and nearest_points have the three forms of a query as well; they are declared entry by entry in the tables below:
+# what follows the handle
+_NEAREST = [vp, vp, u32, u32, P(NearestOut), _INFO]
+_NEAREST_POINTS = [vp, vp, vp, u32, vp, u32, u32, P(NearestPointsOut), _INFO]
+
+
 def _query_entries(of_map):
     """the queries' entries of one library's table"""
     out = {}
@@ -261,6 +275,10 @@ HIP_API = {
     "la3dm_devmap_diag_add_repeat": (cint, [vp] * 4 + [u32] + [vp] * 2),
     "la3dm_devmap_diag_scan": (cint, [vp, cint, vp, u32, vp, vp]),
     "la3dm_devmap_diag_sort": (cint, [vp, vp, vp, u32, cint, vp, vp]),
+    "la3dm_devmap_nearest_host": (cint, [vp] + _NEAREST),
+    "la3dm_devmap_nearest_device": (cint, [vp] + _NEAREST),
+    "la3dm_devmap_nearest_points_host": (cint, [vp] + _NEAREST_POINTS),
+    "la3dm_devmap_nearest_points_device": (cint, [vp] + _NEAREST_POINTS),
     **_query_entries(of_map=False),
 }
 
@@ -319,6 +337,8 @@ MAP_API = {
     "la3dm_map_diff_file": (cint, [vp, C.c_char_p] + QUERIES["diff"][2][2:]),
     "la3dm_map_evict": (cint, [vp] + QUERIES["pack_region"][2] + [P(EraseStats)]),
     "la3dm_map_evict_file": (cint, [vp, C.c_char_p, vp, vp, cint, P(EraseStats)]),
+    "la3dm_map_nearest": (cint, [vp] + _NEAREST),
+    "la3dm_map_nearest_points": (cint, [vp] + _NEAREST_POINTS),
     **_query_entries(of_map=True),
 }
 HIP_SYMBOLS = list(HIP_API)

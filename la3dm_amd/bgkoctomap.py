@@ -22,6 +22,7 @@ DIFF_PAIRS_CHANGED = 0x0FBEFBE      # LA3DM_DIFF_PAIRS_CHANGED: the 20 (then, no
 GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: voxels of gain's region, n * m rays, n * W set words
 SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS = 1 << 28, 1 << 20, 1 << 20, 1 << 32, 255   # LA3DM_SCORE_MAX_*
 SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID = range(5)   # LA3DM_SCORE_*: the columns of score_poses' counts
+NEAREST_NONE, NEAREST_MAX_RADIUS = 0xFFFFFFFF, 255   # LA3DM_NEAREST_*: nearest found no obstacle within the radius; the largest radius
 PATH_BLOCKED, PATH_LEFT, PATH_TRUNCATED, PATH_INVALID = 1, 2, 4, 8   # LA3DM_PATH_*: the bits of score_paths' flags
 PATH_NONE = 0xFFFFFFFF              # LA3DM_PATH_NONE: score_paths' stop of a walk that did not stop
 PATHS_MAX_STEPS, PATHS_MAX_WAY, PATHS_MAX_PATHS, PATHS_MAX_WAYPOINTS = 1 << 20, 1024, 1 << 20, 1 << 26   # LA3DM_PATHS_MAX_*
@@ -468,6 +469,53 @@ class BGKOctoMap:
             out["counts"] = np.empty((P, 5) if ok else (1, 5), np.uint32)
         out.update(self._region_call(self._M.la3dm_map_score_poses, lo3, d3, _addr(pts), n, _addr(T), P, mask, int(radius),
                                      C.byref(_out(_lib.ScoreOut, out))))
+        return out
+
+    def nearest(self, lo, dims, obstacles=("occupied",), radius=16, fields=("index", "d2")):
+        """WHICH obstacle is the nearest: per voxel of the region of box(lo, dims) index (uint32, shape dims) = the flat index
+        (i * ny + j) * nz + k of the nearest voxel of the region whose class is in `obstacles` — the smallest flat index among
+        obstacles at the same distance, the voxel's own index on an obstacle, NEAREST_NONE beyond `radius` voxels — and d2
+        (uint32) = exactly distance_field(lo, dims, obstacles, radius)'s d2.  np.unravel_index(index, dims) gives the
+        obstacle's (i', j', k'); v - nearest(v) is the direction away from it.  obstacles: as distance_field takes them;
+        radius: 1 .. 255 voxels.  Obstacles outside the region are not seen: pad the region by `radius` where that matters.
+        `fields` names the arrays wanted (at least one).  Also returned: origin, block_key, cell as box() returns them.  At
+        most 2^28 voxels.  A device-resident map runs the query on the device pool (no host mirror refresh); a host-mode map
+        runs it on the CPU, with identical results."""
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= 1 << 28)
+        fields = _want("nearest", fields, ("index", "d2"))
+        mask = _class_mask(obstacles)
+        _fit("nearest: obstacles and radius must fit 32 bits", (mask, radius))
+        out = {k: np.empty(tuple(d) if ok else (1,), np.uint32) for k in ("index", "d2") if k in fields}
+        out.update(self._region_call(self._M.la3dm_map_nearest, lo3, d3, mask, int(radius), C.byref(_out(_lib.NearestOut, out))))
+        return out
+
+    _NEAREST_POINTS_FIELDS = dict(cls=np.uint8, voxel=np.uint32, index=np.uint32, d2=np.uint32)
+
+    def nearest_points(self, lo, dims, points, pose=None, obstacles=("occupied",), radius=16, fields=("cls", "voxel", "index", "d2")):
+        """nearest() per point of a cloud — the correspondences of an ICP step.  Every point of `points` (n, 3) is moved by
+        `pose` ((3, 4) or (12,), row-major [R | t], float32 and op by op as score_poses moves it; None: the points are taken
+        as they are, in the map frame), its voxel resolved as search resolves it.  Returns a dict of (n,) arrays, those named
+        in `fields`: cls uint8 = the point's class as score_poses counts it (SCORE_HIT: on an obstacle, SCORE_NEAR: one within
+        `radius` voxels, SCORE_FAR, SCORE_OUTSIDE the region, SCORE_INVALID: a coordinate the lattice cannot hold); voxel =
+        the flat index of the point's voxel (NEAREST_NONE for OUTSIDE and INVALID); index = nearest()'s index at that voxel
+        (NEAREST_NONE for FAR, OUTSIDE, INVALID); d2 = its squared distance in voxels (DF_FAR likewise); plus origin,
+        block_key, cell as box() returns them — origin + unravel_index(index, dims) * resolution is the obstacle's centre.
+        obstacles, radius and the region's blind spot: as nearest().  At most 2^28 voxels and 2^20 points."""
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: d[0] * d[1] * d[2] <= 1 << 28)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        T = None
+        if pose is not None:
+            T = np.ascontiguousarray(pose, np.float32)
+            if T.shape not in ((3, 4), (12,)):
+                raise ValueError("nearest_points: pose must have the shape (3, 4) or (12,)")
+        fields = _want("nearest_points", fields, self._NEAREST_POINTS_FIELDS)
+        mask = _class_mask(obstacles)
+        n = pts.shape[0]
+        _fit("nearest_points: obstacles, radius and the number of points must fit 32 bits", (mask, radius, n))
+        ok = ok and n <= SCORE_MAX_POINTS
+        out = {k: np.empty(n if ok else 1, t) for k, t in self._NEAREST_POINTS_FIELDS.items() if k in fields}
+        out.update(self._region_call(self._M.la3dm_map_nearest_points, lo3, d3, _addr(pts), n, _addr(T), mask, int(radius),
+                                     C.byref(_out(_lib.NearestPointsOut, out))))
         return out
 
     _PATHS_FIELDS = dict(cost=np.uint64, steps=np.uint32, stop=np.uint32, min_d2=np.uint32, ways=np.uint32, flags=np.uint8)

@@ -32,6 +32,7 @@
 #include "devmap_frontier.h"
 #include "devmap_gain.h"
 #include "devmap_score.h"
+#include "devmap_nearest.h"
 #include "devmap_paths.h"
 #include "devmap_reach.h"
 #include "devmap_travel.h"
@@ -93,6 +94,7 @@ struct la3dm_devmap {
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
     Arena score_work;             // score_poses: d2 (4 bytes per voxel), then the chunks' partial records (devmap_score.h); score_paths: d2 (devmap_paths.h)
+    Arena nt_work;                // nearest: the y keys (4 bytes per voxel), the z offsets (2), the obstacle bits; nearest_points: index and d2 as well (devmap_nearest.h)
     Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
     Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
     Arena clusters_work;          // clusters: two brick-major label buffers, side / active per brick, the round counts, sizes, flags, numbers (devmap_clusters.h)
@@ -731,7 +733,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->score_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3218,6 +3220,183 @@ int la3dm_devmap_distance_device(la3dm_devmap *dm, const float *lo3, const uint3
 int la3dm_devmap_distance_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
                                uint32_t radius, const la3dm_distance_out *out, la3dm_region_info *info) {
     return distance_query(dm, true, "la3dm_devmap_distance_host", lo3, dims3, obstacle_mask, radius, out, info);
+}
+
+// ---- nearest and nearest_points: which obstacle is the nearest (devmap_nearest.h) ---------------------------------
+
+// the parts of nt_work: per voxel the y keys, the z offsets and the obstacle bits; for nearest_points index and d2 as well
+struct NtWork {
+    uint32_t *keys;
+    int16_t *az;
+    uint32_t *bits;
+    uint32_t *index, *d2;   // null for nearest, whose answer goes to the caller's arrays
+};
+
+static int nearest_reserve(la3dm_devmap *dm, size_t n, bool with_answer, NtWork &w) {
+    const auto pad = [](size_t bytes) { return (bytes + 15) & ~(size_t)15; };
+    const size_t keys = pad(4 * n), az = pad(2 * n), bits = pad(4 * ((n + 31) / 32)), answer = with_answer ? pad(4 * n) : 0;
+    DM_RESERVE(dm->nt_work, keys + az + bits + 2 * answer);
+    char *p = (char *)dm->nt_work.ptr;
+    w.keys = (uint32_t *)p;
+    w.az = (int16_t *)(p + keys);
+    w.bits = (uint32_t *)(p + keys + az);
+    w.index = with_answer ? (uint32_t *)(p + keys + az + bits) : nullptr;
+    w.d2 = with_answer ? (uint32_t *)(p + keys + az + bits + answer) : nullptr;
+    return LA3DM_OK;
+}
+
+// the y pass over 16-bit z offsets or the x pass over 32-bit keys: staged in LDS where the rows of a workgroup and their
+// halo fit, else straight from global memory (y: radius <= 240, x: radius <= 112)
+static void nt_pass_launch(hipStream_t st, bool x_pass, uint32_t grid, uint32_t rows, const NtPassArgs &p) {
+    const uint32_t lds = rows * 64u * (x_pass ? 4u : 2u);
+    const bool fits = lds <= kDfLdsBytes;
+    void (*pass)(NtPassArgs) = x_pass ? (fits ? dm_nt_pass<uint32_t, true> : dm_nt_pass<uint32_t, false>)
+                                      : (fits ? dm_nt_pass<int16_t, true> : dm_nt_pass<int16_t, false>);
+    hipLaunchKernelGGL(pass, dim3(grid), dim3(256), fits ? lds : 0, st, p);
+}
+
+// The four launches on the map's stream: distance_field's bits, the z offsets, the y keys, the x pass with the chase into
+// index and d2 (device memory, either may be null).
+static void nearest_launch(la3dm_devmap *dm, const RegionGeom &g, uint32_t obstacle_mask, uint32_t radius, const NtWork &w, uint32_t *index,
+                           uint32_t *d2) {
+    hipStream_t st = dm->ctx->stream;
+    const RegionArgs a = region_args(dm, g);
+    hipLaunchKernelGGL(dm_df_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, obstacle_mask, w.bits);
+    hipLaunchKernelGGL(dm_nt_z, dim3(cdiv(a.total, 256)), dim3(256), 0, st, w.bits, w.az, a.total, a.nz, radius);
+    NtPassArgs p;
+    memset(&p, 0, sizeof(p));
+    p.radius = radius;
+    p.r2 = radius * radius;
+    p.ny = a.ny;
+    p.nz = a.nz;
+    const uint32_t rows = kDfRows + 2u * radius;   // what a workgroup stages at most
+    p.in = w.az;
+    p.keys = w.keys;
+    p.L = a.ny;
+    p.S = a.nz;
+    p.n_lt = cdiv(p.L, kDfRows);
+    p.n_ct = cdiv(p.S, 64);
+    nt_pass_launch(st, false, a.nx * p.n_lt * p.n_ct, rows, p);
+    p.in = w.keys;
+    p.keys = nullptr;
+    p.az = w.az;
+    p.index = index;
+    p.d2 = d2;
+    p.L = a.nx;
+    p.S = a.ny * a.nz;
+    p.n_lt = cdiv(p.L, kDfRows);
+    p.n_ct = cdiv(p.S, 64);
+    nt_pass_launch(st, true, p.n_lt * p.n_ct, rows, p);
+}
+
+static int nearest_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask,
+                         uint32_t radius, const la3dm_nearest_out *out, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::nearest_check(obstacle_mask, radius, 0)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kNearest, out != nullptr, out && (out->index || out->d2), who, g));
+    la3dm_nearest_out o = *out;
+    const size_t n = (size_t)g.total;
+    if (dm->n_blocks == 0) {   // every voxel is MISSING: each its own nearest obstacle, or none anywhere
+        const Fill f{dm, host};
+        const bool all = (obstacle_mask >> LA3DM_RAY_MISSING) & 1u;
+        DM_OK(f.bytes(o.d2, all ? 0 : 0xFF, 4 * n));
+        if (!all) {
+            DM_OK(f.bytes(o.index, 0xFF, 4 * n));
+        } else if (o.index && host) {
+            for (size_t v = 0; v < n; ++v) o.index[v] = (uint32_t)v;
+        } else if (o.index) {
+            hipLaunchKernelGGL(dm_nt_iota, dim3(cdiv((uint32_t)n, 256)), dim3(256), 0, dm->ctx->stream, o.index, (uint32_t)n);
+            DM_TRY(hipGetLastError());
+        }
+    } else {
+        Stage s(dm, host);
+        s.out(o.index, n);
+        s.out(o.d2, n);
+        DM_OK(s.reserve());
+        NtWork w;
+        DM_OK(nearest_reserve(dm, n, false, w));
+        nearest_launch(dm, g, obstacle_mask, radius, w, o.index, o.d2);
+        DM_TRY(hipGetLastError());
+        DM_OK(s.download());
+    }
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_nearest_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                                const la3dm_nearest_out *d_out, la3dm_region_info *info) {
+    return nearest_query(dm, false, "la3dm_devmap_nearest_device", lo3, dims3, obstacle_mask, radius, d_out, info);
+}
+
+int la3dm_devmap_nearest_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                              const la3dm_nearest_out *out, la3dm_region_info *info) {
+    return nearest_query(dm, true, "la3dm_devmap_nearest_host", lo3, dims3, obstacle_mask, radius, out, info);
+}
+
+static int nearest_points_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const float *points3,
+                                uint32_t n_points, const float *pose12, uint32_t obstacle_mask, uint32_t radius,
+                                const la3dm_nearest_points_out *out, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::nearest_check(obstacle_mask, radius, n_points)));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kNearestPoints, true, true, who, g));   // lo, dims, the limit and the range: before any buffer
+    DM_OK(refuse(dm, who, la3dm_region::nearest_buffers(n_points, points3 != nullptr, out != nullptr,
+                                                        out && (out->cls || out->voxel || out->index || out->d2))));
+    if (info) *info = g.info;
+    if (n_points == 0) return LA3DM_OK;
+    la3dm_nearest_points_out o = *out;
+    Stage s(dm, host);
+    s.in(points3, 3ull * n_points);
+    s.in(pose12, 12);
+    s.out(o.cls, n_points);
+    s.out(o.voxel, n_points);
+    s.out(o.index, n_points);
+    s.out(o.d2, n_points);
+    DM_OK(s.reserve());
+    NtPointsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.points = points3;
+    a.pose = pose12;
+    a.n_points = n_points;
+    a.resolution = dm->ctx->p.resolution;
+    a.block_size = dm->block_size;
+    a.lim = 1 << (dm->depth - 1);
+    for (int k = 0; k < 3; ++k) {
+        a.g0[k] = g.g0[k];
+        a.dims[k] = g.dims[k];
+    }
+    if (dm->n_blocks == 0) {   // no transform to run: every voxel at distance 0 from itself, or FAR
+        a.fill = ((obstacle_mask >> LA3DM_RAY_MISSING) & 1u) ? 0u : LA3DM_DF_FAR;
+    } else {
+        NtWork w;
+        DM_OK(nearest_reserve(dm, (size_t)g.total, true, w));
+        nearest_launch(dm, g, obstacle_mask, radius, w, w.index, w.d2);
+        a.index = w.index;
+        a.d2 = w.d2;
+    }
+    a.o_cls = o.cls;
+    a.o_voxel = o.voxel;
+    a.o_index = o.index;
+    a.o_d2 = o.d2;
+    hipLaunchKernelGGL(dm_nt_points, dim3(cdiv(n_points, 256)), dim3(256), 0, dm->ctx->stream, a);
+    DM_TRY(hipGetLastError());
+    DM_OK(s.download());
+    DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_nearest_points_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *d_points3, uint32_t n_points,
+                                       const float *d_pose12, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out *d_out,
+                                       la3dm_region_info *info) {
+    return nearest_points_query(dm, false, "la3dm_devmap_nearest_points_device", lo3, dims3, d_points3, n_points, d_pose12, obstacle_mask, radius,
+                                d_out, info);
+}
+
+int la3dm_devmap_nearest_points_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
+                                     const float *pose12, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out *out,
+                                     la3dm_region_info *info) {
+    return nearest_points_query(dm, true, "la3dm_devmap_nearest_points_host", lo3, dims3, points3, n_points, pose12, obstacle_mask, radius, out,
+                                info);
 }
 
 // ---- frontier of a region (devmap_frontier.h) -----------------------------------------------------------------

@@ -13,6 +13,7 @@
 //   Occupancy                          src/bgkoctomap/bgkoctree_node.cpp:15-44
 #include "bgkoctomap.h"
 #include "region_contract.h"
+#include "nearest_lines.h"
 #include "diff_block.h"
 #include "merge_block.h"
 #include "region_blocks.h"
@@ -1327,6 +1328,115 @@ void BGKOctoMap::distance_field(const float *lo3, const uint32_t *dims3, uint32_
         const bool far = f[v] > r2;
         if (out.d2) out.d2[v] = far ? LA3DM_DF_FAR : f[v];
         if (out.dist) out.dist[v] = far ? std::numeric_limits<float>::infinity() : sqrtf((float)f[v]) * res;
+    }
+}
+
+// ---- nearest and nearest_points: the feature transform of a region.  The host form below is the definition; the device
+// kernels (csrc/devmap_nearest.h) reproduce it exactly.  distance_field's three stages, each keeping its argmin with the
+// smaller coordinate on a tie (host/nearest_lines.h, where the tie-break argument stands); the last stage follows the
+// three offsets to the obstacle.
+namespace {
+// index and / or d2 (either may be null) of every voxel of a region with the classes cls
+void feature_transform(const std::vector<uint8_t> &cls, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius, uint32_t *index,
+                       uint32_t *d2) {
+    namespace nt = la3dm_nearest;
+    const size_t nx = dims3[0], ny = dims3[1], nz = dims3[2], n = nx * ny * nz;
+    std::vector<int16_t> az(n);
+    std::vector<uint32_t> ky(n);
+#pragma omp parallel
+    {
+        std::vector<uint8_t> obstacle(nz);
+#pragma omp for schedule(static)
+        for (size_t line = 0; line < nx * ny; ++line) {   // z
+            for (size_t k = 0; k < nz; ++k) obstacle[k] = (uint8_t)((obstacle_mask >> cls[line * nz + k]) & 1u);
+            nt::line_z(obstacle.data(), nz, radius, az.data() + line * nz);
+        }
+    }
+#pragma omp parallel for collapse(2) schedule(static)
+    for (size_t i = 0; i < nx; ++i)   // y: the lines (i, *, k)
+        for (size_t k = 0; k < nz; ++k) {
+            const int16_t *in = az.data() + i * ny * nz + k;
+            uint32_t *out = ky.data() + i * ny * nz + k;
+            nt::line_pass(
+                ny, radius, [&](size_t j) { return nt::offset_term(in[j * nz]); }, [&](size_t j, uint32_t key) { out[j * nz] = key; });
+        }
+    const uint32_t r2 = radius * radius;
+    const size_t S = ny * nz;
+#pragma omp parallel for schedule(static)
+    for (size_t c = 0; c < S; ++c) {   // x: the lines (*, j, k), and the chase
+        const size_t j = c / nz, k = c % nz;
+        nt::line_pass(
+            nx, radius, [&](size_t i) { return nt::key_sum(ky[i * S + c]); },
+            [&](size_t i, uint32_t key) {
+                const uint32_t sum = nt::key_sum(key);
+                const bool far = sum > r2;
+                if (d2) d2[i * S + c] = far ? LA3DM_DF_FAR : sum;
+                if (!index) return;
+                if (far) {
+                    index[i * S + c] = LA3DM_NEAREST_NONE;
+                    return;
+                }
+                const size_t i2 = (size_t)((ptrdiff_t)i + nt::key_offset(key));
+                const size_t j2 = (size_t)((ptrdiff_t)j + nt::key_offset(ky[i2 * S + c]));
+                const size_t k2 = (size_t)((ptrdiff_t)k + az[(i2 * ny + j2) * nz + k]);
+                index[i * S + c] = (uint32_t)((i2 * ny + j2) * nz + k2);
+            });
+    }
+}
+}  // namespace
+
+void BGKOctoMap::nearest(const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_out &out,
+                         la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_nearest_host(dmap, lo3, dims3, obstacle_mask, radius, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::nearest: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string refusal = la3dm_region::nearest_check(obstacle_mask, radius, 0);
+    if (!refusal.empty()) throw std::invalid_argument("BGKOctoMap::nearest: " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kNearest, out.index != nullptr || out.d2 != nullptr, "nearest", g0, inf);
+    if (info) *info = inf;
+    feature_transform(region_classes(*this, lo3, dims3), dims3, obstacle_mask, radius, out.index, out.d2);
+}
+
+// a loop over world_voxel — after score_voxel's transform where a pose is given — and two gathers
+void BGKOctoMap::nearest_points(const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points, const float *pose12,
+                                uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out &out, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_nearest_points_host(dmap, lo3, dims3, points3, n_points, pose12, obstacle_mask, radius, &out, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::nearest_points: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::nearest_points";
+    std::string refusal = la3dm_region::nearest_check(obstacle_mask, radius, n_points);
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kNearestPoints, true, "nearest_points", g0, inf);
+    refusal = la3dm_region::nearest_buffers(n_points, points3 != nullptr, true, out.cls || out.voxel || out.index || out.d2);
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    if (info) *info = inf;
+    if (n_points == 0) return;
+    const size_t n = (size_t)dims3[0] * dims3[1] * dims3[2];
+    std::vector<uint32_t> index(n), d2(n);
+    feature_transform(region_classes(*this, lo3, dims3), dims3, obstacle_mask, radius, index.data(), d2.data());
+    const int lim = 1 << (block_depth - 1);
+#pragma omp parallel for schedule(static)
+    for (uint32_t p = 0; p < n_points; ++p) {
+        const float *q = points3 + 3 * (size_t)p;
+        uint32_t f = 0;
+        uint32_t cls = pose12 ? la3dm_region::score_voxel(pose12, q[0], q[1], q[2], resolution, block_size, lim, g0, dims3, f)
+                              : la3dm_region::world_voxel(q, resolution, block_size, lim, g0, dims3, f);
+        const bool inside = cls == LA3DM_SCORE_HIT;
+        if (inside) cls = la3dm_region::score_class(d2[f]);
+        if (out.cls) out.cls[p] = (uint8_t)cls;
+        if (out.voxel) out.voxel[p] = inside ? f : LA3DM_NEAREST_NONE;
+        if (out.index) out.index[p] = inside ? index[f] : LA3DM_NEAREST_NONE;
+        if (out.d2) out.d2[p] = inside ? d2[f] : LA3DM_DF_FAR;
     }
 }
 

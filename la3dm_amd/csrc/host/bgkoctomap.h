@@ -482,6 +482,20 @@ public:
     void score_poses(const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points, const float *poses12,
                      uint32_t n_poses, uint32_t obstacle_mask, uint32_t radius, const la3dm_score_out &out,
                      la3dm_region_info *info = nullptr) const;
+    /// Which obstacle is the nearest (contract: include/la3dm_hip.h, la3dm_devmap_nearest_host): per voxel of box's region
+    /// out.index = the flat index of the nearest voxel of the region whose class is in obstacle_mask — the smallest flat
+    /// index among equals, LA3DM_NEAREST_NONE beyond `radius` (1 .. 255) voxels — and out.d2 = distance_field's d2; either
+    /// may be null, not both.  Bad arguments throw std::invalid_argument.  A device-resident map runs the query on the
+    /// device pool (no mirror refresh); a host-mode map runs distance_field's three stages with their argmins
+    /// (host/nearest_lines.h): that form is the definition, and both give the same integers.
+    void nearest(const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_out &out,
+                 la3dm_region_info *info = nullptr) const;
+    /// nearest per point of a cloud — the correspondences of an ICP step: every point of points3 is moved by pose12 (row-major
+    /// 3 x 4 [R | t], score_poses' transform; null: the points as they are, no arithmetic), its voxel resolved as search
+    /// resolves it; out.cls = score_poses' class of the point, out.voxel = the voxel's flat index, out.index = nearest's
+    /// index there, out.d2 = the squared distance (NONE / FAR where the contract says so).  Every array may be null, not all.
+    void nearest_points(const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points, const float *pose12,
+                        uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out &out, la3dm_region_info *info = nullptr) const;
     /// Cost and clearance of many candidate trajectories (contract: include/la3dm_hip.h, la3dm_devmap_score_paths_host):
     /// every path of ways3 (n_paths x n_way x 3 floats, world frame) is walked voxel by voxel from waypoint to waypoint
     /// through box's region against d2 = distance_field(lo, dims, obstacle_mask, max(1, clearance, soft_radius)); the walk

@@ -432,6 +432,23 @@ int la3dm_map_score_paths(const la3dm_map *m, const float *lo3, const uint32_t *
         return 0;)
 }
 
+int la3dm_map_nearest(const la3dm_map *m, const float *lo3, const uint32_t *dims3, uint32_t obstacle_mask, uint32_t radius,
+                      const la3dm_nearest_out *out, la3dm_region_info *info) {
+    GUARD(
+        const la3dm_nearest_out none = la3dm_nearest_out();   // (all null)
+        m->map->nearest(lo3, dims3, obstacle_mask, radius, out ? *out : none, info);
+        return 0;)
+}
+
+int la3dm_map_nearest_points(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
+                             const float *pose12, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out *out,
+                             la3dm_region_info *info) {
+    GUARD(
+        const la3dm_nearest_points_out none = la3dm_nearest_points_out();   // (all null)
+        m->map->nearest_points(lo3, dims3, points3, n_points, pose12, obstacle_mask, radius, out ? *out : none, info);
+        return 0;)
+}
+
 int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                     uint32_t pass_mask, uint32_t obstacle_mask, uint32_t clearance, uint32_t connectivity, uint32_t max_steps,
                     const uint32_t *targets, uint32_t n_targets, const la3dm_reach_out *out, la3dm_reach_stats *stats,

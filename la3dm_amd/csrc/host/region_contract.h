@@ -1,7 +1,7 @@
 // region_contract.h — what a valid region query is (include/la3dm_hip.h "Region"), once for the device library
 // (devmap.hip) and the host map (bgkoctomap.cpp): the limits of each query, their order, their texts and the anchor
 // arithmetic.  Host code, but for the inlines marked LA3DM_HD, which the device kernels compile as well (score_poses:
-// csrc/devmap_score.h; score_paths: csrc/devmap_paths.h).  A check answers with the text of the refusal, without the caller's prefix, or with an empty
+// csrc/devmap_score.h; score_paths: csrc/devmap_paths.h; nearest_points: csrc/devmap_nearest.h).  A check answers with the text of the refusal, without the caller's prefix, or with an empty
 // string; how a refusal is reported (an error code and a stored text, an exception) is the caller's business.
 #ifndef LA3DM_REGION_CONTRACT_H
 #define LA3DM_REGION_CONTRACT_H
@@ -175,11 +175,10 @@ LA3DM_HD inline float pose_axis(const float *row, float x, float y, float z) { r
 
 // The class of a (pose, point) pair up to the cost volume: LA3DM_SCORE_INVALID, LA3DM_SCORE_OUTSIDE, or LA3DM_SCORE_HIT
 // for a pair whose voxel lies in the region — f is then its flat index, and d2[f] decides between HIT, NEAR and FAR
-// (score_class).
-LA3DM_HD inline uint32_t score_voxel(const float *pose12, float x, float y, float z, float resolution, float block_size, int lim,
-                                     const uint32_t *g0, const uint32_t *dims, uint32_t &f) {
-    float w[3];
-    for (int c = 0; c < 3; ++c) w[c] = pose_axis(pose12 + 4 * c, x, y, z);
+// (score_class).  score_voxel is the transform followed by world_voxel, which takes the coordinate w in the map frame
+// (nearest_points without a pose starts there).
+LA3DM_HD inline uint32_t world_voxel(const float *w, float resolution, float block_size, int lim, const uint32_t *g0,
+                                     const uint32_t *dims, uint32_t &f) {
     for (int c = 0; c < 3; ++c)
         if (!axis_in_range(w[c], resolution)) return LA3DM_SCORE_INVALID;
     uint32_t at[3];
@@ -193,7 +192,35 @@ LA3DM_HD inline uint32_t score_voxel(const float *pose12, float x, float y, floa
     f = (at[0] * dims[1] + at[1]) * dims[2] + at[2];
     return LA3DM_SCORE_HIT;
 }
+LA3DM_HD inline uint32_t score_voxel(const float *pose12, float x, float y, float z, float resolution, float block_size, int lim,
+                                     const uint32_t *g0, const uint32_t *dims, uint32_t &f) {
+    float w[3];
+    for (int c = 0; c < 3; ++c) w[c] = pose_axis(pose12 + 4 * c, x, y, z);
+    return world_voxel(w, resolution, block_size, lim, g0, dims, f);
+}
 LA3DM_HD inline uint32_t score_class(uint32_t d2) { return d2 == 0 ? LA3DM_SCORE_HIT : (d2 != LA3DM_DF_FAR ? LA3DM_SCORE_NEAR : LA3DM_SCORE_FAR); }
+
+// ---- nearest and nearest_points (contract: include/la3dm_hip.h, la3dm_devmap_nearest_host) ----
+// nearest's limit, and its buffers as the region's last check; nearest_points' buffers follow the region's (nearest_buffers)
+constexpr Query kNearest = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, "out: index or d2 must not be NULL"};
+constexpr Query kNearestPoints = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, ""};
+
+// the checks of the two queries' own arguments, before the region's (nearest: n_points = 0)
+inline std::string nearest_check(uint32_t obstacle_mask, uint32_t radius, uint32_t n_points) {
+    if (obstacle_mask == 0 || (obstacle_mask & ~0x1Fu)) return "obstacle_mask must hold at least one of the bits 0x1F and no other";
+    if (radius == 0 || radius > LA3DM_NEAREST_MAX_RADIUS) return "radius must lie in [1, LA3DM_NEAREST_MAX_RADIUS (255)]";
+    if (n_points > LA3DM_SCORE_MAX_POINTS) return "n_points: more than LA3DM_SCORE_MAX_POINTS (2^20) points";
+    return "";
+}
+
+// nearest_points' checks that follow the region's: the buffers
+inline std::string nearest_buffers(uint32_t n_points, bool has_points, bool has_out, bool has_any) {
+    if (n_points == 0) return "";
+    if (!has_points) return "points3 is NULL";
+    if (!has_out) return "out is NULL";
+    if (!has_any) return "out: cls, voxel, index or d2 must not be NULL";
+    return "";
+}
 
 // words of one viewpoint's set
 inline uint32_t gain_words(uint64_t total) { return (uint32_t)((total + 31) / 32); }
