@@ -213,6 +213,10 @@ int la3dm_gp_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *scan, void *strea
  *
  *  - samples: every training sample in original order, (x, y, z, ray) with ray = -1 for a hit, else the index
  *    of its segment (bgklvoctomap.cpp:303-423 builds them); a ray's samples are contiguous, first = segment start.
+ *    PRECONDITION: along a ray every coordinate of its samples is monotone (non-decreasing or non-increasing, as stored in
+ *    fp32) — true of samples taken along a straight segment.  The samples of a ray inside a voxel's box are then one
+ *    contiguous run, and the kernel finds the run's first sample (the one that adds the ray's row) by looking at the ray's
+ *    first sample and at the previous sample only; samples that wander in and out of a box would add a row per entry.
  *  - sorted: the same samples bucketed on a grid of edge g aligned with the blocks (bucket = floor((v +
  *    block_size/2) / g), g = 4 * resolution for block_depth >= 3 else block_size), buckets x-fastest over
  *    [cell_min, cell_min + cell_dim), ascending original index inside a bucket; w = original index (int bits).
@@ -220,7 +224,8 @@ int la3dm_gp_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *scan, void *strea
  *  - blocks: centre, bucket coordinates of the block's lowest bucket, and dense per-node arrays of the
  *    FINEST layer only (8^(block_depth-1) nodes per block, octree index order): alpha, beta in/out; state in:
  *    LV code of the node (4 = pruned / not a base-resolution leaf: skipped); state out: LA3DM_LEAF_UPDATED |
- *    new state when update() ran, LA3DM_LV_HAS_INFO when the voxel's box held any sample. */
+ *    new state when update() ran, LA3DM_LV_HAS_INFO when the voxel's box held any sample.  Every state byte is rewritten:
+ *    a node that came in as 4 comes back as 0, like any node that was not updated and saw no sample (alpha, beta untouched). */
 #define LA3DM_LV_HAS_INFO 0x40u
 enum { LA3DM_LV_FREE = 0, LA3DM_LV_OCCUPIED = 1, LA3DM_LV_UNKNOWN = 2, LA3DM_LV_UNCERTAIN = 3, LA3DM_LV_PRUNED = 4 };
 typedef struct la3dm_lv_scan {

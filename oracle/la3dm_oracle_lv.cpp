@@ -16,7 +16,9 @@
 // LUT, leaf order, prune and block hashing are pinned against the reference's own compiled LV sources
 // (oracle/_ref/libla3dm_ref_lv.so = ref_harness.cpp -DLA3DM_REF_LV; golden tests/golden/ref_kat_lv.npz;
 // tests/test_oracle.py::test_lv_*_against_reference_kat).  The Eigen/PCL parts (kernel arithmetic, voxel grid) and
-// the R-tree gather order are restated here => **parity unpinned** for those.
+// the R-tree gather order are restated here => **parity unpinned** for those.  The voxel body (lv_voxel: box, rows,
+// distance, kernel, sums, gate, node) is checked against a float64 evaluation of the reference's formulas with a derived
+// bound on hand-built packed scans (orc_lv_packed_scan, tests/lv_f64_ref.py, tests/test_lv_f64_cpu.py).
 //
 // Row order.  The reference sums a voxel's kernel row in R-tree search order (then Eigen's GEMV
 // order) — both unpinned.  Restated order: the training points are bucketed on a grid of edge
@@ -368,6 +370,80 @@ inline bool in_box(V3 lo, V3 hi, V3 q) {  // closed, rtree.h:1519-1532
     return !(lo.x > q.x || q.x > hi.x || lo.y > q.y || q.y > hi.y || lo.z > q.z || q.z > hi.z);
 }
 
+// gather grid (see header): bucket edge g, bucket index = floor((v + block_size/2) / g) in double
+struct Grid {
+    double g, half;
+    int r;
+    explicit Grid(const Params &p)
+        : g(p.depth >= 3 ? 4.0 * (double)p.resolution : (double)p.block_size), half(0.5 * (double)p.block_size),
+          r((int)std::ceil((double)p.ell / g)) {}
+    int64_t cidx(float v) const { return (int64_t)std::floor(((double)v + half) / g); }
+};
+
+// One voxel of the leaf loop (bgklvoctomap.cpp:162-238), shared by the map path (insert_lv) and the packed-scan entry
+// (orc_lv_packed_scan): the candidates in the closed box c +- ell in gather order, one row per hit and one per ray at its
+// lowest-index sample in the box (a full search from the ray's first sample), the two sums in the current sum mode, the
+// gate and lv_update.  bucket(ix, iy, iz, begin, end) hands out the sample indices of a bucket, ascending, or false.
+// Returns 0 when the box holds no sample, else 1, + 2 when the node was updated.
+template <class BucketFn>
+int lv_voxel(const Params &p, const Training &T, const Grid &G, const V3 c, const BucketFn &bucket, std::vector<int> &cand,
+             Node &node, double &n_rows) {
+    const V3 hs{p.ell, p.ell, p.ell};
+    const V3 bl = c - hs, bh = c + hs;
+    const int r = G.r;
+    // candidates in box, in gather order
+    cand.clear();
+    const int64_t cx = G.cidx(c.x), cy = G.cidx(c.y), cz = G.cidx(c.z);
+    for (int64_t dz = -r; dz <= r; ++dz)
+        for (int64_t dy = -r; dy <= r; ++dy)
+            for (int64_t dx = -r; dx <= r; ++dx) {
+                const int *b0 = nullptr, *b1 = nullptr;
+                if (!bucket(cx + dx, cy + dy, cz + dz, b0, b1)) continue;
+                for (const int *it = b0; it != b1; ++it)
+                    if (in_box(bl, bh, T.xy[*it])) cand.push_back(*it);
+            }
+    if (cand.empty()) return 0;  // :168-175
+    // one row per hit, one row per ray at its lowest-index sample in the box (:176-205)
+    // sum mode 1 (orc_set_sum_mode, la3dm_oracle.cpp): the same fp32 kv and kv * y, summed in double and rounded to
+    // fp32 once per voxel — the value the fp32 chains approximate, whatever the order of the rows
+    const bool sum64 = g_orc_sum_mode == 1;
+    double dybar = 0.0, dkbar = 0.0;
+    float ybar = 0.0f, kbar = 0.0f;
+    for (int i : cand) {
+        const int ray = T.ray_idx[i];
+        float kv, y;
+        if (ray < 0) {
+            kv = cov_sparse_line(seg_dist(c, T.xy[i], T.xy[i]), p.ell, p.sf2);
+            y = 1.0f;
+        } else {
+            bool first = true;
+            for (int q = T.ray_base[ray]; q < i && first; ++q)
+                if (in_box(bl, bh, T.xy[q])) first = false;
+            if (!first) continue;
+            kv = cov_sparse_line(seg_dist(c, T.ray0[ray], T.ray1[ray]), p.ell, p.sf2);
+            y = 0.0f;
+        }
+        if (sum64) {
+            const float ky = kv * y;
+            dybar += (double)ky;
+            dkbar += (double)kv;
+        } else {
+            ybar += kv * y;
+            kbar += kv;
+        }
+        n_rows += 1;
+    }
+    if (sum64) {
+        ybar = (float)dybar;
+        kbar = (float)dkbar;
+    }
+    if (kbar > 0.001f) {  // :236-238
+        lv_update(p, node, ybar, kbar);
+        return 3;
+    }
+    return 1;
+}
+
 void insert_lv(Map &m, const std::vector<V3> &cloud, V3 origin, float ds_resolution, float free_res, float max_range) {
     const Params &p = m.p;
     Training T;
@@ -391,17 +467,19 @@ void insert_lv(Map &m, const std::vector<V3> &cloud, V3 origin, float ds_resolut
             for (float z = lo.z - bs; z <= hi.z + 2 * bs; z += bs) blocks.push_back(block_key(p, x, y, z));
     m.st.n_bbox_blocks = (double)blocks.size();
 
-    // gather grid (see header): bucket edge g, bucket index = floor((v + block_size/2) / g) in double
-    const double g = p.depth >= 3 ? 4.0 * (double)p.resolution : (double)p.block_size;
-    const double half = 0.5 * (double)p.block_size;
-    const int r = (int)std::ceil((double)p.ell / g);
-    auto cidx = [&](float v) { return (int64_t)std::floor(((double)v + half) / g); };
+    const Grid G(p);
     auto ckey = [](int64_t ix, int64_t iy, int64_t iz) { return ((ix + 1048576) << 42) | ((iy + 1048576) << 21) | (iz + 1048576); };
     std::unordered_map<int64_t, std::vector<int>> bucket;
-    for (size_t i = 0; i < T.xy.size(); ++i) bucket[ckey(cidx(T.xy[i].x), cidx(T.xy[i].y), cidx(T.xy[i].z))].push_back((int)i);
+    for (size_t i = 0; i < T.xy.size(); ++i) bucket[ckey(G.cidx(T.xy[i].x), G.cidx(T.xy[i].y), G.cidx(T.xy[i].z))].push_back((int)i);
+    auto bucket_at = [&](int64_t ix, int64_t iy, int64_t iz, const int *&b0, const int *&b1) {
+        auto bt = bucket.find(ckey(ix, iy, iz));
+        if (bt == bucket.end()) return false;
+        b0 = bt->second.data();
+        b1 = b0 + bt->second.size();
+        return true;
+    };
 
     std::vector<int64_t> test_blocks;
-    const V3 hs{p.ell, p.ell, p.ell};
     // Blocks are independent (a voxel reads the training set and writes its own node): the OpenMP build runs one task
     // per DISTINCT block key; a key the float-stepped bbox loop lists twice is visited twice by the same task, in
     // order, as the reference's serial loop does.
@@ -443,59 +521,10 @@ void insert_lv(Map &m, const std::vector<V3> &cloud, V3 origin, float ds_resolut
             if (size > p.resolution) continue;  // :157-160
             const V3 &o = m.lut[d][idx];
             const V3 c{o.x + block->center.x, o.y + block->center.y, o.z + block->center.z};
-            const V3 bl = c - hs, bh = c + hs;
             n_visited += 1;
-            // candidates in box, in gather order
-            cand.clear();
-            const int64_t cx = cidx(c.x), cy = cidx(c.y), cz = cidx(c.z);
-            for (int64_t dz = -r; dz <= r; ++dz)
-                for (int64_t dy = -r; dy <= r; ++dy)
-                    for (int64_t dx = -r; dx <= r; ++dx) {
-                        auto bt = bucket.find(ckey(cx + dx, cy + dy, cz + dz));
-                        if (bt == bucket.end()) continue;
-                        for (int i : bt->second)
-                            if (in_box(bl, bh, T.xy[i])) cand.push_back(i);
-                    }
-            if (cand.empty()) continue;  // :168-175
-            // one row per hit, one row per ray at its lowest-index sample in the box (:176-205)
-            // sum mode 1 (orc_set_sum_mode, la3dm_oracle.cpp): the same fp32 kv and kv * y, summed in double and rounded to
-            // fp32 once per voxel — the value the fp32 chains approximate, whatever the order of the rows
-            const bool sum64 = g_orc_sum_mode == 1;
-            double dybar = 0.0, dkbar = 0.0;
-            float ybar = 0.0f, kbar = 0.0f;
-            for (int i : cand) {
-                const int ray = T.ray_idx[i];
-                float kv, y;
-                if (ray < 0) {
-                    kv = cov_sparse_line(seg_dist(c, T.xy[i], T.xy[i]), p.ell, p.sf2);
-                    y = 1.0f;
-                } else {
-                    bool first = true;
-                    for (int q = T.ray_base[ray]; q < i && first; ++q)
-                        if (in_box(bl, bh, T.xy[q])) first = false;
-                    if (!first) continue;
-                    kv = cov_sparse_line(seg_dist(c, T.ray0[ray], T.ray1[ray]), p.ell, p.sf2);
-                    y = 0.0f;
-                }
-                if (sum64) {
-                    const float ky = kv * y;
-                    dybar += (double)ky;
-                    dkbar += (double)kv;
-                } else {
-                    ybar += kv * y;
-                    kbar += kv;
-                }
-                n_rows += 1;
-            }
-            if (sum64) {
-                ybar = (float)dybar;
-                kbar = (float)dkbar;
-            }
-            Node &node = block->layer[d][idx];
-            if (kbar > 0.001f) {  // :236-238
-                lv_update(p, node, ybar, kbar);
-                n_updates += 1;
-            }
+            const int got = lv_voxel(p, T, G, c, bucket_at, cand, block->layer[d][idx], n_rows);
+            if (got == 0) continue;  // :168-175
+            if (got & 2) n_updates += 1;
             has_info = true;
         }
         info[bi] = has_info;
@@ -537,6 +566,60 @@ void orc_lv_insert_pointcloud(void *h, const float *xyz, int64_t n, const float 
     insert_lv(*m, cloud, V3{origin[0], origin[1], origin[2]}, ds_resolution, free_res, max_range);
 }
 void orc_lv_stats(void *h, double *out11) { std::memcpy(out11, &((Map *)h)->st, sizeof(Stats)); }
+
+// A packed scan (the arrays of la3dm_lv_scan, include/la3dm_hip.h) evaluated by lv_voxel, the map path's voxel body: every
+// node of the finest layer of every packed block whose state is not PRUNED, at lut + centre; buckets from cell_off and the
+// original indices in sorted's w, the voxel's own bucket from its centre as in the map path (blk_cell0 is not read).
+// alpha / beta in/out; state out as the contract words it: 0x40 when the box held a sample, 0x80 | state after update().
+void orc_lv_packed_scan(void *h, const float *samples4, int64_t n_samples, const float *sorted4, const float *rays8, int64_t n_rays,
+                        const uint32_t *cell_off, const int32_t *cell_min, const int32_t *cell_dim, int64_t n_blk,
+                        const float *blk_center, float *alpha, float *beta, uint8_t *state) {
+    Map *m = (Map *)h;
+    const Params &p = m->p;
+    Training T;
+    for (int64_t i = 0; i < n_samples; ++i) {
+        T.xy.push_back(V3{samples4[4 * i], samples4[4 * i + 1], samples4[4 * i + 2]});
+        T.ray_idx.push_back((int)samples4[4 * i + 3]);
+    }
+    for (int64_t i = 0; i < n_rays; ++i) {
+        int32_t first;
+        std::memcpy(&first, rays8 + 8 * i + 3, 4);
+        T.ray_base.push_back(first);
+        T.ray0.push_back(V3{rays8[8 * i], rays8[8 * i + 1], rays8[8 * i + 2]});
+        T.ray1.push_back(V3{rays8[8 * i + 4], rays8[8 * i + 5], rays8[8 * i + 6]});
+    }
+    const size_t ncell = (size_t)cell_dim[0] * cell_dim[1] * cell_dim[2];
+    std::vector<int> order(cell_off[ncell]);
+    for (size_t j = 0; j < order.size(); ++j) std::memcpy(&order[j], sorted4 + 4 * j + 3, 4);
+    auto bucket_at = [&](int64_t ix, int64_t iy, int64_t iz, const int *&b0, const int *&b1) {
+        const int64_t x = ix - cell_min[0], y = iy - cell_min[1], z = iz - cell_min[2];
+        if (x < 0 || y < 0 || z < 0 || x >= cell_dim[0] || y >= cell_dim[1] || z >= cell_dim[2]) return false;
+        const size_t cell = ((size_t)z * cell_dim[1] + (size_t)y) * cell_dim[0] + (size_t)x;
+        b0 = order.data() + cell_off[cell];
+        b1 = order.data() + cell_off[cell + 1];
+        return b0 != b1;
+    };
+    const Grid G(p);
+    const int d = p.depth - 1;
+    const size_t npb = m->lut[d].size();
+    std::vector<int> cand;
+    double n_rows = 0;
+    for (int64_t b = 0; b < n_blk; ++b)
+        for (size_t i = 0; i < npb; ++i) {
+            const size_t ni = (size_t)b * npb + i;
+            if (state[ni] == LV_PRUNED) {
+                state[ni] = 0;
+                continue;
+            }
+            const V3 &o = m->lut[d][i];
+            const V3 c{o.x + blk_center[3 * b], o.y + blk_center[3 * b + 1], o.z + blk_center[3 * b + 2]};
+            Node node{0, alpha[ni], beta[ni], state[ni]};
+            const int got = lv_voxel(p, T, G, c, bucket_at, cand, node, n_rows);
+            alpha[ni] = node.A;
+            beta[ni] = node.B;
+            state[ni] = (uint8_t)((got ? 0x40 : 0) | ((got & 2) ? 0x80 | node.state : 0));
+        }
+}
 
 // training data of one scan: samples (x, y, z, ray index or -1) and segments (6 floats)
 int64_t orc_lv_training_data(void *h, const float *xyz, int64_t n, const float *origin, float ds_resolution, float free_res,

@@ -51,6 +51,8 @@ def _load(name):
     lib.orc_lv_map_destroy.argtypes = [C.c_void_p]
     lib.orc_lv_insert_pointcloud.argtypes = [C.c_void_p, f32p, C.c_int64, f32p, C.c_float, C.c_float, C.c_float]
     lib.orc_lv_stats.argtypes = [C.c_void_p, f64p]
+    lib.orc_lv_packed_scan.argtypes = [C.c_void_p, f32p, C.c_int64, f32p, f32p, C.c_int64, np.ctypeslib.ndpointer(np.uint32, flags="C_CONTIGUOUS"),
+                                       i32p, i32p, C.c_int64, f32p, f32p, f32p, u8p]
     lib.orc_lv_training_data.restype = C.c_int64
     lib.orc_lv_training_data.argtypes = [C.c_void_p, f32p, C.c_int64, f32p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]
@@ -393,6 +395,26 @@ class OracleLVMap:
         self.L.orc_lv_training_data(self.h, xyz, xyz.shape[0], origin, ds_resolution, free_res, max_range,
                                     xy.ctypes.data, n, rays.ctypes.data, nr.value, C.byref(nr))
         return xy, rays
+
+    def packed_scan(self, samples, sorted_, rays8, cell_off, cell_min, cell_dim, blk_center, alpha, beta, state):
+        """A packed scan (the arrays of la3dm_lv_scan) through the map path's voxel body, in the current sum and trig modes:
+        (alpha, beta, state byte) of every node of the finest layer; the arguments are left unchanged"""
+        c = np.ascontiguousarray
+        samples, sorted_, rays8 = (c(x, np.float32).reshape(-1, k) for x, k in ((samples, 4), (sorted_, 4), (rays8, 8)))
+        ctr = c(blk_center, np.float32).reshape(-1, 3)
+        a, b, st = np.array(alpha, np.float32), np.array(beta, np.float32), np.array(state, np.uint8)
+        self.L.orc_lv_packed_scan(self.h, samples, len(samples), sorted_, rays8, len(rays8), c(cell_off, np.uint32),
+                                  c(cell_min, np.int32), c(cell_dim, np.int32), len(ctr), ctr, a, b, st)
+        return a, b, st
+
+    def lut(self, block_depth):
+        """Block::key_loc_map, depth-major, as [sum 8^d, 3]"""
+        out, o = [], np.zeros(3, np.float32)
+        for d in range(block_depth):
+            for i in range(8 ** d):
+                assert self.L.orc_lv_lut(self.h, d, i, o)
+                out.append(o.copy())
+        return np.ascontiguousarray(out, np.float32)
 
     def leaves(self, all_blocks=False):
         n = self.L.orc_lv_dump_leaves(self.h, int(all_blocks), None, None, None, None, None, None, None, None, 0)
