@@ -1292,6 +1292,81 @@ int la3dm_devmap_clusters_host(la3dm_devmap *dm, const float *lo3, const uint32_
 int la3dm_devmap_clusters_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
                                  const la3dm_clusters_out *d_out, uint32_t *n_found, la3dm_clusters_stats *stats,
                                  la3dm_region_info *info);
+/* Footing: where a ground robot can stand in a region of the map — the voxels with ground directly below, room for the
+ * body above, and a footprint round them that is carried, not blocked, and climbable — as an ordered list and per column.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; k grows
+ *     along +z of the map frame.
+ *   Classes.  cls(g) is what box would report for lattice voxel g, inside or outside the region: FREE 0, OCCUPIED 1,
+ *     UNKNOWN 2, MISSING 3, a BGK-LV map's UNCERTAIN 4.  Classes outside the region are read from the map, as frontier
+ *     reads its one-voxel halo: the answer for a voxel does not depend on where the region's faces are.
+ *   Parameters (la3dm_footing_params).  support_mask and clear_mask hold the bits of stop_mask; headroom h, radius r,
+ *     step s, min_support c.
+ *   Definition.  ez = (0, 0, 1); disc = {(di, dj) : 0 < di^2 + dj^2 <= r^2}, N = |disc| (N = 0 for r = 0).
+ *     stand(g) <=> cls(g - ez) in support_mask and cls(g + t ez) in clear_mask for every t in [0, h): ground below, and
+ *       room for the body.
+ *     near(g)  <=> stand(g + dk ez) for some |dk| <= s: there is ground within a climbable height of g.
+ *     body(g)  <=> cls(g + t ez) in clear_mask for every t in [s, h): nothing in the body's way above the height the
+ *       robot can climb over.
+ *     foot(v), v in the region, <=> stand(v); body(v + (di, dj, 0)) for every (di, dj) in disc; and
+ *       #{(di, dj) in disc : near(v + (di, dj, 0))} >= c.
+ *     A cylinder of radius r and height h with a ground clearance of s voxels that stands at v hits nothing and has
+ *     ground under at least c of its N footprint cells.  c = N is the strict footprint, a smaller c tolerates the holes of
+ *     a sparsely observed floor, c = 0 asks only for an unobstructed body.
+ *   Outputs.  *n_found = the number of foot voxels, whatever cap is.  out->index[cap]: the flat indices of the first
+ *     min(n, cap) foot voxels in ascending order; entries past them are not written.  Dense, per column i * ny + j, and
+ *     independent of cap: out->levels (uint32) = the foot voxels of the column, out->lowest / out->highest (int32) = their
+ *     smallest / largest k, -1 where there are none.  cap = 0 with out NULL, or with only dense arrays set, counts.
+ *     stats (a host struct, may be NULL): n_stand = the voxels of the region with stand, n_body = those with stand and the
+ *     body condition, n_foot, disc_cells = N.  On an empty map n = 0, levels = 0, lowest = highest = -1.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written, nothing reserved), in this
+ *     order: a NULL params; a mask that is 0 or has bits above 0x1F; masks that overlap; headroom outside [1,
+ *     LA3DM_FOOTING_MAX_HEADROOM]; radius above LA3DM_FOOTING_MAX_RADIUS; step above LA3DM_FOOTING_MAX_STEP or step >=
+ *     headroom; min_support > N; cap > 0 without out->index; what box refuses for lo and dims; a padded box that is too
+ *     large or leaves the block-field range — the padded box (nx + 2r, ny + 2r, nz + h + 2s) extends r in x and y, 1 + s
+ *     below and h - 1 + s above; it is refused when it holds more than LA3DM_FOOTING_MAX_CELLS voxels or when its block
+ *     fields leave [0, 2^20); last a NULL n_found.
+ *   Integer arithmetic on classes throughout: the results equal the host form (BGKOctoMap::footing on a host-mode map,
+ *     host/footing_cells.h over the classes of the padded box) exactly.
+ *   Device form (csrc/devmap_footing.h): bit streams over the padded box, 32 voxels per word with k fastest — one pool
+ *     probe per padded voxel gives the support and the clear stream, a word pass derives stand, near and body from shifted
+ *     windows, a second one ANDs the body windows over the disc and counts the near windows in a bit-sliced counter for
+ *     the words that hold a stand bit, the map's scan and an emit kernel give the list, one lane per column the dense
+ *     arrays.  No atomic is used.  Working storage: seven words per 32 padded voxels — 7/8 byte per padded voxel — and
+ *     24 KB of partial counts, in a grow-only arena of the devmap (released with it). */
+#define LA3DM_FOOTING_MAX_CELLS    (1u << 28)
+#define LA3DM_FOOTING_MAX_HEADROOM 32
+#define LA3DM_FOOTING_MAX_RADIUS   8
+#define LA3DM_FOOTING_MAX_STEP     4
+typedef struct la3dm_footing_params {
+    uint32_t support_mask;   /* classes that carry: the voxel below */
+    uint32_t clear_mask;     /* classes the body may occupy */
+    uint32_t headroom;       /* h: voxels of free height, 1 .. LA3DM_FOOTING_MAX_HEADROOM */
+    uint32_t radius;         /* r: footprint radius in voxels, 0 .. LA3DM_FOOTING_MAX_RADIUS */
+    uint32_t step;           /* s: climbable height in voxels, 0 .. LA3DM_FOOTING_MAX_STEP, < headroom */
+    uint32_t min_support;    /* c: footprint cells that must be carried, 0 .. N */
+} la3dm_footing_params;
+typedef struct la3dm_footing_out {
+    uint32_t *index;      /* [cap] or NULL */
+    uint32_t *levels;     /* [nx ny] or NULL, independent of cap */
+    int32_t  *lowest;     /* [nx ny] or NULL */
+    int32_t  *highest;    /* [nx ny] or NULL */
+} la3dm_footing_out;
+typedef struct la3dm_footing_stats {
+    uint32_t n_stand;      /* voxels of the region with stand */
+    uint32_t n_body;       /* ... and the body condition over the disc */
+    uint32_t n_foot;       /* foot voxels: n */
+    uint32_t disc_cells;   /* N */
+} la3dm_footing_stats;
+/* host pointers: the launches, download of min(*n_found, cap) entries and the dense arrays, synchronise — on the map's
+ * stream */
+int la3dm_devmap_footing_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params,
+                              uint64_t cap, const la3dm_footing_out *out, uint64_t *n_found, la3dm_footing_stats *stats,
+                              la3dm_region_info *info);
+/* device pointers (out's arrays already in HBM on the map's device, 4-byte aligned; lo3, dims3, params, n_found, stats
+ * and info stay host-side); returns when the results are complete */
+int la3dm_devmap_footing_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params,
+                                uint64_t cap, const la3dm_footing_out *d_out, uint64_t *n_found, la3dm_footing_stats *stats,
+                                la3dm_region_info *info);
 /* Leaf export =the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

@@ -182,6 +182,17 @@ int la3dm_map_nearest(const la3dm_map *m, const float *lo3, const uint32_t *dims
 int la3dm_map_nearest_points(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *points3, uint32_t n_points,
                              const float *pose12, uint32_t obstacle_mask, uint32_t radius, const la3dm_nearest_points_out *out,
                              la3dm_region_info *info);
+/* BGKOctoMap::footing: where a ground robot can stand.  The voxels of box's region with a class of params->support_mask
+ * directly below, params->headroom voxels of params->clear_mask classes from the voxel upwards, and a footprint of
+ * params->radius voxels round them that is not blocked above params->step voxels and has ground within params->step
+ * voxels of height under at least params->min_support of its cells.  *n_found = their number; out->index = the flat
+ * indices of the first min(*n_found, cap) in ascending order; out->levels / lowest / highest (dense, per column, optional)
+ * = the foot voxels of the column and their smallest / largest k (-1: none); stats (may be NULL) = the voxels that pass
+ * each condition and the cells of the footprint.  cap = 0 only counts.  Contract, limits and refusals: include/la3dm_hip.h
+ * (la3dm_devmap_footing_host).  Device-resident maps run the query on the device pool without a mirror refresh,
+ * host-mode maps on the CPU; the results are identical. */
+int la3dm_map_footing(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params, uint64_t cap,
+                      const la3dm_footing_out *out, uint64_t *n_found, la3dm_footing_stats *stats, la3dm_region_info *info);
 /* BGKOctoMap::score_paths: cost and clearance of many candidate trajectories.  Every path of ways3 (n_paths x n_way x 3
  * floats, world frame; a shorter path repeats its last waypoint) is walked voxel by voxel through box's region against d2 =
  * distance_field(lo, dims, obstacle_mask, max(1, clearance, soft_radius)); out->cost (mandatory) [n_paths] = travel's cost

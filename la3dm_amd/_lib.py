@@ -113,6 +113,18 @@ class NearestPointsOut(C.Structure):   # la3dm_nearest_points_out
     _fields_ = [(k, C.c_void_p) for k in ("cls", "voxel", "index", "d2")]
 
 
+class FootingParams(C.Structure):  # la3dm_footing_params
+    _fields_ = [(k, C.c_uint32) for k in ("support_mask", "clear_mask", "headroom", "radius", "step", "min_support")]
+
+
+class FootingOut(C.Structure):   # la3dm_footing_out
+    _fields_ = [(k, C.c_void_p) for k in ("index", "levels", "lowest", "highest")]
+
+
+class FootingStats(_Stats):   # la3dm_footing_stats
+    _fields_ = [(k, C.c_uint32) for k in ("n_stand", "n_body", "n_foot", "disc_cells")]
+
+
 class PathsParams(C.Structure):  # la3dm_paths_params
     _fields_ = [("obstacle_mask", C.c_uint32), ("clearance", C.c_uint32), ("soft_radius", C.c_uint32), ("penalty", C.c_uint32),
                 ("move_cost", C.c_uint32 * 3), ("max_steps", C.c_uint32)]
@@ -229,6 +241,8 @@ QUERY_DIFFERS = {
 # what follows the handle
 _NEAREST = [vp, vp, u32, u32, P(NearestOut), _INFO]
 _NEAREST_POINTS = [vp, vp, vp, u32, vp, u32, u32, P(NearestPointsOut), _INFO]
+# ... and so has footing
+_FOOTING = [vp, vp, P(FootingParams), u64, P(FootingOut), P(u64), P(FootingStats), _INFO]
 
 
 def _query_entries(of_map):
@@ -279,6 +293,8 @@ HIP_API = {
     "la3dm_devmap_nearest_device": (cint, [vp] + _NEAREST),
     "la3dm_devmap_nearest_points_host": (cint, [vp] + _NEAREST_POINTS),
     "la3dm_devmap_nearest_points_device": (cint, [vp] + _NEAREST_POINTS),
+    "la3dm_devmap_footing_host": (cint, [vp] + _FOOTING),
+    "la3dm_devmap_footing_device": (cint, [vp] + _FOOTING),
     **_query_entries(of_map=False),
 }
 
@@ -339,6 +355,7 @@ MAP_API = {
     "la3dm_map_evict_file": (cint, [vp, C.c_char_p, vp, vp, cint, P(EraseStats)]),
     "la3dm_map_nearest": (cint, [vp] + _NEAREST),
     "la3dm_map_nearest_points": (cint, [vp] + _NEAREST_POINTS),
+    "la3dm_map_footing": (cint, [vp] + _FOOTING),
     **_query_entries(of_map=True),
 }
 HIP_SYMBOLS = list(HIP_API)

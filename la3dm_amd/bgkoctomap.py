@@ -23,6 +23,7 @@ GAIN_MAX_CELLS = GAIN_MAX_RAYS = GAIN_MAX_WORDS = 1 << 28   # LA3DM_GAIN_MAX_*: 
 SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_RADIUS = 1 << 28, 1 << 20, 1 << 20, 1 << 32, 255   # LA3DM_SCORE_MAX_*
 SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID = range(5)   # LA3DM_SCORE_*: the columns of score_poses' counts
 NEAREST_NONE, NEAREST_MAX_RADIUS = 0xFFFFFFFF, 255   # LA3DM_NEAREST_*: nearest found no obstacle within the radius; the largest radius
+FOOTING_MAX_CELLS, FOOTING_MAX_HEADROOM, FOOTING_MAX_RADIUS, FOOTING_MAX_STEP = 1 << 28, 32, 8, 4   # LA3DM_FOOTING_MAX_*
 PATH_BLOCKED, PATH_LEFT, PATH_TRUNCATED, PATH_INVALID = 1, 2, 4, 8   # LA3DM_PATH_*: the bits of score_paths' flags
 PATH_NONE = 0xFFFFFFFF              # LA3DM_PATH_NONE: score_paths' stop of a walk that did not stop
 PATHS_MAX_STEPS, PATHS_MAX_WAY, PATHS_MAX_PATHS, PATHS_MAX_WAYPOINTS = 1 << 20, 1024, 1 << 20, 1 << 26   # LA3DM_PATHS_MAX_*
@@ -516,6 +517,64 @@ class BGKOctoMap:
         out = {k: np.empty(n if ok else 1, t) for k, t in self._NEAREST_POINTS_FIELDS.items() if k in fields}
         out.update(self._region_call(self._M.la3dm_map_nearest_points, lo3, d3, _addr(pts), n, _addr(T), mask, int(radius),
                                      C.byref(_out(_lib.NearestPointsOut, out))))
+        return out
+
+    _FOOTING_FIELDS = dict(index=np.uint32, levels=np.uint32, lowest=np.int32, highest=np.int32)
+
+    def footing(self, lo, dims, support=("occupied",), clear=("free",), headroom=2, radius=0, step=0, min_support=None,
+                fields=("index",), cap=None):
+        """Where a ground robot can stand in the region of box(lo, dims), as an ordered list and per column.  A voxel v is a
+        foot voxel when the voxel directly below it has a class in `support`, the `headroom` voxels from v upwards have
+        classes in `clear` (v stands), every cell of the disc of `radius` voxels round v is clear from `step` voxels above
+        v's height up to the headroom (the body hits nothing it cannot climb over), and at least `min_support` cells of
+        that disc have a standing place within `step` voxels of v's height (the footprint is carried).  support / clear:
+        names out of free / occupied / unknown / missing (/ uncertain on a BGK-LV map) or an integer bit mask, as
+        raycast_many's `stop`; they must not overlap.  headroom 1 .. 32, radius 0 .. 8, step 0 .. 4 and below headroom;
+        min_support=None asks for every cell of the disc, footprint_cells(radius), a smaller value tolerates holes in a
+        sparsely observed floor, 0 asks only for an unobstructed body.  Classes outside the region are read from the map:
+        the answer for a voxel does not depend on where the region's faces are.  Returns n = the number of foot voxels and,
+        as `fields` names them, index (uint32) = their flat indices (i * ny + j) * nz + k in ascending order — what
+        clusters(members=...) takes —, levels (uint32, shape (nx, ny)) = the foot voxels per column, lowest / highest
+        (int32) = their smallest / largest k, -1 where there is none; n_stand, n_body, n_foot, disc_cells = the voxels that
+        pass each condition and the cells of the disc; plus origin, block_key, cell as box() returns them.  cap=None counts
+        first and then fills exactly n entries; an integer cap fills the first min(n, cap) and n is still the total.  At
+        most 2^28 voxels in the padded box (nx + 2 radius, ny + 2 radius, nz + headroom + 2 step).  A device-resident map
+        runs the query on the device pool (no host mirror refresh); a host-mode map runs it on the CPU, with identical
+        results."""
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: True)
+        fields = _want("footing", fields, self._FOOTING_FIELDS)
+        masks = [_class_mask(support), _class_mask(clear)]
+        if min_support is None:
+            min_support = footprint_cells(radius) if 0 <= int(radius) <= FOOTING_MAX_RADIUS else 0
+        _fit("footing: support, clear, headroom, radius, step and min_support must fit 32 bits", masks + [headroom, radius, step, min_support])
+        if cap is not None:
+            _fit("footing: cap must fit 64 bits", [cap], bits=64)
+        ok = ok and (d[0] + 2 * int(radius)) * (d[1] + 2 * int(radius)) * (d[2] + int(headroom) + 2 * int(step)) <= FOOTING_MAX_CELLS
+        params = _lib.FootingParams(masks[0], masks[1], int(headroom), int(radius), int(step), int(min_support))
+        found, stats = C.c_uint64(0), _lib.FootingStats()
+        region = {}
+
+        def call(k, arrays):
+            o = _out(_lib.FootingOut, arrays, null_empty=("index",))
+            region.update(self._region_call(self._M.la3dm_map_footing, lo3, d3, C.byref(params), k, C.byref(o) if arrays else None,
+                                            C.byref(found), C.byref(stats)))
+            return int(found.value)
+
+        out = {k: np.empty((d[0], d[1]) if ok else (1,), t) for k, t in self._FOOTING_FIELDS.items() if k != "index" and k in fields}
+        if cap is None:   # the two-call protocol: count (the dense arrays come with this call), then fill exactly n
+            k = call(0, out)
+            filled = {}
+        else:
+            k = min(int(cap), cells if ok else 1)
+            filled = dict(out)
+        filled.update(index=np.empty(k, np.uint32))
+        total = k
+        if cap is not None or (k and "index" in fields):
+            total = call(k, filled)
+        if "index" in fields:
+            out["index"] = filled["index"][:min(total, k)]
+        out.update(n=total, **stats.as_dict())
+        out.update(region)
         return out
 
     _PATHS_FIELDS = dict(cost=np.uint64, steps=np.uint32, stop=np.uint32, min_d2=np.uint32, ways=np.uint32, flags=np.uint8)
@@ -1102,6 +1161,14 @@ def poses_xyz_yaw(center, dxyz_dyaw):
         c, s = math.cos(dyaw), math.sin(dyaw)
         out[i] = [[c, -s, 0.0, (cx + dx) - (c * cx - s * cy)], [s, c, 0.0, (cy + dy) - (s * cx + c * cy)], [0.0, 0.0, 1.0, dz]]
     return out
+
+
+def footprint_cells(radius):
+    """N of footing: the cells (di, dj) of a disc of `radius` voxels without its centre, 0 < di^2 + dj^2 <= radius^2"""
+    r = int(radius)
+    if r < 0:
+        raise ValueError("footprint_cells: radius must be >= 0")
+    return sum(1 for di in range(-r, r + 1) for dj in range(-r, r + 1) if 0 < di * di + dj * dj <= r * r)
 
 
 def follow_parents(parent, dims, index):

@@ -30,6 +30,7 @@
 #include "devmap_region.h"
 #include "devmap_distance.h"
 #include "devmap_frontier.h"
+#include "devmap_footing.h"
 #include "devmap_gain.h"
 #include "devmap_score.h"
 #include "devmap_nearest.h"
@@ -92,6 +93,7 @@ struct la3dm_devmap {
     Arena train, grid, axis_tab, m_code, q_out;
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
+    Arena ft_work;                // footing: 7/8 byte per padded voxel (five bit streams, popcounts, prefixes: devmap_footing.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
     Arena score_work;             // score_poses: d2 (4 bytes per voxel), then the chunks' partial records (devmap_score.h); score_paths: d2 (devmap_paths.h)
     Arena nt_work;                // nearest: the y keys (4 bytes per voxel), the z offsets (2), the obstacle bits; nearest_points: index and d2 as well (devmap_nearest.h)
@@ -733,7 +735,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->ft_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3526,6 +3528,123 @@ int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_
                                const la3dm_frontier_out *out, uint64_t *n_found, la3dm_region_info *info) {
     return frontier_query(dm, true, "la3dm_devmap_frontier_host", lo3, dims3, open_mask, unknown_mask, connectivity, min_neighbours, cap, out,
                           n_found, info);
+}
+
+// ---- footing of a region (devmap_footing.h) --------------------------------------------------------------------
+
+// Bits, derive, foot, scan, (cap > 0) emit and (a dense array) columns on the map's stream; o's arrays are device memory.
+// d_stats: where the launches leave the kFtWaves partial counts of n_stand, n_body and n_foot (working storage).
+static int footing_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_footing_params &p, uint64_t cap, const la3dm_footing_out &o,
+                          const uint32_t *&d_stats) {
+    hipStream_t st = dm->ctx->stream;
+    RegionArgs a = region_args(dm, g);
+    a.g0[0] = g.g0[0] - p.radius;   // (footing_query's region check: g0 >= the pad below)
+    a.g0[1] = g.g0[1] - p.radius;
+    a.g0[2] = g.g0[2] - (1u + p.step);
+    a.nx = g.dims[0] + 2u * p.radius;
+    a.ny = g.dims[1] + 2u * p.radius;
+    a.nz = g.dims[2] + p.headroom + 2u * p.step;
+    a.total = a.nx * a.ny * a.nz;   // <= LA3DM_FOOTING_MAX_CELLS
+    const uint32_t n_words = cdiv(a.total, 32);
+    const size_t stride = ((size_t)n_words + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
+    DM_RESERVE(dm->ft_work, 4ull * (7 * stride + 3 * kFtWaves));
+    uint32_t *base = (uint32_t *)dm->ft_work.ptr;
+    FootingArgs f;
+    memset(&f, 0, sizeof(f));
+    f.nx = g.dims[0];
+    f.ny = g.dims[1];
+    f.nz = g.dims[2];
+    f.PY = a.ny;
+    f.PZ = a.nz;
+    f.h = p.headroom;
+    f.r = p.radius;
+    f.s = p.step;
+    f.c = p.min_support;
+    f.total = a.total;
+    f.n_words = n_words;
+    f.support = base;
+    f.clear = base + stride;
+    f.stand = base + 2 * stride;
+    f.near = base + 3 * stride;
+    f.body = base + 4 * stride;
+    f.count = base + 5 * stride;
+    f.offset = base + 6 * stride;
+    f.stats = base + 7 * stride;
+    f.cap = cap;
+    f.index = cap ? o.index : nullptr;
+    f.levels = o.levels;
+    f.lowest = o.lowest;
+    f.highest = o.highest;
+    hipLaunchKernelGGL(dm_ft_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, p.support_mask, p.clear_mask, base, base + stride);
+    hipLaunchKernelGGL(dm_ft_derive, dim3(cdiv(n_words, 256)), dim3(256), 0, st, f);
+    const dim3 wgrid(cdiv(n_words + 1, 256));
+    hipLaunchKernelGGL(dm_ft_foot, dim3(kFtWaves / 4), dim3(256), 0, st, f);   // four waves per workgroup
+    DM_TRY(hipGetLastError());
+    dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
+    int rc = exclusive_scan(dm, f.count, base + 6 * stride, n_words + 1);
+    if (rc != LA3DM_OK) return rc;
+    if (cap) hipLaunchKernelGGL(dm_ft_emit, wgrid, dim3(256), 0, st, f);
+    if (o.levels || o.lowest || o.highest)
+        hipLaunchKernelGGL(dm_ft_columns, dim3(cdiv((uint64_t)g.dims[0] * g.dims[1], 256)), dim3(256), 0, st, f);
+    DM_TRY(hipGetLastError());
+    d_stats = f.stats;
+    return LA3DM_OK;
+}
+
+static int footing_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3,
+                         const la3dm_footing_params *params, uint64_t cap, const la3dm_footing_out *out, uint64_t *n_found,
+                         la3dm_footing_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::footing_check(params, cap, out && out->index, "->")));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::footing_query(*params), true, true, who, g));   // lo, dims, the limit and the range
+    if (!n_found) return refuse(dm, who, "n_found is NULL");
+    hipStream_t st = dm->ctx->stream;
+    la3dm_footing_out o;
+    memset(&o, 0, sizeof(o));
+    if (out) o = *out;
+    const size_t n = (size_t)g.total, n_col = (size_t)g.dims[0] * g.dims[1];
+    uint32_t counts[3] = {0, 0, 0};
+    if (dm->n_blocks == 0) {   // every voxel MISSING, and the masks do not overlap: nothing stands
+        const Fill f{dm, host};
+        DM_OK(f.bytes(o.levels, 0, 4 * n_col));
+        DM_OK(f.bytes(o.lowest, 0xFF, 4 * n_col));
+        DM_OK(f.bytes(o.highest, 0xFF, 4 * n_col));
+        DM_TRY(hipStreamSynchronize(st));
+    } else {
+        // the list has at most one entry per voxel and no more than cap; only what was found is copied back
+        const size_t room = (size_t)std::min<uint64_t>(cap, n);
+        Stage s(dm, host);
+        const int i_index = s.out(o.index, room);
+        s.out(o.levels, n_col);
+        s.out(o.lowest, n_col);
+        s.out(o.highest, n_col);
+        DM_OK(s.reserve());
+        const uint32_t *d_stats = nullptr;
+        DM_OK(footing_launch(dm, g, *params, room, o, d_stats));
+        std::vector<uint32_t> partial(3 * kFtWaves);
+        DM_TRY(hipMemcpyAsync(partial.data(), d_stats, 4 * partial.size(), hipMemcpyDeviceToHost, st));
+        DM_TRY(hipStreamSynchronize(st));
+        for (size_t t = 0; t < partial.size(); ++t) counts[t % 3] += partial[t];   // (each sum is at most the voxels of the region)
+        s.count(i_index, counts[2]);
+        DM_OK(s.download());
+        if (host) DM_TRY(hipStreamSynchronize(st));
+    }
+    *n_found = counts[2];
+    if (stats) *stats = la3dm_footing_stats{counts[0], counts[1], counts[2], la3dm_footing::disc_cells(params->radius)};
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_footing_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params,
+                                uint64_t cap, const la3dm_footing_out *d_out, uint64_t *n_found, la3dm_footing_stats *stats,
+                                la3dm_region_info *info) {
+    return footing_query(dm, false, "la3dm_devmap_footing_device", lo3, dims3, params, cap, d_out, n_found, stats, info);
+}
+
+int la3dm_devmap_footing_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params,
+                              uint64_t cap, const la3dm_footing_out *out, uint64_t *n_found, la3dm_footing_stats *stats,
+                              la3dm_region_info *info) {
+    return footing_query(dm, true, "la3dm_devmap_footing_host", lo3, dims3, params, cap, out, n_found, stats, info);
 }
 
 // ---- gain of candidate viewpoints (devmap_gain.h) ---------------------------------------------------------------

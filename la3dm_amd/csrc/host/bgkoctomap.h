@@ -460,6 +460,18 @@ public:
     void frontier(const float *lo3, const uint32_t *dims3, uint32_t open_mask, uint32_t unknown_mask, uint32_t connectivity,
                   uint32_t min_neighbours, uint64_t cap, const la3dm_frontier_out &out, uint64_t *n_found,
                   la3dm_region_info *info = nullptr) const;
+    /// Footing over box's region (contract: include/la3dm_hip.h, la3dm_devmap_footing_host): where a ground robot can stand —
+    /// the voxels with a class of p->support_mask directly below and p->headroom voxels of p->clear_mask classes from the
+    /// voxel upwards, round which every cell of a disc of p->radius voxels is clear above p->step voxels and at least
+    /// p->min_support cells have such a standing place within p->step voxels of height.  Classes past the region's faces
+    /// are read from the map.  *n_found = their number; out.index = the flat indices of the first min(*n_found, cap) in
+    /// ascending order; out.levels / lowest / highest (dense, per column, optional) = the foot voxels of the column and
+    /// their smallest / largest k; stats (may be null) = the voxels that pass each condition and the cells of the disc.
+    /// Bad arguments throw std::invalid_argument.  A device-resident map runs the query on the device pool (no mirror
+    /// refresh); a host-mode map reads the classes of the padded box and calls host/footing_cells.h: that form is the
+    /// definition, and both give the same integers.
+    void footing(const float *lo3, const uint32_t *dims3, const la3dm_footing_params *p, uint64_t cap, const la3dm_footing_out &out,
+                 uint64_t *n_found, la3dm_footing_stats *stats = nullptr, la3dm_region_info *info = nullptr) const;
     /// Gain of candidate viewpoints over box's region (contract: include/la3dm_hip.h, la3dm_devmap_gain_host): the n * m
     /// segments origins[v] -> origins[v] + offsets[d] are walked exactly as raycast_many(stop_mask, max_steps) walks them;
     /// every row whose class is in `count_mask` and whose voxel lies in the region sets that voxel's bit in viewpoint v's

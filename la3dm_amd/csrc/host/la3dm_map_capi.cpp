@@ -399,6 +399,14 @@ int la3dm_map_frontier(const la3dm_map *m, const float *lo3, const uint32_t *dim
         return 0;)
 }
 
+int la3dm_map_footing(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params, uint64_t cap,
+                      const la3dm_footing_out *out, uint64_t *n_found, la3dm_footing_stats *stats, la3dm_region_info *info) {
+    GUARD(
+        const la3dm_footing_out none = la3dm_footing_out();   // (all null)
+        m->map->footing(lo3, dims3, params, cap, out ? *out : none, n_found, stats, info);
+        return 0;)
+}
+
 int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
                    const float *offsets3, uint32_t mdirs, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                    const la3dm_gain_out *out, la3dm_region_info *info) {

@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../../include/la3dm_hip.h"
+#include "footing_cells.h"
 
 #if defined(__HIPCC__)
 #define LA3DM_HD __host__ __device__
@@ -21,26 +22,34 @@
 
 namespace la3dm_region {
 
+// The voxels a query reads outside its region, per axis: limit and block-field range are taken on the padded box.
+struct Pad {
+    uint32_t lo[3], hi[3];    // voxels below voxel (0, 0, 0) and above voxel (nx - 1, ny - 1, nz - 1)
+    const char *range_text;   // refusal when the padded box leaves the block-field range
+};
+constexpr Pad kPadNone = {{0, 0, 0}, {0, 0, 0}, ""};
+constexpr Pad kPadOne = {{1, 1, 1}, {1, 1, 1}, "dims: the block fields of the region padded by one voxel leave [0, 2^20)"};
+
 struct Query {
     uint64_t max_cells;       // limit on the number of voxels (columns: of columns)
     const char *limit_text;
     bool columns;             // the limit counts columns, and nz has LA3DM_COLUMNS_MAX_NZ as a limit of its own
-    bool padded;              // limit and block-field range are taken on the region padded by one voxel on every side
+    Pad pad;                  // what the query reads past the region's faces
     const char *mandatory;    // refusal when the mandatory output is missing ("->" stands for the caller's member access)
     uint32_t brick = 0;       // > 0: the limit is taken on the region with every axis rounded up to a multiple of `brick`
 };
 
-constexpr Query kBox = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, false, "out->cls must not be NULL"};
-constexpr Query kColumns = {1ull << 30, "dims: more than 2^30 columns", true, false, "out->counts must not be NULL"};
-constexpr Query kDistance = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, "out: d2 or dist must not be NULL"};
-constexpr Query kFrontier = {LA3DM_FR_MAX_CELLS, "dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
-constexpr Query kGain = {LA3DM_GAIN_MAX_CELLS, "dims: more than LA3DM_GAIN_MAX_CELLS (2^28) voxels", false, false, ""};
-constexpr Query kReach = {LA3DM_REACH_MAX_CELLS, "dims: more than LA3DM_REACH_MAX_CELLS (2^28) voxels in the padded region", false, true, ""};
-constexpr Query kTravel = {LA3DM_TRAVEL_MAX_CELLS, "dims: more than LA3DM_TRAVEL_MAX_CELLS (2^28) voxels in the region rounded up to whole bricks", false, false, "",
+constexpr Query kBox = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, kPadNone, "out->cls must not be NULL"};
+constexpr Query kColumns = {1ull << 30, "dims: more than 2^30 columns", true, kPadNone, "out->counts must not be NULL"};
+constexpr Query kDistance = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, kPadNone, "out: d2 or dist must not be NULL"};
+constexpr Query kFrontier = {LA3DM_FR_MAX_CELLS, "dims: more than LA3DM_FR_MAX_CELLS (2^28) voxels in the padded region", false, kPadOne, ""};
+constexpr Query kGain = {LA3DM_GAIN_MAX_CELLS, "dims: more than LA3DM_GAIN_MAX_CELLS (2^28) voxels", false, kPadNone, ""};
+constexpr Query kReach = {LA3DM_REACH_MAX_CELLS, "dims: more than LA3DM_REACH_MAX_CELLS (2^28) voxels in the padded region", false, kPadOne, ""};
+constexpr Query kTravel = {LA3DM_TRAVEL_MAX_CELLS, "dims: more than LA3DM_TRAVEL_MAX_CELLS (2^28) voxels in the region rounded up to whole bricks", false, kPadNone, "",
                            LA3DM_TRAVEL_BRICK};
 // clusters: box's own limit here; the axis and brick limits follow the region's checks (clusters_region_check)
-constexpr Query kClusters = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, false, ""};
-constexpr Query kScore = {LA3DM_SCORE_MAX_CELLS, "dims: more than LA3DM_SCORE_MAX_CELLS (2^28) voxels", false, false, ""};
+constexpr Query kClusters = {LA3DM_BOX_MAX_CELLS, "dims: more than LA3DM_BOX_MAX_CELLS (2^30) voxels", false, kPadNone, ""};
+constexpr Query kScore = {LA3DM_SCORE_MAX_CELLS, "dims: more than LA3DM_SCORE_MAX_CELLS (2^28) voxels", false, kPadNone, ""};
 
 struct Anchor {
     uint32_t g0[3];      // global voxel index of voxel (0, 0, 0): block field * lim + cell
@@ -80,9 +89,10 @@ inline std::string resolve(const Query &q, const float *lo, const uint32_t *dims
         if (!(std::fabs(lo[k] / resolution) < 1073741824.0f)) return "lo must be finite with |lo / resolution| < 2^30";
     for (int k = 0; k < 3; ++k)
         if (dims[k] == 0) return "dims must be >= 1 on every axis";
-    const uint64_t pad = q.padded ? 2 : 0, ncol = (uint64_t)dims[0] * dims[1];
+    const uint64_t ncol = (uint64_t)dims[0] * dims[1];
     uint64_t e[3];   // the extents the limit counts: padded, rounded up to whole bricks, or as they are
-    for (int k = 0; k < 3; ++k) e[k] = q.brick ? ((uint64_t)dims[k] + q.brick - 1) / q.brick * q.brick : dims[k] + pad;
+    for (int k = 0; k < 3; ++k)
+        e[k] = q.brick ? ((uint64_t)dims[k] + q.brick - 1) / q.brick * q.brick : (uint64_t)dims[k] + q.pad.lo[k] + q.pad.hi[k];
     const uint64_t pcol = e[0] * e[1];
     if (q.columns) {
         if (ncol > q.max_cells) return q.limit_text;
@@ -103,8 +113,7 @@ inline std::string resolve(const Query &q, const float *lo, const uint32_t *dims
         a.cell[k] = v[k].cell;
         const long long first = v[k].b * lim + a.cell[k], last = first + (long long)dims[k] - 1;
         if (last / lim >= top) return "dims: the region's block fields leave [0, 2^20)";
-        if (q.padded && (first == 0 || (last + 1) / lim >= top))
-            return "dims: the block fields of the region padded by one voxel leave [0, 2^20)";
+        if (first < (long long)q.pad.lo[k] || (last + (long long)q.pad.hi[k]) / lim >= top) return q.pad.range_text;
         a.g0[k] = (uint32_t)first;
         a.block_key = (a.block_key << 20) | v[k].b;
     }
@@ -202,8 +211,8 @@ LA3DM_HD inline uint32_t score_class(uint32_t d2) { return d2 == 0 ? LA3DM_SCORE
 
 // ---- nearest and nearest_points (contract: include/la3dm_hip.h, la3dm_devmap_nearest_host) ----
 // nearest's limit, and its buffers as the region's last check; nearest_points' buffers follow the region's (nearest_buffers)
-constexpr Query kNearest = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, "out: index or d2 must not be NULL"};
-constexpr Query kNearestPoints = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, ""};
+constexpr Query kNearest = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, kPadNone, "out: index or d2 must not be NULL"};
+constexpr Query kNearestPoints = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, kPadNone, ""};
 
 // the checks of the two queries' own arguments, before the region's (nearest: n_points = 0)
 inline std::string nearest_check(uint32_t obstacle_mask, uint32_t radius, uint32_t n_points) {
@@ -302,7 +311,7 @@ inline uint32_t travel_entry(const la3dm_travel_params &p, uint32_t d2) {
 }
 
 // ---- score_paths (contract: include/la3dm_hip.h, la3dm_devmap_score_paths_host) ----
-constexpr Query kPaths = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, false, ""};
+constexpr Query kPaths = {LA3DM_DF_MAX_CELLS, "dims: more than LA3DM_DF_MAX_CELLS (2^28) voxels", false, kPadNone, ""};
 
 // the checks of score_paths' own arguments and buffers, all before the region's (`member` as in resolve)
 inline std::string paths_check(const la3dm_paths_params *p, uint32_t n_paths, uint32_t n_way, bool has_ways, bool has_out, bool has_cost,
@@ -381,6 +390,34 @@ LA3DM_HD inline bool path_blocked(uint32_t clearance, uint32_t d2) { return d2 !
 LA3DM_HD inline uint32_t path_entry(const la3dm_paths_params &p, uint32_t nz, uint32_t d2) {
     const uint32_t move = nz == 1u ? p.move_cost[0] : (nz == 2u ? p.move_cost[1] : p.move_cost[2]);   // (no runtime-indexed array: registers)
     return move + travel_pen(p.soft_radius, p.penalty, d2);
+}
+
+// ---- footing (contract: include/la3dm_hip.h, la3dm_devmap_footing_host) ----
+// the checks of footing's own arguments and of its list, all before the region's
+inline std::string footing_check(const la3dm_footing_params *p, uint64_t cap, bool has_index, const char *member) {
+    if (!p) return "params is NULL";
+    if (p->support_mask == 0 || (p->support_mask & ~0x1Fu)) return "support_mask must hold at least one of the bits 0x1F and no other";
+    if (p->clear_mask == 0 || (p->clear_mask & ~0x1Fu)) return "clear_mask must hold at least one of the bits 0x1F and no other";
+    if (p->support_mask & p->clear_mask) return "support_mask and clear_mask must not overlap";
+    if (p->headroom == 0 || p->headroom > LA3DM_FOOTING_MAX_HEADROOM) return "headroom must lie in [1, LA3DM_FOOTING_MAX_HEADROOM (32)]";
+    if (p->radius > LA3DM_FOOTING_MAX_RADIUS) return "radius must not exceed LA3DM_FOOTING_MAX_RADIUS (8)";
+    if (p->step > LA3DM_FOOTING_MAX_STEP || p->step >= p->headroom) return "step must not exceed LA3DM_FOOTING_MAX_STEP (4) and must be below headroom";
+    if (p->min_support > la3dm_footing::disc_cells(p->radius)) return "min_support must not exceed the cells of the footprint, N";
+    if (cap > 0 && !has_index) return std::string("out") + member + "index must not be NULL with cap > 0";
+    return "";
+}
+
+// the region's checks of footing: limit and range on the padded box of these (checked) parameters
+inline Query footing_query(const la3dm_footing_params &p) {
+    return Query{LA3DM_FOOTING_MAX_CELLS,
+                 "dims: more than LA3DM_FOOTING_MAX_CELLS (2^28) voxels in the padded box",
+                 false,
+                 Pad{{p.radius, p.radius, 1u + p.step}, {p.radius, p.radius, p.headroom - 1u + p.step}, "dims: the block fields of the padded box leave [0, 2^20)"},
+                 ""};
+}
+
+inline la3dm_footing::Params footing_params(const la3dm_footing_params &p) {
+    return la3dm_footing::Params{p.support_mask, p.clear_mask, p.headroom, p.radius, p.step, p.min_support};
 }
 
 // the checks of clusters' own arguments and buffers, all before the region's; `out` may be null
