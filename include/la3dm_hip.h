@@ -1367,6 +1367,115 @@ int la3dm_devmap_footing_host(la3dm_devmap *dm, const float *lo3, const uint32_t
 int la3dm_devmap_footing_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params,
                                 uint64_t cap, const la3dm_footing_out *d_out, uint64_t *n_found, la3dm_footing_stats *stats,
                                 la3dm_region_info *info);
+/* Drive: the least cost of a ground route from seed voxels over a set of MEMBER voxels of a region — the voxels footing
+ * finds —, with moves that climb or drop up to `step` voxels, and a parent per voxel to drive along.  travel routes a
+ * flying point through a class mask; drive routes a ground robot over the places where it can stand.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's; k grows
+ *     along +z of the map frame.
+ *   Members, list mode (params->footing NULL, params->members not NULL).  members[n_members] are flat indices, e.g.
+ *     footing's index.  clusters' rule for from_list = 1: an index >= nx ny nz is ignored, a voxel listed twice counts
+ *     once, n_members = 0 is served (members must still point somewhere: a NULL members with a NULL footing is no mode at
+ *     all).  There is no class test: the list is the truth, the pool is never read, and an empty map is served like any
+ *     other.
+ *   Members, footing mode (params->footing not NULL; members NULL, n_members 0).  The members are exactly the voxels that
+ *     footing(lo, dims, *params->footing) would list.  params->footing is a host pointer in both pointer forms.  On an
+ *     empty map there is no member.
+ *   Moves.  A move goes from member u to member v = u + (a, b, c) with (a, b) != (0, 0), |a|, |b| <= 1 and |c| <= step,
+ *     step in 0 ... LA3DM_DRIVE_MAX_STEP.  connectivity is 4 (|a| + |b| = 1) or 8.  There is no purely vertical move: a
+ *     floor and a table top in one column are joined only by a ramp of members.  Diagonal moves are not tested for corner
+ *     cutting, as for travel.  The move costs move_cost[|a| + |b| - 1] + (c > 0 ? climb_up * c : climb_down * -c);
+ *     move_cost[0], move_cost[1] in 1 ... LA3DM_TRAVEL_MAX_MOVE, climb_up, climb_down in 0 ... LA3DM_TRAVEL_MAX_MOVE.  Every
+ *     move costs at least 1, so the least costs are unique.
+ *   Cost.  cost[v] = the minimum over all walks of members from any seeded member to v; a seeded member costs 0.
+ *     LA3DM_DRIVE_NONE for a non-member, for a member no walk reaches, and where the least cost exceeds max_cost (1 ...
+ *     2^31).  (Candidates above max_cost are dropped while relaxing; every prefix of a least-cost walk is no dearer than the
+ *     walk, so no cost <= max_cost changes.)  No sum overflows 32 bits: a candidate is at most 2^31 + 2^16 + 4 * 2^16.
+ *   Seeds, targets, snap.  seeds and targets are flat indices.  snap in 0 ... LA3DM_DRIVE_MAX_SNAP.  A seed or target (i,
+ *     j, k) stands for the member (i, j, k') with the largest k' in [max(0, k - snap), k]: the sensor's voxel can be passed
+ *     as it is.  With an index out of range (>= nx ny nz), or with no such member, a seed is ignored and a target gets
+ *     LA3DM_DRIVE_NONE.  n_seeded counts the DISTINCT seeded members; n_seeds = 0 is served.  target_cost[t] = the cost at
+ *     the snapped member, target_index[t] (optional) = that member's flat index, or LA3DM_DRIVE_NONE.
+ *   Parent (optional, dense uint8).  The offset o = u - v from v back to u has the code q = ((o_i + 1) * 3 + (o_j + 1)) *
+ *     9 + (o_k + 4), 0 ... 80.  A seeded member gets 40, a non-member or an unreached voxel 255, any other reached v the
+ *     smallest q such that the move u -> v is allowed, u lies in the region and is a member, cost[u] is finite and cost[u] +
+ *     move(u -> v) == cost[v].  Such a q exists and is a function of `cost` and the member set alone; following parents
+ *     strictly lowers the cost and ends at a seeded member.
+ *   Outputs (la3dm_drive_out).  cost [nx ny nz]; parent [nx ny nz]; of_member [n_members] = the cost per list entry,
+ *     LA3DM_DRIVE_NONE for an ignored entry, list mode only; target_cost and target_index [n_targets].  At least one of
+ *     cost, of_member, target_cost must be set.
+ *   Stats (always a host struct, may be NULL).  Contract: n_members (distinct members in the region), n_seeded, n_reached
+ *     (members with a finite cost, seeds included), max_cost (the largest finite cost, 0 when nothing is reached).
+ *     Diagnostics of the device form, all 0 in the host form and no part of device == host: rounds, brick_runs, capped, as
+ *     travel's.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written, nothing reserved), in this order:
+ *     a NULL params; a connectivity other than 4 or 8; step > LA3DM_DRIVE_MAX_STEP; snap > LA3DM_DRIVE_MAX_SNAP; a
+ *     move_cost of 0 or > LA3DM_TRAVEL_MAX_MOVE; climb_up or climb_down > LA3DM_TRAVEL_MAX_MOVE; max_cost outside 1 ...
+ *     LA3DM_TRAVEL_MAX_COST; n_members > LA3DM_DRIVE_MAX_MEMBERS; n_seeds > LA3DM_DRIVE_MAX_SEEDS; n_targets > 2^28; a NULL
+ *     seeds, targets or members with a non-zero count; both modes at once (footing and members), or neither; a NULL out;
+ *     of_member set in footing mode or with n_members = 0; an out with none of cost, of_member and target_cost (parent or
+ *     target_index alone is not enough); target_cost or target_index set with n_targets = 0, or target_cost unset with
+ *     n_targets > 0.  Footing mode then refuses what footing refuses for *params->footing, in footing's order and with its
+ *     texts.  Then what box refuses for lo and dims, and a region whose axes, each rounded up to a multiple of
+ *     LA3DM_DRIVE_BRICK, hold more than LA3DM_DRIVE_MAX_CELLS voxels; in footing mode last footing's padded box that is too
+ *     large or leaves the block-field range.
+ *   Non-convergence.  A call that needs more than LA3DM_DRIVE_MAX_ROUNDS rounds fails with LA3DM_ERR_LIMIT and a text
+ *     that says so; the outputs are then unspecified.
+ *   Integers throughout, and the answer is unique: the results equal the host form (host/drive_cells.h — Dijkstra with a
+ *     binary heap, then the parent pass — which BGKOctoMap::drive calls on a host-mode map, in footing mode after its own
+ *     footing) exactly.
+ *   Device form (csrc/devmap_drive.h on csrc/devmap_brick.h's grid and round driver): travel's scheme.  The round kernel
+ *     relaxes a brick in a 10 x 10 x 16 LDS tile that holds LA3DM_DRIVE_MAX_STEP levels below and above the brick.  In
+ *     footing mode footing's launches run up to the foot words and one kernel turns the foot bits of the region's voxels
+ *     into entry words: nothing is listed, scanned or downloaded.  Working storage, in a grow-only arena of the devmap
+ *     (released with it, re-initialised on every call): 12 bytes per voxel of the region rounded up to whole bricks, 16
+ *     bytes per brick and the round counts; in footing mode also footing's own working storage. */
+#define LA3DM_DRIVE_NONE        0xFFFFFFFFu
+#define LA3DM_DRIVE_MAX_CELLS   (1u << 28)
+#define LA3DM_DRIVE_MAX_MEMBERS (1u << 28)
+#define LA3DM_DRIVE_MAX_SEEDS   (1u << 20)
+#define LA3DM_DRIVE_MAX_STEP    4
+#define LA3DM_DRIVE_MAX_SNAP    32
+#define LA3DM_DRIVE_MAX_ROUNDS  (1u << 16)
+#define LA3DM_DRIVE_BRICK       8
+#define LA3DM_DRIVE_INNER       16
+#define LA3DM_DRIVE_BATCH       8
+typedef struct la3dm_drive_params {
+    const uint32_t *members;                 /* list mode: [n_members] flat indices (device form: device memory); else NULL */
+    const la3dm_footing_params *footing;     /* footing mode: a host struct; else NULL */
+    uint32_t n_members;
+    uint32_t connectivity;   /* 4 or 8 */
+    uint32_t step;           /* voxels a move may climb or drop, 0 ... LA3DM_DRIVE_MAX_STEP */
+    uint32_t snap;           /* voxels a seed or target may lie above its member, 0 ... LA3DM_DRIVE_MAX_SNAP */
+    uint32_t move_cost[2];   /* moves with |a| + |b| = 1, 2 */
+    uint32_t climb_up;       /* per voxel climbed */
+    uint32_t climb_down;     /* per voxel dropped */
+    uint32_t max_cost;       /* 1 ... LA3DM_TRAVEL_MAX_COST */
+} la3dm_drive_params;
+typedef struct la3dm_drive_out {
+    uint32_t *cost;          /* [nx ny nz] or NULL */
+    uint8_t *parent;         /* [nx ny nz] or NULL */
+    uint32_t *of_member;     /* [n_members] or NULL; list mode only */
+    uint32_t *target_cost;   /* [n_targets] or NULL */
+    uint32_t *target_index;  /* [n_targets] or NULL */
+} la3dm_drive_out;
+typedef struct la3dm_drive_stats {
+    uint32_t n_members;   /* distinct members in the region */
+    uint32_t n_seeded;    /* distinct seeded members */
+    uint32_t n_reached;   /* members with a finite cost, seeds included */
+    uint32_t max_cost;    /* the largest finite cost */
+    uint32_t rounds, brick_runs, capped;   /* diagnostics of the device form */
+} la3dm_drive_stats;
+/* host pointers (params->members included): upload of the list, the seeds and the targets, the launches, download of what
+ * was asked for, synchronise — on the map's stream */
+int la3dm_devmap_drive_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                            const la3dm_drive_params *params, const uint32_t *targets, uint32_t n_targets,
+                            const la3dm_drive_out *out, la3dm_drive_stats *stats, la3dm_region_info *info);
+/* device pointers (seeds, targets, params->members and out's arrays already in HBM on the map's device, the word arrays
+ * 4-byte aligned; lo3, dims3, params, params->footing, stats and info stay host-side); returns when the results are
+ * complete */
+int la3dm_devmap_drive_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
+                              const la3dm_drive_params *params, const uint32_t *d_targets, uint32_t n_targets,
+                              const la3dm_drive_out *d_out, la3dm_drive_stats *stats, la3dm_region_info *info);
 /* Leaf export =the publish loop of the static node (src/bgkoctomap/bgkoctomap_static_node.cpp:101-136) with the
  * cube-list bookkeeping of MarkerArrayPub (include/common/markerarray_pub.h:104-147) minus ROS, run on the pool:
  * state 1 = OCCUPIED leaves coloured by height (heightMapColor when min_z < max_z, else the marker default),

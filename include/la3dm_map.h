@@ -224,6 +224,18 @@ int la3dm_map_reach(const la3dm_map *m, const float *lo3, const uint32_t *dims3,
 int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
                      const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
                      la3dm_travel_stats *stats, la3dm_region_info *info);
+/* BGKOctoMap::drive: cost[v] = the least cost of a ground route from any of the seed voxels to v over the member voxels of
+ * box's region — those of the list params->members, or with params->footing set the voxels footing would list — by moves
+ * to one of the 4 or 8 horizontal neighbours that climb or drop at most params->step voxels; LA3DM_DRIVE_NONE for a
+ * non-member and where no walk of at most params->max_cost exists.  A seed or target stands for the highest member at
+ * most params->snap voxels below it.  out->parent[v] = the code ((o_i + 1) * 3 + (o_j + 1)) * 9 + (o_k + 4) of the offset
+ * to the member a least-cost walk came from, 40 at a seeded member, 255 where unreached; out->target_cost[t] and
+ * out->target_index[t] = the cost at the member of targets[t] and that member.  Contract, limits and refusals:
+ * include/la3dm_hip.h (la3dm_devmap_drive_host).  Device-resident maps relax bricks of the region on the device without a
+ * mirror refresh, host-mode maps run their own footing and Dijkstra on the CPU; the results are identical. */
+int la3dm_map_drive(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                    const la3dm_drive_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_drive_out *out,
+                    la3dm_drive_stats *stats, la3dm_region_info *info);
 /* BGKOctoMap::clusters: the connected groups of the member voxels of box's region — every voxel with a class in
  * params->member_mask, or those of the list params->members — under params->connectivity, confined to tiles of
  * params->tile voxels (0: untiled) and kept from params->min_size members up; numbered in ascending order of their

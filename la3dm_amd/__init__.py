@@ -12,6 +12,8 @@ from .bgkoctomap import FOOTING_MAX_CELLS, FOOTING_MAX_HEADROOM, FOOTING_MAX_RAD
 from .bgkoctomap import REACH_NONE, REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS, REACH_BATCH  # noqa: F401
 from .bgkoctomap import TRAVEL_NONE, TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_MOVE, TRAVEL_MAX_PENALTY, TRAVEL_MAX_SEEDS  # noqa: F401
 from .bgkoctomap import TRAVEL_MAX_ROUNDS, TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH, follow_parents  # noqa: F401
+from .bgkoctomap import DRIVE_NONE, DRIVE_MAX_CELLS, DRIVE_MAX_MEMBERS, DRIVE_MAX_SEEDS, DRIVE_MAX_ROUNDS, DRIVE_MAX_STEP, DRIVE_MAX_SNAP  # noqa: F401
+from .bgkoctomap import DRIVE_BRICK, DRIVE_INNER, DRIVE_BATCH, DRIVE_SEED_CODE, follow_drive_parents  # noqa: F401
 from .bgkoctomap import CLUSTERS_NONE, CLUSTERS_MAX_CELLS, CLUSTERS_MAX_MEMBERS, CLUSTERS_MAX_ROUNDS, CLUSTERS_MAX_AXIS  # noqa: F401
 from .bgkoctomap import CLUSTERS_MAX_TILE, CLUSTERS_BRICK, CLUSTERS_INNER, CLUSTERS_BATCH  # noqa: F401
 from .bgkoctomap import pack_info, load_map, PACK_CLASSES  # noqa: F401

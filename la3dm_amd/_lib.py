@@ -155,6 +155,20 @@ class TravelStats(_Stats):  # la3dm_travel_stats
     _fields_ = [(k, C.c_uint32) for k in ("n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")]
 
 
+class DriveParams(C.Structure):  # la3dm_drive_params
+    _fields_ = [("members", C.c_void_p), ("footing", C.POINTER(FootingParams)), ("n_members", C.c_uint32), ("connectivity", C.c_uint32),
+                ("step", C.c_uint32), ("snap", C.c_uint32), ("move_cost", C.c_uint32 * 2), ("climb_up", C.c_uint32),
+                ("climb_down", C.c_uint32), ("max_cost", C.c_uint32)]
+
+
+class DriveOut(C.Structure):     # la3dm_drive_out
+    _fields_ = [(k, C.c_void_p) for k in ("cost", "parent", "of_member", "target_cost", "target_index")]
+
+
+class DriveStats(_Stats):   # la3dm_drive_stats
+    _fields_ = [(k, C.c_uint32) for k in ("n_members", "n_seeded", "n_reached", "max_cost", "rounds", "brick_runs", "capped")]
+
+
 class ClustersParams(C.Structure):  # la3dm_clusters_params
     _fields_ = [(k, C.c_uint32) for k in ("member_mask", "from_list", "connectivity", "tile", "min_size", "n_members")] + \
                [("members", C.c_void_p), ("cap", C.c_uint32)]
@@ -243,6 +257,9 @@ _NEAREST = [vp, vp, u32, u32, P(NearestOut), _INFO]
 _NEAREST_POINTS = [vp, vp, vp, u32, vp, u32, u32, P(NearestPointsOut), _INFO]
 # ... and so has footing
 _FOOTING = [vp, vp, P(FootingParams), u64, P(FootingOut), P(u64), P(FootingStats), _INFO]
+# ... and drive: one row for its three forms
+_DRIVE = {f"la3dm_{form}": (cint, [vp, vp, vp, vp, u32, P(DriveParams), vp, u32, P(DriveOut), P(DriveStats), _INFO])
+          for form in ("map_drive", "devmap_drive_host", "devmap_drive_device")}
 
 
 def _query_entries(of_map):
@@ -295,6 +312,7 @@ HIP_API = {
     "la3dm_devmap_nearest_points_device": (cint, [vp] + _NEAREST_POINTS),
     "la3dm_devmap_footing_host": (cint, [vp] + _FOOTING),
     "la3dm_devmap_footing_device": (cint, [vp] + _FOOTING),
+    **{n: sig for n, sig in _DRIVE.items() if n.startswith("la3dm_devmap_")},
     **_query_entries(of_map=False),
 }
 
@@ -356,6 +374,7 @@ MAP_API = {
     "la3dm_map_nearest": (cint, [vp] + _NEAREST),
     "la3dm_map_nearest_points": (cint, [vp] + _NEAREST_POINTS),
     "la3dm_map_footing": (cint, [vp] + _FOOTING),
+    "la3dm_map_drive": _DRIVE["la3dm_map_drive"],
     **_query_entries(of_map=True),
 }
 HIP_SYMBOLS = list(HIP_API)

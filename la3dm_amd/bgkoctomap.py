@@ -34,6 +34,11 @@ TRAVEL_NONE = 0xFFFFFFFF            # LA3DM_TRAVEL_NONE: travel found no walk to
 TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_SEEDS, TRAVEL_MAX_ROUNDS = 1 << 28, 1 << 31, 1 << 20, 1 << 16   # LA3DM_TRAVEL_MAX_*
 TRAVEL_MAX_MOVE = TRAVEL_MAX_PENALTY = 1 << 16
 TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH = 8, 16, 8   # LA3DM_TRAVEL_*: a brick's edge, iterations of one brick run, rounds queued between two reads of the counts
+DRIVE_NONE = 0xFFFFFFFF             # LA3DM_DRIVE_NONE: a non-member, or a member drive found no walk to
+DRIVE_MAX_CELLS, DRIVE_MAX_MEMBERS, DRIVE_MAX_SEEDS, DRIVE_MAX_ROUNDS = 1 << 28, 1 << 28, 1 << 20, 1 << 16   # LA3DM_DRIVE_MAX_*
+DRIVE_MAX_STEP, DRIVE_MAX_SNAP = 4, 32   # voxels a move may climb or drop; voxels a seed or target may lie above its member
+DRIVE_BRICK, DRIVE_INNER, DRIVE_BATCH = 8, 16, 8   # LA3DM_DRIVE_*: as travel's
+DRIVE_SEED_CODE = 40                # drive's parent code of a seeded member: the offset (0, 0, 0)
 CLUSTERS_NONE = 0xFFFFFFFF          # LA3DM_CLUSTERS_NONE: a non-member, or a member of a dropped cluster
 CLUSTERS_MAX_CELLS, CLUSTERS_MAX_MEMBERS, CLUSTERS_MAX_ROUNDS = 1 << 28, 1 << 28, 1 << 16   # LA3DM_CLUSTERS_MAX_*
 CLUSTERS_MAX_AXIS = CLUSTERS_MAX_TILE = 1 << 15
@@ -693,6 +698,77 @@ class BGKOctoMap:
         out.update(stats.as_dict(), **region)
         return out
 
+    def drive(self, lo, dims, seeds, members=None, footing=None, connectivity=8, step=1, snap=0, move_cost=(10, 14), climb_up=0,
+              climb_down=0, max_cost=None, targets=None, fields=("cost",)):
+        """Least costs of ground routes from seed voxels over the member voxels of the region of box(lo, dims), and the
+        parents to drive along.  The members are the voxels of `members` (flat indices (i * ny + j) * nz + k, e.g. footing's
+        index; one out of range is ignored, one listed twice counts once; no class is tested and the map is not read) or,
+        with footing=dict(support=, clear=, headroom=, radius=, step=, min_support=) — footing()'s parameters —, exactly the
+        voxels footing(lo, dims, **footing) lists: a device-resident map then feeds footing's kernels into the query
+        without listing or downloading anything.  One of the two, not both.  A move goes from a member to a member at one
+        of the `connectivity` (4 or 8) horizontal neighbours, up to `step` (0 .. 4) voxels higher or lower — never straight
+        up or down — and costs move_cost[0] (straight) or move_cost[1] (diagonal) plus climb_up per voxel climbed or
+        climb_down per voxel dropped.  seeds and targets are flat indices; each stands for the highest member of its column
+        at most `snap` (0 .. 32) voxels below it, so the sensor's voxel can be passed as it is; a seed without one is
+        ignored.  cost[v] = the least cost of a walk of members from any seed to v, DRIVE_NONE for a non-member and where
+        there is none of at most max_cost (None: TRAVEL_MAX_COST).  parent[v] (uint8) = the code ((o_i + 1) * 3 + (o_j + 1))
+        * 9 + (o_k + 4) of the offset to the member a least-cost walk came from — the smallest such code — 40 at a seed and
+        255 where unreached: follow_drive_parents(parent, dims, index) lists the route.  fields: any of "cost", "parent",
+        "of_member" (the cost per entry of `members`) and "target_index" (the member each target stands for, DRIVE_NONE
+        without one); target_cost comes with `targets`, and fields=() with targets fetches the targets' answers alone.
+        Returns a dict with those arrays, n_members, n_seeded, n_reached, max_cost (the largest finite cost), the device
+        form's diagnostics rounds, brick_runs and capped (0 on a host-mode map), plus origin, block_key, cell as box()
+        returns them.  A device-resident map relaxes 8 x 8 x 8 bricks of the region on the device (no host mirror refresh);
+        a host-mode map runs Dijkstra on the CPU, with identical results."""
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: ((d[0] + 7) // 8) * ((d[1] + 7) // 8) * ((d[2] + 7) // 8) * 512 <= DRIVE_MAX_CELLS)
+        fields = _want("drive", fields, ("cost", "parent", "of_member", "target_index"))
+        s, t, nt = _indices(seeds, targets)
+        lst = None if members is None else np.ascontiguousarray(members, np.uint32).reshape(-1)
+        nm = 0 if lst is None else lst.size
+        max_cost = TRAVEL_MAX_COST if max_cost is None else int(max_cost)
+        moves = [int(v) for v in move_cost]
+        if len(moves) != 2:
+            raise ValueError("drive: move_cost must hold two values")
+        words = [int(connectivity), int(step), int(snap)] + moves + [int(climb_up), int(climb_down), max_cost]
+        msg = "drive: connectivity, step, snap, move_cost, climb_up, climb_down, max_cost, footing's parameters and the numbers of members, seeds and targets must fit 32 bits"
+        _fit(msg, words + [nm, s.size, nt])
+        fp = None
+        if footing is not None:
+            f = dict(support=("occupied",), clear=("free",), headroom=2, radius=0, step=0, min_support=None)
+            bad = set(footing) - set(f)
+            if bad:
+                raise ValueError(f"drive: unknown footing parameters {sorted(bad)}")
+            f.update(footing)
+            if f["min_support"] is None:
+                f["min_support"] = footprint_cells(f["radius"]) if 0 <= int(f["radius"]) <= FOOTING_MAX_RADIUS else 0
+            fw = [_class_mask(f["support"]), _class_mask(f["clear"])] + [int(f[k]) for k in ("headroom", "radius", "step", "min_support")]
+            _fit(msg, fw)
+            fp = _lib.FootingParams(*fw)
+            ok = ok and (d[0] + 2 * fw[3]) * (d[1] + 2 * fw[3]) * (d[2] + fw[2] + 2 * fw[4]) <= FOOTING_MAX_CELLS
+        shape = tuple(d) if ok else (1,)
+        # list mode with an empty list: the pointer still says which mode it is
+        at = None if lst is None else (lst if nm else np.zeros(1, np.uint32)).ctypes.data
+        p = _lib.DriveParams(at, C.pointer(fp) if fp is not None else None, nm, words[0], words[1], words[2], (C.c_uint32 * 2)(*moves),
+                             words[5], words[6], words[7])
+        out = {}
+        if "cost" in fields:
+            out["cost"] = np.empty(shape, np.uint32)
+        if "parent" in fields:
+            out["parent"] = np.empty(shape, np.uint8)
+        if "of_member" in fields:
+            out["of_member"] = np.empty(nm, np.uint32)
+        if t is not None:
+            out["target_cost"] = np.empty(nt, np.uint32)
+            if "target_index" in fields:
+                out["target_index"] = np.empty(nt, np.uint32)
+        elif "target_index" in fields:
+            raise ValueError("drive: target_index needs targets")
+        stats = _lib.DriveStats()
+        region = self._region_call(self._M.la3dm_map_drive, lo3, d3, _addr(s), s.size, C.byref(p), _addr(t), nt,
+                                   C.byref(_out(_lib.DriveOut, out, null_empty=("of_member", "target_cost", "target_index"))), C.byref(stats))
+        out.update(stats.as_dict(), **region)
+        return out
+
     def clusters(self, lo, dims, members=None, member=("free",), connectivity=26, tile=0, min_size=1, cap=None, fields=("label",)):
         """The connected groups of the member voxels of the region of box(lo, dims).  A member is a voxel whose class (box's
         cls) is in `member` (names or an integer bit mask, as travel takes them) — every such voxel of the region, or with
@@ -1187,4 +1263,23 @@ def follow_parents(parent, dims, index):
         f += ((q // 9 - 1) * ny + ((q // 3) % 3 - 1)) * nz + (q % 3 - 1)
     if path:
         raise ValueError("follow_parents: the parents do not lead to a seed")
+    return np.zeros(0, np.int64)
+
+
+def follow_drive_parents(parent, dims, index):
+    """The route from flat index `index` back to its seed through drive's `parent` array (any shape of prod(dims) codes): the
+    flat indices, `index` first and the seeded member last.  Empty where `index` was not reached (code 255)."""
+    par = np.asarray(parent).reshape(-1)
+    ny, nz = int(dims[1]), int(dims[2])
+    f, path = int(index), []
+    while par[f] != 255:
+        path.append(f)
+        q = int(par[f])
+        if q == DRIVE_SEED_CODE:
+            return np.array(path, np.int64)
+        if q > 80 or len(path) > par.size:
+            break
+        f += ((q // 27 - 1) * ny + ((q // 9) % 3 - 1)) * nz + (q % 9 - 4)
+    if path:
+        raise ValueError("follow_drive_parents: the parents do not lead to a seed")
     return np.zeros(0, np.int64)

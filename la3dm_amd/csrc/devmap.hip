@@ -37,6 +37,7 @@
 #include "devmap_paths.h"
 #include "devmap_reach.h"
 #include "devmap_travel.h"
+#include "devmap_drive.h"
 #include "devmap_clusters.h"
 #include "devmap_pack.h"
 #include "devmap_merge.h"
@@ -99,6 +100,7 @@ struct la3dm_devmap {
     Arena nt_work;                // nearest: the y keys (4 bytes per voxel), the z offsets (2), the obstacle bits; nearest_points: index and d2 as well (devmap_nearest.h)
     Arena reach_work;             // reach: four bit streams of the padded box, the level counts, 4 bytes per voxel (devmap_reach.h)
     Arena travel_work;            // travel: two brick-major cost buffers, the entry words, side / active per brick, the round counts, d2 (devmap_travel.h)
+    Arena drive_work;             // drive: two brick-major cost buffers, the entry words, side / active per brick, the round counts (devmap_drive.h)
     Arena clusters_work;          // clusters: two brick-major label buffers, side / active per brick, the round counts, sizes, flags, numbers (devmap_clusters.h)
     Arena clusters_rec;           // clusters: the records of the clusters written (sums, keys, boxes, first, size, rep)
     Arena pack_stream, pack_counts;   // save / load: the stream as it leaves or enters the device; the blocks' leaf counts (devmap_pack.h)
@@ -735,7 +737,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->ft_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->ft_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->drive_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3532,10 +3534,10 @@ int la3dm_devmap_frontier_host(la3dm_devmap *dm, const float *lo3, const uint32_
 
 // ---- footing of a region (devmap_footing.h) --------------------------------------------------------------------
 
-// Bits, derive, foot, scan, (cap > 0) emit and (a dense array) columns on the map's stream; o's arrays are device memory.
-// d_stats: where the launches leave the kFtWaves partial counts of n_stand, n_body and n_foot (working storage).
-static int footing_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_footing_params &p, uint64_t cap, const la3dm_footing_out &o,
-                          const uint32_t *&d_stats) {
+// Bits, derive and foot on the map's stream: footing's launches up to the foot words, which lie in f.stand afterwards (the
+// popcounts in f.count, the partial counts in f.stats).  Fills f but for cap and the output arrays.  drive's footing mode
+// stops here.
+static int footing_words(la3dm_devmap *dm, const RegionGeom &g, const la3dm_footing_params &p, FootingArgs &f) {
     hipStream_t st = dm->ctx->stream;
     RegionArgs a = region_args(dm, g);
     a.g0[0] = g.g0[0] - p.radius;   // (footing_query's region check: g0 >= the pad below)
@@ -3549,7 +3551,6 @@ static int footing_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_foo
     const size_t stride = ((size_t)n_words + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
     DM_RESERVE(dm->ft_work, 4ull * (7 * stride + 3 * kFtWaves));
     uint32_t *base = (uint32_t *)dm->ft_work.ptr;
-    FootingArgs f;
     memset(&f, 0, sizeof(f));
     f.nx = g.dims[0];
     f.ny = g.dims[1];
@@ -3570,18 +3571,30 @@ static int footing_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_foo
     f.count = base + 5 * stride;
     f.offset = base + 6 * stride;
     f.stats = base + 7 * stride;
+    hipLaunchKernelGGL(dm_ft_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, p.support_mask, p.clear_mask, base, base + stride);
+    hipLaunchKernelGGL(dm_ft_derive, dim3(cdiv(n_words, 256)), dim3(256), 0, st, f);
+    hipLaunchKernelGGL(dm_ft_foot, dim3(kFtWaves / 4), dim3(256), 0, st, f);   // four waves per workgroup
+    DM_TRY(hipGetLastError());
+    return LA3DM_OK;
+}
+
+// footing_words, scan, (cap > 0) emit and (a dense array) columns on the map's stream; o's arrays are device memory.
+// d_stats: where the launches leave the kFtWaves partial counts of n_stand, n_body and n_foot (working storage).
+static int footing_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_footing_params &p, uint64_t cap, const la3dm_footing_out &o,
+                          const uint32_t *&d_stats) {
+    hipStream_t st = dm->ctx->stream;
+    FootingArgs f;
+    int rc = footing_words(dm, g, p, f);
+    if (rc != LA3DM_OK) return rc;
     f.cap = cap;
     f.index = cap ? o.index : nullptr;
     f.levels = o.levels;
     f.lowest = o.lowest;
     f.highest = o.highest;
-    hipLaunchKernelGGL(dm_ft_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, p.support_mask, p.clear_mask, base, base + stride);
-    hipLaunchKernelGGL(dm_ft_derive, dim3(cdiv(n_words, 256)), dim3(256), 0, st, f);
+    const uint32_t n_words = f.n_words;
     const dim3 wgrid(cdiv(n_words + 1, 256));
-    hipLaunchKernelGGL(dm_ft_foot, dim3(kFtWaves / 4), dim3(256), 0, st, f);   // four waves per workgroup
-    DM_TRY(hipGetLastError());
     dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
-    int rc = exclusive_scan(dm, f.count, base + 6 * stride, n_words + 1);
+    rc = exclusive_scan(dm, f.count, const_cast<uint32_t *>(f.offset), n_words + 1);
     if (rc != LA3DM_OK) return rc;
     if (cap) hipLaunchKernelGGL(dm_ft_emit, wgrid, dim3(256), 0, st, f);
     if (o.levels || o.lowest || o.highest)
@@ -4028,7 +4041,8 @@ int la3dm_devmap_reach_host(la3dm_devmap *dm, const float *lo3, const uint32_t *
 
 // ---- the host side of the brick scheme that travel and clusters share (devmap_brick.h) ---------------------------------
 constexpr uint32_t kBrickCountRing = 1024;   // rounds whose counts the working storage holds before they are cleared again
-static_assert(kBrickCountRing % LA3DM_TRAVEL_BATCH == 0 && kBrickCountRing % LA3DM_CLUSTERS_BATCH == 0, "a batch never straddles the ring's end");
+static_assert(kBrickCountRing % LA3DM_TRAVEL_BATCH == 0 && kBrickCountRing % LA3DM_CLUSTERS_BATCH == 0 && kBrickCountRing % LA3DM_DRIVE_BATCH == 0,
+              "a batch never straddles the ring's end");
 
 // Fills the grid of region g and lays a query's working storage out in `work`:
 //   value 0 | value 1 | `more_cells` further arrays of a word per cell | side 0 | side 1 | active 0 | active 1 | counts |
@@ -4186,6 +4200,119 @@ int la3dm_devmap_travel_host(la3dm_devmap *dm, const float *lo3, const uint32_t 
                              const la3dm_travel_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out *out,
                              la3dm_travel_stats *stats, la3dm_region_info *info) {
     return travel_query(dm, true, "la3dm_devmap_travel_host", lo3, dims3, seeds, n_seeds, params, targets, n_targets, out, stats, info);
+}
+
+// ---- drive: least cost of a ground route over the member voxels of a region, with parents (devmap_drive.h) -------------
+
+// the instantiation of a kernel template <int kConn, int kStep> for a connectivity and a step that the query's check has
+// found to be 4 or 8 and 0 ... 4
+#define DM_DR_BY_STEP(kernel, conn, step) \
+    ((step) == 0 ? kernel<conn, 0> : (step) == 1 ? kernel<conn, 1> : (step) == 2 ? kernel<conn, 2> : (step) == 3 ? kernel<conn, 3> : kernel<conn, 4>)
+#define DM_BY_DRIVE(kernel, connectivity, step) ((connectivity) == 4 ? DM_DR_BY_STEP(kernel, 4, step) : DM_DR_BY_STEP(kernel, 8, step))
+
+// The whole query on the map's stream; every pointer but `stats` and p.footing is device memory.  The working storage is
+// initialised here on every call.  The rounds are queued LA3DM_DRIVE_BATCH at a time (brick_rounds).  o.cost and o.parent
+// may be null: dm_dr_finish then only accumulates the totals.
+static int drive_launch(la3dm_devmap *dm, const RegionGeom &g, const uint32_t *d_seeds, uint32_t n_seeds, const la3dm_drive_params &p,
+                        const uint32_t *d_targets, uint32_t n_targets, const la3dm_drive_out &o, la3dm_drive_stats &stats) {
+    hipStream_t st = dm->ctx->stream;
+    DriveArgs a;
+    memset(&a, 0, sizeof(a));
+    a.move[0] = p.move_cost[0];
+    a.move[1] = p.move_cost[1];
+    a.up = p.climb_up;
+    a.down = p.climb_down;
+    a.max_cost = p.max_cost;
+    a.snap = p.snap;
+    // layout: cost 0 | cost 1 | E | side .. totals
+    uint32_t *own;
+    int rc = brick_layout(dm, dm->drive_work, g, 1, 0, a.g, a.totals, own);
+    if (rc != LA3DM_OK) return rc;
+    a.E = a.g.val[1] + (size_t)a.g.n_bricks * 512;
+    DM_TRY(hipMemsetAsync(a.g.side[0], 0, 4ull * (own - a.g.side[0]), st));
+    hipLaunchKernelGGL(dm_dr_clear, dim3(a.g.n_bricks * 2u), dim3(256), 0, st, a);
+    if (p.footing) {
+        if (dm->n_blocks) {   // (an empty map: every voxel MISSING, nothing stands, the pool is not read)
+            FootingArgs f;
+            rc = footing_words(dm, g, *p.footing, f);
+            if (rc != LA3DM_OK) return rc;
+            hipLaunchKernelGGL(dm_dr_foot, dim3(cdiv(a.g.n_cells, 256)), dim3(256), 0, st, a, f.stand, f.PY, f.PZ, f.r, f.s);
+        }
+    } else if (p.n_members) {
+        hipLaunchKernelGGL(dm_dr_members, dim3(cdiv(p.n_members, 256)), dim3(256), 0, st, a, p.members, p.n_members);
+    }
+    DM_TRY(hipGetLastError());
+    memset(&stats, 0, sizeof(stats));
+    uint32_t queued = 0;
+    if (n_seeds) {
+        hipLaunchKernelGGL(DM_BY_DRIVE(dm_dr_seed, p.connectivity, p.step), dim3(cdiv(n_seeds, 256)), dim3(256), 0, st, a, d_seeds, n_seeds);
+        DM_TRY(hipGetLastError());
+        const auto round_kernel = DM_BY_DRIVE(dm_dr_round, p.connectivity, p.step);
+        rc = brick_rounds<LA3DM_DRIVE_BATCH>(
+            dm, a.g, [&](uint32_t turn, uint32_t slot) { hipLaunchKernelGGL(round_kernel, dim3(a.g.n_bricks), dim3(512), 0, st, a, turn, slot); },
+            LA3DM_DRIVE_MAX_ROUNDS, "la3dm_devmap_drive: no fixed point after LA3DM_DRIVE_MAX_ROUNDS (2^16) rounds; the outputs are unspecified",
+            queued, stats.rounds, stats.brick_runs, stats.capped);
+        if (rc != LA3DM_OK) return rc;
+    }
+    const uint32_t *side = a.g.side[queued & 1u];
+    hipLaunchKernelGGL(DM_BY_DRIVE(dm_dr_finish, p.connectivity, p.step), dim3(cdiv(a.g.n_cells, 256)), dim3(256), 0, st, a, side, o.cost, o.parent);
+    DM_TRY(hipGetLastError());
+    const uint32_t n_list = o.of_member ? p.n_members : 0u;
+    if (n_targets + n_list) {
+        hipLaunchKernelGGL(dm_dr_gather, dim3(cdiv(n_targets + n_list, 256)), dim3(256), 0, st, a, side, d_targets, n_targets, o.target_cost,
+                           o.target_index, p.members, n_list, o.of_member);
+        DM_TRY(hipGetLastError());
+    }
+    uint32_t totals[4];
+    DM_TRY(hipMemcpyAsync(totals, a.totals, sizeof(totals), hipMemcpyDeviceToHost, st));
+    DM_TRY(hipStreamSynchronize(st));
+    stats.n_seeded = totals[0];
+    stats.n_reached = totals[1];
+    stats.max_cost = totals[2];
+    stats.n_members = totals[3];
+    return LA3DM_OK;
+}
+
+static int drive_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3, const uint32_t *seeds,
+                       uint32_t n_seeds, const la3dm_drive_params *params, const uint32_t *targets, uint32_t n_targets,
+                       const la3dm_drive_out *out, la3dm_drive_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::drive_check(params, n_seeds, n_targets, seeds != nullptr, targets != nullptr, out, "->")));
+    if (params->footing) DM_OK(refuse(dm, who, la3dm_region::footing_check(params->footing, 0, false, "->")));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::kDrive, true, true, who, g));
+    if (params->footing) DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::footing_query(*params->footing), true, true, who, g));   // the padded box
+    la3dm_drive_out o = *out;
+    la3dm_drive_params p = *params;
+    const size_t n = (size_t)g.total;
+    Stage s(dm, host);
+    s.in(seeds, n_seeds);
+    s.in(targets, n_targets);
+    s.in(p.members, p.n_members);
+    s.out(o.cost, n);
+    s.out(o.parent, n);
+    s.out(o.of_member, p.n_members);
+    s.out(o.target_cost, n_targets);
+    s.out(o.target_index, n_targets);
+    DM_OK(s.reserve());
+    la3dm_drive_stats ds;
+    DM_OK(drive_launch(dm, g, seeds, n_seeds, p, targets, n_targets, o, ds));   // (ends in a synchronise)
+    DM_OK(s.download());
+    if (host) DM_TRY(hipStreamSynchronize(dm->ctx->stream));
+    if (stats) *stats = ds;
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_drive_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *d_seeds, uint32_t n_seeds,
+                              const la3dm_drive_params *params, const uint32_t *d_targets, uint32_t n_targets,
+                              const la3dm_drive_out *d_out, la3dm_drive_stats *stats, la3dm_region_info *info) {
+    return drive_query(dm, false, "la3dm_devmap_drive_device", lo3, dims3, d_seeds, n_seeds, params, d_targets, n_targets, d_out, stats, info);
+}
+
+int la3dm_devmap_drive_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                            const la3dm_drive_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_drive_out *out,
+                            la3dm_drive_stats *stats, la3dm_region_info *info) {
+    return drive_query(dm, true, "la3dm_devmap_drive_host", lo3, dims3, seeds, n_seeds, params, targets, n_targets, out, stats, info);
 }
 
 // ---- clusters: connected groups of a region's member voxels, optionally tiled (devmap_clusters.h) ----------------------

@@ -1721,6 +1721,45 @@ void BGKOctoMap::travel(const float *lo3, const uint32_t *dims3, const uint32_t 
     if (stats) *stats = s;
 }
 
+// ---- drive over a region.  host/drive_cells.h is the definition; the device kernels (csrc/devmap_drive.h) reproduce it
+// bit for bit.  Here the member bytes are built: from the list, or from this map's own footing over the same region.
+void BGKOctoMap::drive(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, const la3dm_drive_params *p,
+                       const uint32_t *targets, uint32_t n_targets, const la3dm_drive_out *out, la3dm_drive_stats *stats,
+                       la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_drive_host(dmap, lo3, dims3, seeds, n_seeds, p, targets, n_targets, out, stats, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::drive: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::drive: ";
+    std::string refusal = la3dm_region::drive_check(p, n_seeds, n_targets, seeds != nullptr, targets != nullptr, out, ".");
+    if (refusal.empty() && p->footing) refusal = la3dm_region::footing_check(p->footing, 0, false, ".");
+    if (!refusal.empty()) throw std::invalid_argument(w + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::kDrive, true, "drive", g0, inf);
+    if (p->footing) region_anchor(lo3, dims3, la3dm_region::footing_query(*p->footing), true, "drive", g0, inf);   // the padded box
+    const size_t n = (size_t)dims3[0] * dims3[1] * dims3[2];
+    std::vector<uint8_t> member(n, 0);
+    if (p->footing) {
+        std::vector<uint32_t> index(n);
+        uint64_t found = 0;
+        la3dm_footing_out fo = la3dm_footing_out();
+        fo.index = index.data();
+        footing(lo3, dims3, p->footing, n, fo, &found);
+        for (uint64_t t = 0; t < found; ++t) member[index[t]] = 1;
+    } else {
+        for (uint32_t t = 0; t < p->n_members; ++t)
+            if (p->members[t] < n) member[p->members[t]] = 1;
+    }
+    const la3dm_drive::Counts c = la3dm_drive::cells(dims3, member.data(), seeds, n_seeds, targets, n_targets, p->members, p->n_members,
+                                                     la3dm_region::drive_params(*p), out->cost, out->parent, out->of_member, out->target_cost,
+                                                     out->target_index);
+    if (info) *info = inf;
+    if (stats) *stats = la3dm_drive_stats{c.n_members, c.n_seeded, c.n_reached, c.max_cost, 0, 0, 0};
+}
+
 // ---- clusters of a region.  The host form below is the definition; the device kernels (csrc/devmap_clusters.h) reproduce
 // it bit for bit.  box's classes (and the list) give the members; a flood fill from every unlabelled member in ascending
 // flat order numbers the clusters by their smallest index; the kept ones are renumbered in that order; one pass over the

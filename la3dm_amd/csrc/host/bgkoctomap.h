@@ -543,6 +543,21 @@ public:
     void travel(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, const la3dm_travel_params &p,
                 const uint32_t *targets, uint32_t n_targets, const la3dm_travel_out &out, la3dm_travel_stats *stats = nullptr,
                 la3dm_region_info *info = nullptr) const;
+    /// Drive over box's region (contract: include/la3dm_hip.h, la3dm_devmap_drive_host): cost[v] = the least cost of a
+    /// ground route from any seed to v over the MEMBER voxels — those of the list p.members or, with p.footing set, the
+    /// voxels footing(lo, dims, *p.footing) lists — by moves to one of the 4 or 8 horizontal neighbours that climb or
+    /// drop at most p.step voxels and cost p.move_cost plus p.climb_up / p.climb_down per voxel of height;
+    /// LA3DM_DRIVE_NONE for a non-member and where no walk of at most p.max_cost exists.  A seed or target stands for the
+    /// highest member at most p.snap voxels below it.  out.parent (may be null) = the code of the offset to the member a
+    /// least-cost walk came from, 40 at a seed, 255 where unreached; out.of_member = the cost per list entry;
+    /// out.target_cost / out.target_index = the cost at the targets' members and those members; stats (may be null) = the
+    /// members, the seeded and reached ones, the largest finite cost, and the device form's diagnostics.  Bad arguments
+    /// throw std::invalid_argument.  A device-resident map relaxes bricks of the region on the device (no mirror refresh;
+    /// in footing mode footing's kernels feed it without a list); a host-mode map runs its own footing and
+    /// host/drive_cells.h: that form is the definition, and both give the same integers.
+    void drive(const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds, const la3dm_drive_params *p,
+               const uint32_t *targets, uint32_t n_targets, const la3dm_drive_out *out, la3dm_drive_stats *stats = nullptr,
+               la3dm_region_info *info = nullptr) const;
     /// Clusters over box's region (contract: include/la3dm_hip.h, la3dm_devmap_clusters_host): the maximal sets of members
     /// — voxels with a class in p.member_mask, all of them or those of the list p.members — connected under p.connectivity
     /// inside tiles of p.tile voxels (0: untiled); those with fewer than p.min_size members are dropped, the others

@@ -481,6 +481,14 @@ int la3dm_map_travel(const la3dm_map *m, const float *lo3, const uint32_t *dims3
         return 0;)
 }
 
+int la3dm_map_drive(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const uint32_t *seeds, uint32_t n_seeds,
+                    const la3dm_drive_params *params, const uint32_t *targets, uint32_t n_targets, const la3dm_drive_out *out,
+                    la3dm_drive_stats *stats, la3dm_region_info *info) {
+    GUARD(
+        m->map->drive(lo3, dims3, seeds, n_seeds, params, targets, n_targets, out, stats, info);
+        return 0;)
+}
+
 int la3dm_map_clusters(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_clusters_params *params,
                        const la3dm_clusters_out *out, uint32_t *n_found, la3dm_clusters_stats *stats, la3dm_region_info *info) {
     GUARD(

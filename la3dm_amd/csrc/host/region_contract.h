@@ -12,6 +12,7 @@
 #include <string>
 
 #include "../../../include/la3dm_hip.h"
+#include "drive_cells.h"
 #include "footing_cells.h"
 
 #if defined(__HIPCC__)
@@ -418,6 +419,48 @@ inline Query footing_query(const la3dm_footing_params &p) {
 
 inline la3dm_footing::Params footing_params(const la3dm_footing_params &p) {
     return la3dm_footing::Params{p.support_mask, p.clear_mask, p.headroom, p.radius, p.step, p.min_support};
+}
+
+// ---- drive (contract: include/la3dm_hip.h, la3dm_devmap_drive_host) ----
+static_assert(LA3DM_DRIVE_MAX_STEP == LA3DM_FOOTING_MAX_STEP && LA3DM_DRIVE_MAX_STEP == la3dm_drive::kMaxStep && LA3DM_DRIVE_NONE == la3dm_drive::kNone,
+              "a move climbs what footing calls climbable; host/drive_cells.h states the two constants again");
+constexpr Query kDrive = {LA3DM_DRIVE_MAX_CELLS, "dims: more than LA3DM_DRIVE_MAX_CELLS (2^28) voxels in the region rounded up to whole bricks", false, kPadNone, "",
+                          LA3DM_DRIVE_BRICK};
+
+// the checks of drive's own arguments and buffers, all before the region's (`member` as in resolve); footing mode goes on
+// with footing_check(p->footing, 0, false, member)
+inline std::string drive_check(const la3dm_drive_params *p, uint32_t n_seeds, uint32_t n_targets, bool has_seeds, bool has_targets,
+                               const la3dm_drive_out *out, const char *member) {
+    if (!p) return "params is NULL";
+    if (p->connectivity != 4 && p->connectivity != 8) return "connectivity must be 4 or 8";
+    if (p->step > LA3DM_DRIVE_MAX_STEP) return "step must not exceed LA3DM_DRIVE_MAX_STEP (4)";
+    if (p->snap > LA3DM_DRIVE_MAX_SNAP) return "snap must not exceed LA3DM_DRIVE_MAX_SNAP (32)";
+    for (int k = 0; k < 2; ++k)
+        if (p->move_cost[k] == 0 || p->move_cost[k] > LA3DM_TRAVEL_MAX_MOVE) return "move_cost: both entries must lie in [1, LA3DM_TRAVEL_MAX_MOVE (2^16)]";
+    if (p->climb_up > LA3DM_TRAVEL_MAX_MOVE) return "climb_up must not exceed LA3DM_TRAVEL_MAX_MOVE (2^16)";
+    if (p->climb_down > LA3DM_TRAVEL_MAX_MOVE) return "climb_down must not exceed LA3DM_TRAVEL_MAX_MOVE (2^16)";
+    if (p->max_cost == 0 || p->max_cost > LA3DM_TRAVEL_MAX_COST) return "max_cost must lie in [1, LA3DM_TRAVEL_MAX_COST (2^31)]";
+    if (p->n_members > LA3DM_DRIVE_MAX_MEMBERS) return "n_members: more than LA3DM_DRIVE_MAX_MEMBERS (2^28) entries";
+    if (n_seeds > LA3DM_DRIVE_MAX_SEEDS) return "n_seeds: more than LA3DM_DRIVE_MAX_SEEDS (2^20) seeds";
+    if (n_targets > (1u << 28)) return "n_targets: more than 2^28 targets";
+    if (n_seeds > 0 && !has_seeds) return "seeds is NULL with n_seeds > 0";
+    if (n_targets > 0 && !has_targets) return "targets is NULL with n_targets > 0";
+    if (p->n_members > 0 && !p->members) return "members is NULL with n_members > 0";
+    if (p->footing && p->members) return "footing and members are both set: members must be NULL and n_members 0 in footing mode";
+    if (!p->footing && !p->members) return "footing and members are both NULL: one of the two modes must be chosen";
+    if (!out) return "out is NULL";
+    const std::string o = std::string("out") + member;
+    if (out->of_member && p->footing) return o + "of_member is set in footing mode";
+    if (out->of_member && p->n_members == 0) return o + "of_member is set with n_members = 0";
+    if (!out->cost && !out->of_member && !out->target_cost) return o + "cost, " + o + "of_member or " + o + "target_cost must not be NULL";
+    if (out->target_cost && n_targets == 0) return o + "target_cost is set with n_targets = 0";
+    if (out->target_index && n_targets == 0) return o + "target_index is set with n_targets = 0";
+    if (!out->target_cost && n_targets > 0) return o + "target_cost must not be NULL with n_targets > 0";
+    return "";
+}
+
+inline la3dm_drive::Params drive_params(const la3dm_drive_params &p) {
+    return la3dm_drive::Params{p.connectivity, p.step, p.snap, {p.move_cost[0], p.move_cost[1]}, p.climb_up, p.climb_down, p.max_cost};
 }
 
 // the checks of clusters' own arguments and buffers, all before the region's; `out` may be null
