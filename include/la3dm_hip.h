@@ -255,8 +255,18 @@ int la3dm_bgklv_scan_device(la3dm_ctx *ctx, const la3dm_lv_scan *scan, void *str
  * HIP 7.2 runtime, still one marker packet ahead of the kernel (measured: DESIGN section 5,
  * profiles/step_gap).  The GP and BGK-LV scans, whose dominant step is several launches, record
  * one event before and one after them (two marker packets on the stream).
- * This call waits for the events, writes the elapsed milliseconds of each scan call since the
- * last call (oldest first, at most cap; *n_out = how many there were) and resets the list. */
+ * The one-launch BGK scan (bgk_predict_fuse_t1: block_depth 3, full blocks) uses no event at
+ * "time_kernel" 1: a plain launch of an instance of the kernel that reads the device's wall clock
+ * as each wave enters and leaves and keeps the stamps in a record owned by the context, so a timed
+ * step puts nothing but the kernel on the stream.  Its figure is FIRST WAVE IN TO LAST WAVE OUT: it
+ * leaves out the dispatch set-up before the first wave and the end-of-kernel cache write-back after
+ * the last, which an event pair or a kernel trace includes (1.1 - 1.5 us on small grids); the stamped
+ * instance is itself about 2 us slower on the 200 k-ray scan, where its figure reads 0.5 us above the
+ * event pair's (profiles/kernel_stamps).  "time_kernel" 2 times that scan with the event pair as well
+ * (every other scan: the same as 1); so does 1 on a device that reports no wall-clock rate.
+ * This call waits for the timed launches, writes the elapsed milliseconds of each scan call since
+ * the last call (oldest first whichever way each was timed, at most cap; *n_out = how many there
+ * were) and resets the list.  Setting "time_kernel" drops what was timed and not read. */
 int la3dm_kernel_times(la3dm_ctx *ctx, float *ms, uint32_t cap, uint32_t *n_out);
 
 /* Diagnostics used by the parity tests: evaluate one primitive of the device

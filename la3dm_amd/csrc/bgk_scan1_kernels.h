@@ -23,7 +23,7 @@ namespace la3dm_dev {
 // nbr_range and label_seq are not read.  Full blocks only (the host verifies it from the leaf count), tpb_shift 0 or more,
 // one descriptor per block (desc_shift is not read: the host takes this path at block_depth 3 only).
 template <int kTrig>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) void bgk_predict_fuse_t1(BgkArgs a) {
+__device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     __shared__ __attribute__((aligned(16))) unsigned char s_lds[5120];
     const uint32_t task = bgk_task_of_workgroup(a);
     if (task >= a.n_tasks) return;
@@ -283,6 +283,37 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) v
             a.state[lw] = 0;
         }
     }
+}
+
+// the untimed launch: the tile body and nothing else
+template <int kTrig>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) void bgk_predict_fuse_t1(BgkArgs a) {
+    bgk_scan1_tile<kTrig>(a);
+}
+
+// One record of stamps per launch, all zero before the launch (la3dm_ctx.h: the stamp pool): kStampSlots entry stamps of
+// 8 bytes side by side, then kStampSlots exit stamps of 8 bytes, each on a 128-byte line of its own.
+constexpr uint32_t kStampSlots = 64, kStampExitStride = 16;   // (stride in 8-byte words)
+constexpr uint32_t kStampRecordBytes = 8u * (kStampSlots + kStampSlots * kStampExitStride);
+
+// "time_kernel" 1: the same tile body between two reads of the device's constant-rate wall clock, so that the kernel's time
+// needs no event and no packet beside the kernel's own.  Entry: each of the first kStampSlots workgroups stores its stamp in a
+// slot of its own (the host takes the least of the slots that were written).  Exit, on EVERY path out of the body (the early
+// returns of bgk_scan1_tile come back here): one atomicMax without a return value per wave, on exit slot blockIdx.x mod
+// kStampSlots (the host takes the greatest).  The exit slots are shards that must not share a line: atomics on one 128-byte
+// line queue up behind each other wherever in the line they land — with the 64 slots side by side (four lines) a grid of
+// 40 000 waves was 40 us longer and the 20 000-ray scan took 101 us instead of 36; a line per slot costs nothing that can be
+// measured (profiles/kernel_stamps/README.md).  The clock reads and the entry stores are free.  The stamps leave through
+// `stamps` only; nothing the scan computes depends on them.
+template <int kTrig>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) void bgk_predict_fuse_t1s(BgkArgs a, unsigned long long *stamps) {
+    const unsigned long long t_in = wall_clock64();
+    if (blockIdx.x < kStampSlots && threadIdx.x == 0) stamps[blockIdx.x] = t_in;
+    bgk_scan1_tile<kTrig>(a);
+    const unsigned long long t_out = wall_clock64();
+    uint32_t lane = threadIdx.x;
+    asm volatile("" : "+v"(lane));  // (compared again here: the entry's comparison is not kept in registers across the body)
+    if (lane == 0) atomicMax(stamps + kStampSlots + kStampExitStride * (blockIdx.x & (kStampSlots - 1u)), t_out);
 }
 
 }  // namespace la3dm_dev

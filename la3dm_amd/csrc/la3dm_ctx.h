@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <utility>
 #include <vector>
@@ -46,8 +47,15 @@ struct la3dm_ctx {
         hipEvent_t first = nullptr, second = nullptr;
         unsigned flags = 0;  // what hipEventCreateWithFlags was given
     };
-    std::vector<EvPair> ev_pool;  // start / stop events of the dominant kernel, one pair per *_scan_device call (KernelTimer below)
+    std::vector<EvPair> ev_pool;  // start / stop events of the dominant kernel, one pair per *_scan_device call timed by events (KernelTimer below)
     size_t ev_used = 0;
+    // stamp records of the calls timed from inside the kernel (bgk_predict_fuse_t1s; stamps_acquire below): chunks of
+    // kStampChunkRecords records that never move, all zero except the records handed out since the last drain
+    std::vector<unsigned long long *> stamp_chunks;
+    size_t stamp_used = 0;
+    std::vector<hipStream_t> stamp_streams;  // the streams those launches went to (what a drain waits for)
+    std::vector<uint8_t> timed_form;         // one entry per timed call since the last drain, oldest first: 0 = the next event pair, 1 = the next stamp record
+    int wall_clock_khz = 0;                  // hipDeviceAttributeWallClockRate, read once in la3dm_create (0: not available, stamped launches fall back to events)
     // scratch (device-pointer path)
     Arena pts_scaled, nbr_range, blk_desc, label_seq;
     Arena nbr_finite, blk_poison;  // la3dm_bgk_scan_device, two launches: the neighbour table without neighbours that hold a point at no finite distance; one flag per test block
@@ -90,13 +98,24 @@ static inline int arena_reserve(la3dm_ctx *ctx, Arena &a, size_t bytes) {
     return LA3DM_OK;
 }
 
-// ---- kernel timing (option "time_kernel"): the start / stop events of one *_scan_device call's dominant kernel ----
-// Two forms.  Marker form (timer_begin / timer_end round any number of launches): each is a hipEventRecord, a packet of
-// its own on the stream.  Dispatch-bound form (one launch): timer_acquire(.., true), then start and stop are handed to
-// hipExtLaunchKernelGGL.  The stop event is then the completion of the kernel's own dispatch packet, no packet of its own;
-// the start event is still a marker ahead of the kernel with the HIP 7.2 runtime (profiles/step_gap: 3.9 us per step on
-// configs[1], against 7.5 us for the two markers; a launch with the stop event alone costs nothing, but hipEventElapsedTime
-// of that event with itself is 0, so it gives no kernel time).
+// ---- kernel timing (option "time_kernel"): the time of one *_scan_device call's dominant kernel ----
+// Three forms; la3dm_kernel_times returns them in call order whatever the mix (la3dm_ctx::timed_form).
+// Marker form (timer_begin / timer_end round any number of launches): each is a hipEventRecord, a packet of its own on the
+// stream.
+// Dispatch-bound form (one launch): timer_acquire(.., true), then start and stop are handed to hipExtLaunchKernelGGL.  The
+// stop event is then the completion of the kernel's own dispatch packet, no packet of its own; the start event is still a
+// marker ahead of the kernel with the HIP 7.2 runtime (profiles/step_gap: 3.9 us per step on configs[1], against 7.5 us for
+// the two markers; a launch with the stop event alone costs nothing, but hipEventElapsedTime of that event with itself is 0,
+// so it gives no kernel time).  "time_kernel" 1 uses it for every single launch but the one-launch BGK scan, "time_kernel" 2
+// for that one too (the two clocks side by side in one process; also what 1 means where the device reports no wall-clock rate).
+// Stamped form (the one-launch BGK scan at "time_kernel" 1): a plain hipLaunchKernelGGL of bgk_predict_fuse_t1s, which reads
+// the device's wall clock as each wave enters and leaves and writes the stamps into a record of the context's pool
+// (stamps_acquire) — no event, no packet but the kernel's own, no stream operation per launch.  The time is first wave in to
+// last wave out: (greatest exit stamp - least entry stamp) / hipDeviceAttributeWallClockRate.  It leaves out what an event or
+// a kernel trace includes on either side, the command processor's dispatch set-up and the end-of-kernel cache write-back: on
+// small grids it reads 1.1 - 1.5 us below the event pair.  On configs[1] it reads 0.5 us ABOVE it (59.74 against 59.26 us),
+// because the stamped instance is itself about 2 us slower than the plain one: 35 more VALU-class instructions per tile, most of
+// them scalars parked in VGPR lanes, in a kernel whose VALU is 95 % busy (profiles/kernel_stamps/README.md).
 struct KernelTimer {
     hipEvent_t start = nullptr, stop = nullptr;  // both null: "time_kernel" is 0, nothing to do
     explicit operator bool() const { return start != nullptr; }
@@ -125,9 +144,93 @@ static inline int timer_acquire(la3dm_ctx *ctx, KernelTimer &t, bool dispatch_bo
     if (!p.first) HIP_TRY(ctx, hipEventCreateWithFlags(&p.first, flags));
     if (!p.second) HIP_TRY(ctx, hipEventCreateWithFlags(&p.second, flags));
     ++ctx->ev_used;
+    ctx->timed_form.push_back(0);
     t.start = p.first;
     t.stop = p.second;
     return LA3DM_OK;
+}
+
+// ---- the stamp pool ----
+// A record is kStampRecordWords 8-byte words (bgk_scan1_kernels.h: 64 entry slots side by side, then 64 exit slots on a
+// 128-byte line each), zero when it is handed out.  The pool is zeroed in bulk — a chunk when it is created, the used records
+// when they are drained — never per launch: a memset or copy per launch would put back on the stream the packet the stamped
+// form exists to remove.  Growing adds a chunk (one hipMalloc and one memset per kStampChunkRecords launches between two
+// drains, the first of them when "time_kernel" is set); the chunks before it stay where launches in flight write them.
+constexpr size_t kStampEntrySlots = 64, kStampExitSlots = 64, kStampExitStrideWords = 16;
+constexpr size_t kStampRecordWords = kStampEntrySlots + kStampExitSlots * kStampExitStrideWords, kStampChunkRecords = 1024;   // 8.5 KiB, 8.5 MiB
+
+// zero records [0, n) of the pool, from the context's own stream, and wait for it
+static inline int stamps_zero(la3dm_ctx *ctx, size_t n) {
+    for (size_t c = 0; c * kStampChunkRecords < n; ++c) {
+        const size_t recs = std::min(n - c * kStampChunkRecords, kStampChunkRecords);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->stamp_chunks[c], 0, recs * kStampRecordWords * 8, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return LA3DM_OK;
+}
+
+// chunks for `records` records (grow only).  Blocks the host until a new chunk is zero; touches no caller stream.
+static inline int stamps_reserve(la3dm_ctx *ctx, size_t records) {
+    while (ctx->stamp_chunks.size() * kStampChunkRecords < records) {
+        void *p = nullptr;
+        const size_t bytes = kStampChunkRecords * kStampRecordWords * 8;
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+            ctx->err = std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e);
+            return LA3DM_ERR_OOM;
+        }
+        ctx->stamp_chunks.push_back((unsigned long long *)p);
+        HIP_TRY(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return LA3DM_OK;
+}
+
+// the next record of the pool for a launch on `stream`
+static inline int stamps_acquire(la3dm_ctx *ctx, unsigned long long *&rec, hipStream_t stream) {
+    int rc = stamps_reserve(ctx, ctx->stamp_used + 1);
+    if (rc != LA3DM_OK) return rc;
+    rec = ctx->stamp_chunks[ctx->stamp_used / kStampChunkRecords] + (ctx->stamp_used % kStampChunkRecords) * kStampRecordWords;
+    ++ctx->stamp_used;
+    ctx->timed_form.push_back(1);
+    if (std::find(ctx->stamp_streams.begin(), ctx->stamp_streams.end(), stream) == ctx->stamp_streams.end()) ctx->stamp_streams.push_back(stream);
+    return LA3DM_OK;
+}
+
+// wait for the stamped launches since the last drain; host != nullptr: their records, oldest first
+static inline int stamps_collect(la3dm_ctx *ctx, std::vector<unsigned long long> *host) {
+    for (hipStream_t s : ctx->stamp_streams) HIP_TRY(ctx, hipStreamSynchronize(s));
+    if (!host) return LA3DM_OK;
+    host->resize(ctx->stamp_used * kStampRecordWords);
+    for (size_t c = 0; c * kStampChunkRecords < ctx->stamp_used; ++c) {
+        const size_t recs = std::min(ctx->stamp_used - c * kStampChunkRecords, kStampChunkRecords);
+        HIP_TRY(ctx, hipMemcpy(host->data() + c * kStampChunkRecords * kStampRecordWords, ctx->stamp_chunks[c], recs * kStampRecordWords * 8, hipMemcpyDeviceToHost));
+    }
+    return LA3DM_OK;
+}
+
+// forget every timed call since the last drain: the event pairs go back to their pool, the used stamp records to zero (the
+// caller has waited for the launches that write them: stamps_collect)
+static inline int timing_reset(la3dm_ctx *ctx) {
+    if (ctx->stamp_used) {
+        int rc = stamps_zero(ctx, ctx->stamp_used);
+        if (rc != LA3DM_OK) return rc;
+    }
+    ctx->stamp_used = 0;
+    ctx->stamp_streams.clear();
+    ctx->ev_used = 0;
+    ctx->timed_form.clear();
+    return LA3DM_OK;
+}
+
+// milliseconds from first wave in to last wave out of one record (NaN: no wave wrote it)
+static inline float stamps_ms(const unsigned long long *rec, int wall_clock_khz) {
+    unsigned long long t_in = ~0ull, t_out = 0;
+    for (size_t i = 0; i < kStampEntrySlots; ++i)
+        if (rec[i] != 0 && rec[i] < t_in) t_in = rec[i];   // (a grid of fewer than 64 workgroups leaves entry slots at zero)
+    for (size_t i = 0; i < kStampExitSlots; ++i) t_out = std::max(t_out, rec[kStampEntrySlots + kStampExitStrideWords * i]);
+    if (t_in == ~0ull || t_out < t_in) return __builtin_nanf("");
+    return (float)((double)(t_out - t_in) / (double)wall_clock_khz);
 }
 static inline int timer_begin(la3dm_ctx *ctx, KernelTimer &t, hipStream_t stream) {
     int rc = timer_acquire(ctx, t, false);

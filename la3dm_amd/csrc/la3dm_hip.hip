@@ -326,6 +326,9 @@ int la3dm_create(const la3dm_params *params, la3dm_ctx **out) {
     if ((e = hipSetDevice(ctx->device)) != hipSuccess) return fail("hipSetDevice", e);
     if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
         return fail("hipStreamCreate", e);
+    // ticks per millisecond of the clock bgk_predict_fuse_t1s stamps with; where the device does not say, no launch is stamped
+    if (hipDeviceGetAttribute(&ctx->wall_clock_khz, hipDeviceAttributeWallClockRate, ctx->device) != hipSuccess || ctx->wall_clock_khz < 0)
+        ctx->wall_clock_khz = 0;
     std::vector<float4> lut4(ctx->lut_count);
     for (uint32_t i = 0; i < ctx->lut_count; ++i)
         lut4[i] = make_float4(params->lut_xyz[3 * i], params->lut_xyz[3 * i + 1], params->lut_xyz[3 * i + 2], 0.0f);
@@ -355,6 +358,7 @@ void la3dm_destroy(la3dm_ctx *ctx) {
         if (p.first) (void)hipEventDestroy(p.first);
         if (p.second) (void)hipEventDestroy(p.second);
     }
+    for (unsigned long long *c : ctx->stamp_chunks) (void)hipFree(c);
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -432,9 +436,13 @@ int la3dm_set_option(la3dm_ctx *ctx, const char *name, int value) {
         ctx->opt_l_dense_add = value;
         return LA3DM_OK;
     }
-    if (!strcmp(name, "time_kernel")) {
+    if (!strcmp(name, "time_kernel")) {  // 0 off; 1 on, the one-launch BGK scan stamped from inside the kernel; 2 (any other value) on, events for every kernel
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        int rc = stamps_collect(ctx, nullptr);   // what was timed and not read is dropped: stamped launches still in flight first
+        if (rc == LA3DM_OK) rc = timing_reset(ctx);
+        if (rc != LA3DM_OK) return rc;
         ctx->opt_time_kernel = value;
-        ctx->ev_used = 0;
+        if (value == 1 && ctx->wall_clock_khz > 0) return stamps_reserve(ctx, 1);  // the first chunk here, not inside what the caller is about to time
         return LA3DM_OK;
     }
     ctx->err = std::string("la3dm_set_option: unknown option ") + name;
@@ -575,10 +583,15 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     a.occupied_thresh = ctx->p.occupied_thresh;
     a.var_thresh = ctx->p.var_thresh;
     dim3 grid((a.n_tasks + kWavesPerWG - 1) / kWavesPerWG), block(kWavesPerWG * kWave);
-    // "time_kernel" 1: the start / stop events go to the launch itself (hipExtLaunchKernelGGL, flags 0: in stream order, the next
-    // scan reads what this one wrote) — no marker packet after the kernel, see KernelTimer for the one before it; 0: the plain launch
+    // "time_kernel" on: the start / stop events go to the launch itself (hipExtLaunchKernelGGL, flags 0: in stream order, the next
+    // scan reads what this one wrote) — no marker packet after the kernel, see KernelTimer for the one before it; 0: the plain launch.
+    // The one launch at "time_kernel" 1 takes neither: the plain launch of the instance that stamps itself into a record of the pool.
     KernelTimer tm;
-    if ((rc = timer_acquire(ctx, tm, true)) != LA3DM_OK) return rc;
+    unsigned long long *stamps = nullptr;
+    static_assert(kStampRecordWords * 8 == kStampRecordBytes, "the pool's record is the kernel's");
+    if (one_launch && ctx->opt_time_kernel == 1 && ctx->wall_clock_khz > 0) rc = stamps_acquire(ctx, stamps, stream);
+    else rc = timer_acquire(ctx, tm, true);
+    if (rc != LA3DM_OK) return rc;
 #define LAUNCH_BGK_AS(K)                                                                                               \
     if (tm) hipExtLaunchKernelGGL((K), grid, block, (uint32_t)ctx->opt_lds_pad, stream, tm.start, tm.stop, 0u, a);     \
     else hipLaunchKernelGGL((K), grid, block, (size_t)ctx->opt_lds_pad, stream, a);
@@ -592,7 +605,14 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     if (sum_f64) {
         grid = dim3(a.n_tasks);
         block = dim3(kWave);
-        if (one_launch) {
+        if (stamps) {
+            switch (ctx->opt_fast_trig) {
+            case 1: hipLaunchKernelGGL(bgk_predict_fuse_t1s<1>, grid, block, (size_t)ctx->opt_lds_pad, stream, a, stamps); break;
+            case 2: hipLaunchKernelGGL(bgk_predict_fuse_t1s<2>, grid, block, (size_t)ctx->opt_lds_pad, stream, a, stamps); break;
+            case 3: hipLaunchKernelGGL(bgk_predict_fuse_t1s<3>, grid, block, (size_t)ctx->opt_lds_pad, stream, a, stamps); break;
+            default: hipLaunchKernelGGL(bgk_predict_fuse_t1s<0>, grid, block, (size_t)ctx->opt_lds_pad, stream, a, stamps); break;
+            }
+        } else if (one_launch) {
             LAUNCH_BGK(bgk_predict_fuse_t1)
         } else if (use_tables) {
             if (full_blocks) {  // no pruned block in this scan: the kernel without the general path
@@ -1109,16 +1129,24 @@ int la3dm_bgklv_scan_host(la3dm_ctx *ctx, const la3dm_lv_scan *s, la3dm_bgk_coun
 int la3dm_kernel_times(la3dm_ctx *ctx, float *ms, uint32_t cap, uint32_t *n_out) {
     if (!ctx || !n_out) return LA3DM_ERR_ARG;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t n = (uint32_t)ctx->ev_used;
+    const uint32_t n = (uint32_t)ctx->timed_form.size();
+    std::vector<unsigned long long> recs;   // the stamped calls' records, once their launches are through
+    int rc = stamps_collect(ctx, &recs);
+    if (rc != LA3DM_OK) return rc;
+    size_t ev = 0, st = 0;                  // the two forms may alternate: each entry takes the next pair or record of its own pool
     for (uint32_t i = 0; i < n; ++i) {
-        HIP_TRY(ctx, hipEventSynchronize(ctx->ev_pool[i].second));
         float t = 0.f;
-        HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->ev_pool[i].first, ctx->ev_pool[i].second));
+        if (ctx->timed_form[i]) {
+            t = stamps_ms(recs.data() + kStampRecordWords * st++, ctx->wall_clock_khz);
+        } else {
+            const la3dm_ctx::EvPair &p = ctx->ev_pool[ev++];
+            HIP_TRY(ctx, hipEventSynchronize(p.second));
+            HIP_TRY(ctx, hipEventElapsedTime(&t, p.first, p.second));
+        }
         if (ms && i < cap) ms[i] = t;
     }
     *n_out = n;
-    ctx->ev_used = 0;
-    return LA3DM_OK;
+    return timing_reset(ctx);
 }
 
 int la3dm_diag_sweep(la3dm_ctx *ctx, int what, uint32_t lo_bits, uint32_t hi_bits, uint64_t *mismatches) {
