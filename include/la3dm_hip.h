@@ -1377,6 +1377,74 @@ int la3dm_devmap_footing_host(la3dm_devmap *dm, const float *lo3, const uint32_t
 int la3dm_devmap_footing_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params,
                                 uint64_t cap, const la3dm_footing_out *d_out, uint64_t *n_found, la3dm_footing_stats *stats,
                                 la3dm_region_info *info);
+/* Surface: the exposed faces of the solid voxels of a region and an integer normal estimated from them, as an ordered
+ * list and (the faces) per voxel.
+ *   Region and lattice.  The region, anchor, lattice, info and flat index f = (i * ny + j) * nz + k are box's.
+ *   Classes.  cls(g) is what box would report for lattice voxel g, inside or outside the region: FREE 0, OCCUPIED 1,
+ *     UNKNOWN 2, MISSING 3, a BGK-LV map's UNCERTAIN 4.  Classes past the region's faces are read from the map, as frontier
+ *     and footing read theirs: the answer for a voxel does not depend on where the region's faces are.
+ *   Parameters (la3dm_surface_params).  solid_mask and open_mask hold the bits of stop_mask; smooth s, 0 ..
+ *     LA3DM_SURFACE_MAX_SMOOTH.
+ *   Definition.  The six directions are d = 0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z, with unit vectors e_d.
+ *     F_d(u)    = 1 when cls(u) is in solid_mask and cls(u + e_d) is in open_mask, else 0, for every voxel u of the
+ *       lattice, inside the region or not.
+ *     faces(u)  = sum over d of F_d(u) << d.
+ *     A surface voxel is a voxel of the region with faces != 0.
+ *     normal(v) = the sum over all u with |u - v|_inf <= s of (F_1 - F_0, F_3 - F_2, F_5 - F_4)(u): three int16, each at
+ *       most (2 s + 1)^3 = 729 in size.  It points from solid into open space; with s = 0 it is the voxel's own face
+ *       vector.  The sum of the face vectors of a voxelised patch is the area vector of the patch, so the windowed sum is
+ *       an unbiased normal up to the window's rim.  It may be (0, 0, 0) — a one-voxel pillar, a table top seen from both
+ *       sides —: callers treat that as "no normal".
+ *   Outputs.  *n_found = the number of surface voxels, whatever cap is.  out->index[cap] (uint32): the flat indices of the
+ *     first min(n, cap) surface voxels in ascending order; out->faces[cap] (uint8) and out->normal[3 cap] (int16) = the
+ *     same entries' face masks and normals; entries past them are not written.  out->dense_faces[nx ny nz] (uint8,
+ *     independent of cap) = faces of every voxel of the region, 0 where the voxel is not solid or not exposed: what a
+ *     caller gathers at nearest's index.  cap = 0 with out NULL, or with only dense_faces set, counts.  stats (a host
+ *     struct, may be NULL): n_solid = the voxels of the region with a class in solid_mask, n_surface = n, faces[d] = the
+ *     voxels of the region with F_d; the surface area is their sum times resolution^2.  On an empty map n = 0,
+ *     dense_faces = 0 and n_solid = nx ny nz when MISSING is in solid_mask, 0 when it is not.
+ *   Refused as a whole (LA3DM_ERR_ARG, a text that names the argument, nothing written, nothing reserved), in this
+ *     order: a NULL params; a mask that is 0 or has bits above 0x1F; masks that overlap; smooth above
+ *     LA3DM_SURFACE_MAX_SMOOTH; out->normal without out->index; cap > 0 with neither out->index nor out->faces; what box
+ *     refuses for lo and dims; a padded box that is too large or leaves the block-field range — the working box is the
+ *     region padded by p = s + 1 voxels on all six sides, (nx + 2 p, ny + 2 p, nz + 2 p); it is refused when it holds more
+ *     than LA3DM_SURFACE_MAX_CELLS voxels or when its block fields leave [0, 2^20); last a NULL n_found.
+ *   Integer arithmetic on classes throughout: the results equal the host form (BGKOctoMap::surface on a host-mode map,
+ *     host/surface_cells.h over the classes of the padded box) exactly.
+ *   Device form (csrc/devmap_surface.h): bit streams over the padded box, 32 voxels per word with k fastest — one pool
+ *     probe per padded voxel gives the solid and the open stream, a word pass the six face streams, the candidate words
+ *     and the counts, the map's scan and an emit kernel the list; with s > 0 a wave per candidate word sums the face
+ *     windows of the (2 s + 1)^2 columns round it in bit-sliced counters.  No atomic is used.  Working storage: eleven words
+ *     per 32 padded voxels — 11/8 byte per padded voxel — and 64 KB of partial counts, in a grow-only arena of the devmap
+ *     (released with it). */
+#define LA3DM_SURFACE_MAX_CELLS  (1u << 28)
+#define LA3DM_SURFACE_MAX_SMOOTH 4
+typedef struct la3dm_surface_params {
+    uint32_t solid_mask;   /* classes that make a voxel solid */
+    uint32_t open_mask;    /* classes a face may look into */
+    uint32_t smooth;       /* s: half width of the normal's window in voxels, 0 .. LA3DM_SURFACE_MAX_SMOOTH */
+} la3dm_surface_params;
+typedef struct la3dm_surface_out {
+    uint32_t *index;         /* [cap] or NULL */
+    uint8_t  *faces;         /* [cap] or NULL */
+    int16_t  *normal;        /* [3 cap] or NULL; needs index */
+    uint8_t  *dense_faces;   /* [nx ny nz] or NULL, independent of cap */
+} la3dm_surface_out;
+typedef struct la3dm_surface_stats {
+    uint64_t n_solid;      /* voxels of the region with a class in solid_mask */
+    uint64_t n_surface;    /* surface voxels: n */
+    uint64_t faces[6];     /* exposed faces per direction -x, +x, -y, +y, -z, +z */
+} la3dm_surface_stats;
+/* host pointers: the launches, download of min(*n_found, cap) entries and the dense array, synchronise — on the map's
+ * stream */
+int la3dm_devmap_surface_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_surface_params *params,
+                              uint64_t cap, const la3dm_surface_out *out, uint64_t *n_found, la3dm_surface_stats *stats,
+                              la3dm_region_info *info);
+/* device pointers (out's arrays already in HBM on the map's device, index 4-byte and normal 2-byte aligned; lo3, dims3,
+ * params, n_found, stats and info stay host-side); returns when the results are complete */
+int la3dm_devmap_surface_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_surface_params *params,
+                                uint64_t cap, const la3dm_surface_out *d_out, uint64_t *n_found, la3dm_surface_stats *stats,
+                                la3dm_region_info *info);
 /* Drive: the least cost of a ground route from seed voxels over a set of MEMBER voxels of a region — the voxels footing
  * finds —, with moves that climb or drop up to `step` voxels, and a parent per voxel to drive along.  travel routes a
  * flying point through a class mask; drive routes a ground robot over the places where it can stand.

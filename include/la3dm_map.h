@@ -193,6 +193,17 @@ int la3dm_map_nearest_points(const la3dm_map *m, const float *lo3, const uint32_
  * host-mode maps on the CPU; the results are identical. */
 int la3dm_map_footing(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_footing_params *params, uint64_t cap,
                       const la3dm_footing_out *out, uint64_t *n_found, la3dm_footing_stats *stats, la3dm_region_info *info);
+/* BGKOctoMap::surface: the exposed faces and integer normals of box's region.  A voxel whose class is in
+ * params->solid_mask has face d (0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z) when its neighbour in that direction has a class
+ * in params->open_mask; a surface voxel has at least one.  *n_found = their number; out->index / faces / normal = the flat
+ * indices of the first min(*n_found, cap) in ascending order, their face masks and their normals — the sum of the face
+ * vectors of every voxel within params->smooth voxels (Chebyshev), three int16 pointing into open space, possibly zero —;
+ * out->dense_faces (optional) = the face mask of every voxel of the region; stats (may be NULL) = the solid voxels, the
+ * surface voxels and the faces per direction.  cap = 0 only counts.  Contract, limits and refusals: include/la3dm_hip.h
+ * (la3dm_devmap_surface_host).  Device-resident maps run the query on the device pool without a mirror refresh, host-mode
+ * maps on the CPU; the results are identical. */
+int la3dm_map_surface(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_surface_params *params, uint64_t cap,
+                      const la3dm_surface_out *out, uint64_t *n_found, la3dm_surface_stats *stats, la3dm_region_info *info);
 /* BGKOctoMap::score_paths: cost and clearance of many candidate trajectories.  Every path of ways3 (n_paths x n_way x 3
  * floats, world frame; a shorter path repeats its last waypoint) is walked voxel by voxel through box's region against d2 =
  * distance_field(lo, dims, obstacle_mask, max(1, clearance, soft_radius)); out->cost (mandatory) [n_paths] = travel's cost

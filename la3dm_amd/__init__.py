@@ -9,6 +9,7 @@ from .bgkoctomap import PATH_BLOCKED, PATH_LEFT, PATH_TRUNCATED, PATH_INVALID, P
 from .bgkoctomap import PATHS_MAX_STEPS, PATHS_MAX_WAY, PATHS_MAX_PATHS, PATHS_MAX_WAYPOINTS  # noqa: F401
 from .bgkoctomap import NEAREST_NONE, NEAREST_MAX_RADIUS  # noqa: F401
 from .bgkoctomap import FOOTING_MAX_CELLS, FOOTING_MAX_HEADROOM, FOOTING_MAX_RADIUS, FOOTING_MAX_STEP, footprint_cells  # noqa: F401
+from .bgkoctomap import SURFACE_MAX_CELLS, SURFACE_MAX_SMOOTH, surface_quads  # noqa: F401
 from .bgkoctomap import REACH_NONE, REACH_MAX_CELLS, REACH_MAX_STEPS, REACH_MAX_SEEDS, REACH_BATCH  # noqa: F401
 from .bgkoctomap import TRAVEL_NONE, TRAVEL_MAX_CELLS, TRAVEL_MAX_COST, TRAVEL_MAX_MOVE, TRAVEL_MAX_PENALTY, TRAVEL_MAX_SEEDS  # noqa: F401
 from .bgkoctomap import TRAVEL_MAX_ROUNDS, TRAVEL_BRICK, TRAVEL_INNER, TRAVEL_BATCH, follow_parents  # noqa: F401

@@ -125,6 +125,21 @@ class FootingStats(_Stats):   # la3dm_footing_stats
     _fields_ = [(k, C.c_uint32) for k in ("n_stand", "n_body", "n_foot", "disc_cells")]
 
 
+class SurfaceParams(C.Structure):  # la3dm_surface_params
+    _fields_ = [(k, C.c_uint32) for k in ("solid_mask", "open_mask", "smooth")]
+
+
+class SurfaceOut(C.Structure):   # la3dm_surface_out
+    _fields_ = [(k, C.c_void_p) for k in ("index", "faces", "normal", "dense_faces")]
+
+
+class SurfaceStats(_Stats):   # la3dm_surface_stats
+    _fields_ = [("n_solid", C.c_uint64), ("n_surface", C.c_uint64), ("faces", C.c_uint64 * 6)]
+
+    def as_dict(self):
+        return dict(n_solid=int(self.n_solid), n_surface=int(self.n_surface), face_count=tuple(int(v) for v in self.faces))
+
+
 class PathsParams(C.Structure):  # la3dm_paths_params
     _fields_ = [("obstacle_mask", C.c_uint32), ("clearance", C.c_uint32), ("soft_radius", C.c_uint32), ("penalty", C.c_uint32),
                 ("move_cost", C.c_uint32 * 3), ("max_steps", C.c_uint32)]
@@ -257,6 +272,7 @@ _NEAREST = [vp, vp, u32, u32, P(NearestOut), _INFO]
 _NEAREST_POINTS = [vp, vp, vp, u32, vp, u32, u32, P(NearestPointsOut), _INFO]
 # ... and so has footing
 _FOOTING = [vp, vp, P(FootingParams), u64, P(FootingOut), P(u64), P(FootingStats), _INFO]
+_SURFACE = [vp, vp, P(SurfaceParams), u64, P(SurfaceOut), P(u64), P(SurfaceStats), _INFO]
 # ... and drive: one row for its three forms
 _DRIVE = {f"la3dm_{form}": (cint, [vp, vp, vp, vp, u32, P(DriveParams), vp, u32, P(DriveOut), P(DriveStats), _INFO])
           for form in ("map_drive", "devmap_drive_host", "devmap_drive_device")}
@@ -312,6 +328,8 @@ HIP_API = {
     "la3dm_devmap_nearest_points_device": (cint, [vp] + _NEAREST_POINTS),
     "la3dm_devmap_footing_host": (cint, [vp] + _FOOTING),
     "la3dm_devmap_footing_device": (cint, [vp] + _FOOTING),
+    "la3dm_devmap_surface_host": (cint, [vp] + _SURFACE),
+    "la3dm_devmap_surface_device": (cint, [vp] + _SURFACE),
     **{n: sig for n, sig in _DRIVE.items() if n.startswith("la3dm_devmap_")},
     **_query_entries(of_map=False),
 }
@@ -374,6 +392,7 @@ MAP_API = {
     "la3dm_map_nearest": (cint, [vp] + _NEAREST),
     "la3dm_map_nearest_points": (cint, [vp] + _NEAREST_POINTS),
     "la3dm_map_footing": (cint, [vp] + _FOOTING),
+    "la3dm_map_surface": (cint, [vp] + _SURFACE),
     "la3dm_map_drive": _DRIVE["la3dm_map_drive"],
     **_query_entries(of_map=True),
 }

@@ -24,6 +24,7 @@ SCORE_MAX_CELLS, SCORE_MAX_POINTS, SCORE_MAX_POSES, SCORE_MAX_PAIRS, SCORE_MAX_R
 SCORE_HIT, SCORE_NEAR, SCORE_FAR, SCORE_OUTSIDE, SCORE_INVALID = range(5)   # LA3DM_SCORE_*: the columns of score_poses' counts
 NEAREST_NONE, NEAREST_MAX_RADIUS = 0xFFFFFFFF, 255   # LA3DM_NEAREST_*: nearest found no obstacle within the radius; the largest radius
 FOOTING_MAX_CELLS, FOOTING_MAX_HEADROOM, FOOTING_MAX_RADIUS, FOOTING_MAX_STEP = 1 << 28, 32, 8, 4   # LA3DM_FOOTING_MAX_*
+SURFACE_MAX_CELLS, SURFACE_MAX_SMOOTH = 1 << 28, 4   # LA3DM_SURFACE_MAX_*
 PATH_BLOCKED, PATH_LEFT, PATH_TRUNCATED, PATH_INVALID = 1, 2, 4, 8   # LA3DM_PATH_*: the bits of score_paths' flags
 PATH_NONE = 0xFFFFFFFF              # LA3DM_PATH_NONE: score_paths' stop of a walk that did not stop
 PATHS_MAX_STEPS, PATHS_MAX_WAY, PATHS_MAX_PATHS, PATHS_MAX_WAYPOINTS = 1 << 20, 1024, 1 << 20, 1 << 26   # LA3DM_PATHS_MAX_*
@@ -578,6 +579,59 @@ class BGKOctoMap:
             total = call(k, filled)
         if "index" in fields:
             out["index"] = filled["index"][:min(total, k)]
+        out.update(n=total, **stats.as_dict())
+        out.update(region)
+        return out
+
+    _SURFACE_FIELDS = dict(index=np.uint32, faces=np.uint8, normal=np.int16, dense_faces=np.uint8)
+
+    def surface(self, lo, dims, solid=("occupied",), open=("free",), smooth=0, fields=("index", "faces", "normal"), cap=None):
+        """The exposed faces and integer normals of the region of box(lo, dims).  A voxel whose class is in `solid` has face
+        d (0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z) when its neighbour in that direction has a class in `open`; a surface
+        voxel has at least one.  solid / open: names out of free / occupied / unknown / missing (/ uncertain on a BGK-LV map)
+        or an integer bit mask, as raycast_many's `stop`; they must not overlap.  Classes outside the region are read from
+        the map: the answer for a voxel does not depend on where the region's faces are.  Returns n = the number of surface
+        voxels and, as `fields` names them, index (uint32) = their flat indices (i * ny + j) * nz + k in ascending order,
+        faces (uint8) = their face masks, bit d for direction d, normal (int16, shape (n, 3)) = per listed voxel the sum of
+        the face vectors of every voxel within `smooth` voxels on every axis (0 .. 4) — it points from solid into open space,
+        is at most (2 smooth + 1)^3 in size per component and may be (0, 0, 0), which means "no normal"; normal needs index —,
+        dense_faces (uint8, shape dims) = the face mask of every voxel of the region, 0 where it is not solid or not
+        exposed; n_solid, n_surface, face_count = the solid voxels of the region, n, and the faces per direction (their sum
+        times resolution^2 is the surface area); plus origin, block_key, cell as box() returns them.  cap=None counts first
+        and then fills exactly n entries; an integer cap fills the first min(n, cap) and n is still the total.  At most 2^28
+        voxels in the region padded by smooth + 1 voxels on every side.  A device-resident map runs the query on the device
+        pool (no host mirror refresh); a host-mode map runs it on the CPU, with identical results."""
+        lo3, d3, d, cells, ok = self._region(lo, dims, lambda d: True)
+        fields = _want("surface", fields, self._SURFACE_FIELDS)
+        masks = [_class_mask(solid), _class_mask(open)]
+        _fit("surface: solid, open and smooth must fit 32 bits", masks + [smooth])
+        if cap is not None:
+            _fit("surface: cap must fit 64 bits", [cap], bits=64)
+        ok = ok and int(np.prod([v + 2 * (int(smooth) + 1) for v in d], dtype=object)) <= SURFACE_MAX_CELLS
+        params = _lib.SurfaceParams(masks[0], masks[1], int(smooth))
+        found, stats = C.c_uint64(0), _lib.SurfaceStats()
+        region = {}
+        listed = [k for k in ("index", "faces", "normal") if k in fields]
+
+        def call(k, arrays):
+            o = _out(_lib.SurfaceOut, arrays, null_empty=("index", "faces", "normal"))
+            region.update(self._region_call(self._M.la3dm_map_surface, lo3, d3, C.byref(params), k, C.byref(o) if arrays else None,
+                                            C.byref(found), C.byref(stats)))
+            return int(found.value)
+
+        out = {"dense_faces": np.empty(tuple(d) if ok else (1,), np.uint8)} if "dense_faces" in fields else {}
+        if cap is None:   # the two-call protocol: count (the dense array comes with this call), then fill exactly n
+            k = call(0, out)
+            filled = {}
+        else:
+            k = min(int(cap), cells if ok else 1) if listed else 0
+            filled = dict(out)
+        filled.update({f: np.empty((k, 3) if f == "normal" else k, self._SURFACE_FIELDS[f]) for f in listed})
+        total = k
+        if cap is not None or (k and listed):
+            total = call(k, filled)
+        for f in listed:
+            out[f] = filled[f][:min(total, k)]
         out.update(n=total, **stats.as_dict())
         out.update(region)
         return out
@@ -1245,6 +1299,37 @@ def footprint_cells(radius):
     if r < 0:
         raise ValueError("footprint_cells: radius must be >= 0")
     return sum(1 for di in range(-r, r + 1) for dj in range(-r, r + 1) if 0 < di * di + dj * dj <= r * r)
+
+
+def surface_quads(index, faces, dims):
+    """The exposed faces that surface() lists, as quads.  index, faces: surface's arrays; dims: the region's.  Returns
+    (corners int32 [F, 4, 3], direction uint8 [F], voxel uint32 [F]): one quad per set bit of faces, in list order and then
+    ascending direction d (0: -x, 1: +x, 2: -y, 3: +y, 4: -z, 5: +z); voxel = the flat index it belongs to.  Corners are in
+    voxel-corner units of the region — the world position is origin + (corner - 0.5) * resolution — and run
+    counter-clockwise seen from the open side: for a face along axis a with (b, c) = ((a + 1) % 3, (a + 2) % 3) the plane is
+    v_a + 1 for the positive direction and v_a for the negative, the (b, c) offsets (0, 0), (1, 0), (1, 1), (0, 1) for the
+    positive direction and in the reverse order for the negative.  Integers only."""
+    index = np.ascontiguousarray(index, np.uint32).reshape(-1)
+    faces = np.ascontiguousarray(faces, np.uint8).reshape(-1)
+    nx, ny, nz = (int(v) for v in dims)
+    if index.shape != faces.shape:
+        raise ValueError("surface_quads: index and faces must have the same length")
+    if index.size and int(index.max()) >= nx * ny * nz:
+        raise ValueError("surface_quads: an index lies outside dims")
+    bits = (faces[:, None] >> np.arange(6, dtype=np.uint8)[None, :]) & 1          # [n, 6]: list order, then ascending d
+    entry, direction = np.nonzero(bits)
+    voxel = index[entry]
+    v = np.stack([voxel // (ny * nz), voxel // nz % ny, voxel % nz], 1).astype(np.int32)
+    axis, positive = direction >> 1, (direction & 1).astype(np.int32)
+    corners = np.repeat(v[:, None, :], 4, 1)                                      # [F, 4, 3]
+    rows = np.arange(entry.size)
+    ring = np.array(((0, 0), (1, 0), (1, 1), (0, 1)), np.int32)
+    for t in range(4):
+        off = np.where(positive[:, None] == 1, ring[t][None, :], ring[3 - t][None, :])
+        corners[rows, t, axis] += positive
+        corners[rows, t, (axis + 1) % 3] += off[:, 0]
+        corners[rows, t, (axis + 2) % 3] += off[:, 1]
+    return corners, direction.astype(np.uint8), voxel.astype(np.uint32)
 
 
 def follow_parents(parent, dims, index):

@@ -31,6 +31,7 @@
 #include "devmap_distance.h"
 #include "devmap_frontier.h"
 #include "devmap_footing.h"
+#include "devmap_surface.h"
 #include "devmap_gain.h"
 #include "devmap_score.h"
 #include "devmap_nearest.h"
@@ -95,6 +96,7 @@ struct la3dm_devmap {
     Arena df_work;                // distance field: 4 bytes per voxel (obstacle bits / z distances, then the partial sums)
     Arena fr_work;                // frontier: 1/2 byte per padded voxel (two bit streams, popcounts, prefixes: devmap_frontier.h)
     Arena ft_work;                // footing: 7/8 byte per padded voxel (five bit streams, popcounts, prefixes: devmap_footing.h)
+    Arena sf_work;                // surface: 11/8 byte per padded voxel (eight bit streams, candidates, popcounts, prefixes: devmap_surface.h)
     Arena gain_work;              // gain: one bit per voxel and viewpoint (the sets: devmap_gain.h)
     Arena score_work;             // score_poses: d2 (4 bytes per voxel), then the chunks' partial records (devmap_score.h); score_paths: d2 (devmap_paths.h)
     Arena nt_work;                // nearest: the y keys (4 bytes per voxel), the z offsets (2), the obstacle bits; nearest_points: index and d2 as well (devmap_nearest.h)
@@ -737,7 +739,7 @@ void la3dm_devmap_destroy(la3dm_devmap *dm) {
     (void)hipSetDevice(dm->ctx->device);
     Arena *all[] = {&dm->cloud, &dm->hits, &dm->keep, &dm->nfree, &dm->keep_off, &dm->free_off, &dm->frees_raw, &dm->frees_ds,
                     &dm->xy, &dm->k0, &dm->k1, &dm->v0, &dm->v1, &dm->flag, &dm->scan, &dm->seg_start, &dm->seg_key,
-                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->ft_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->drive_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
+                    &dm->cub_tmp, &dm->scan_status, &dm->radix_state, &dm->radix_tmp, &dm->big, &dm->chunk_desc, &dm->train, &dm->grid, &dm->axis_tab, &dm->m_code, &dm->q_out, &dm->df_work, &dm->fr_work, &dm->ft_work, &dm->sf_work, &dm->gain_work, &dm->score_work, &dm->nt_work, &dm->reach_work, &dm->travel_work, &dm->drive_work, &dm->clusters_work, &dm->clusters_rec, &dm->pack_stream, &dm->pack_counts, &dm->c_flag, &dm->c_weight, &dm->c_scan, &dm->t_key0,
                     &dm->t_key1, &dm->t_ent0, &dm->t_ent1, &dm->t_blockkey, &dm->t_center, &dm->t_nbr, &dm->t_slot, &dm->t_slot0, &dm->nleaf,
                     &dm->leaf_off, &dm->leaf_key, &dm->leaf_alpha, &dm->leaf_beta, &dm->leaf_state, &dm->leaf_node,
                     &dm->l_ray_idx, &dm->l_rays, &dm->l_rows, &dm->l_rows_off, &dm->l_rflag, &dm->l_rscan,
@@ -3658,6 +3660,127 @@ int la3dm_devmap_footing_host(la3dm_devmap *dm, const float *lo3, const uint32_t
                               uint64_t cap, const la3dm_footing_out *out, uint64_t *n_found, la3dm_footing_stats *stats,
                               la3dm_region_info *info) {
     return footing_query(dm, true, "la3dm_devmap_footing_host", lo3, dims3, params, cap, out, n_found, stats, info);
+}
+
+// ---- surface of a region (devmap_surface.h) --------------------------------------------------------------------
+
+// Bits, faces, scan, (cap > 0) emit, (smooth > 0 and a normal array) normals and (the dense array) dense on the map's stream;
+// o's arrays are device memory.  d_stats: where the launches leave the kSfWaves partial counts (working storage).
+static int surface_launch(la3dm_devmap *dm, const RegionGeom &g, const la3dm_surface_params &p, uint64_t cap, const la3dm_surface_out &o,
+                          const uint32_t *&d_stats) {
+    hipStream_t st = dm->ctx->stream;
+    const uint32_t pad = p.smooth + 1u;
+    RegionArgs a = region_args(dm, g);
+    for (int k = 0; k < 3; ++k) a.g0[k] = g.g0[k] - pad;   // (surface_query's region check: g0 >= the pad below)
+    a.nx = g.dims[0] + 2u * pad;
+    a.ny = g.dims[1] + 2u * pad;
+    a.nz = g.dims[2] + 2u * pad;
+    a.total = a.nx * a.ny * a.nz;   // <= LA3DM_SURFACE_MAX_CELLS
+    const uint32_t n_words = cdiv(a.total, 32);
+    const size_t stride = ((size_t)n_words + 1 + 3) & ~(size_t)3;   // every array 16-byte aligned (the scan's vector path)
+    DM_RESERVE(dm->sf_work, 4ull * (11 * stride + 8 * kSfWaves));
+    uint32_t *base = (uint32_t *)dm->sf_work.ptr;
+    SurfaceArgs f;
+    memset(&f, 0, sizeof(f));
+    f.nx = g.dims[0];
+    f.ny = g.dims[1];
+    f.nz = g.dims[2];
+    f.PY = a.ny;
+    f.PZ = a.nz;
+    f.s = p.smooth;
+    f.pad = pad;
+    f.total = a.total;
+    f.n_words = n_words;
+    const bool normals = p.smooth > 0 && cap > 0 && o.normal != nullptr;
+    f.store_faces = normals || o.dense_faces != nullptr;
+    f.solid = base;
+    f.open = base + stride;
+    f.face = base + 2 * stride;
+    f.stride = (uint32_t)stride;
+    f.cand = base + 8 * stride;
+    f.count = base + 9 * stride;
+    f.offset = base + 10 * stride;
+    f.stats = base + 11 * stride;
+    f.cap = cap;
+    f.index = cap ? o.index : nullptr;
+    f.faces = cap ? o.faces : nullptr;
+    f.normal = cap ? o.normal : nullptr;
+    f.dense = o.dense_faces;
+    hipLaunchKernelGGL(dm_ft_bits, dim3(cdiv(a.total, 256)), dim3(256), 0, st, a, p.solid_mask, p.open_mask, base, base + stride);
+    hipLaunchKernelGGL(dm_sf_faces, dim3(kSfWaves / 4), dim3(256), 0, st, f);   // four waves per workgroup
+    DM_TRY(hipGetLastError());
+    dm->counters_clean = false;   // (the scan may flag a dirty state in the counter block)
+    int rc = exclusive_scan(dm, f.count, base + 10 * stride, n_words + 1);
+    if (rc != LA3DM_OK) return rc;
+    if (cap) hipLaunchKernelGGL(dm_sf_emit, dim3(cdiv(n_words, 256)), dim3(256), 0, st, f);
+    if (normals) hipLaunchKernelGGL(dm_sf_normals, dim3(kSfWaves / 4), dim3(256), 0, st, f);
+    if (f.dense) hipLaunchKernelGGL(dm_sf_dense, dim3(cdiv(g.total, 256)), dim3(256), 0, st, f);
+    DM_TRY(hipGetLastError());
+    d_stats = f.stats;
+    return LA3DM_OK;
+}
+
+static int surface_query(la3dm_devmap *dm, bool host, const char *who, const float *lo3, const uint32_t *dims3,
+                         const la3dm_surface_params *params, uint64_t cap, const la3dm_surface_out *out, uint64_t *n_found,
+                         la3dm_surface_stats *stats, la3dm_region_info *info) {
+    RegionGeom g;
+    DM_OK(refuse(dm, who, la3dm_region::surface_check(params, cap, out, "->")));
+    DM_OK(region_resolve(dm, lo3, dims3, la3dm_region::surface_query(*params), true, true, who, g));   // lo, dims, the limit and the range
+    if (!n_found) return refuse(dm, who, "n_found is NULL");
+    hipStream_t st = dm->ctx->stream;
+    la3dm_surface_out o;
+    memset(&o, 0, sizeof(o));
+    if (out) o = *out;
+    const size_t n = (size_t)g.total;
+    uint64_t counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // solid, the six directions, surface voxels
+    if (dm->n_blocks == 0) {   // every voxel MISSING, and the masks do not overlap: no face, and all or no voxel solid
+        if ((params->solid_mask >> LA3DM_RAY_MISSING) & 1u) counts[0] = n;
+        const Fill f{dm, host};
+        DM_OK(f.bytes(o.dense_faces, 0, n));
+        DM_TRY(hipStreamSynchronize(st));
+    } else {
+        // the list has at most one entry per voxel and no more than cap; only what was found is copied back
+        const size_t room = (size_t)std::min<uint64_t>(cap, n);
+        Stage s(dm, host);
+        const int i_index = s.out(o.index, room);
+        const int i_faces = s.out(o.faces, room);
+        const int i_normal = s.out(o.normal, 3 * room);
+        s.out(o.dense_faces, n);
+        DM_OK(s.reserve());
+        const uint32_t *d_stats = nullptr;
+        DM_OK(surface_launch(dm, g, *params, room, o, d_stats));
+        // (a one-workgroup launch that adds the partial counts on the device, so that 32 bytes come back, was measured: it
+        // takes 8 us and the call gets no faster — DESIGN.md 3.24)
+        std::vector<uint32_t> partial(8 * kSfWaves);
+        DM_TRY(hipMemcpyAsync(partial.data(), d_stats, 4 * partial.size(), hipMemcpyDeviceToHost, st));
+        DM_TRY(hipStreamSynchronize(st));
+        for (size_t t = 0; t < partial.size(); ++t) counts[t % 8] += partial[t];   // (each sum is at most the voxels of the region)
+        s.count(i_index, counts[7]);
+        s.count(i_faces, counts[7]);
+        s.count(i_normal, 3 * counts[7]);
+        DM_OK(s.download());
+        if (host) DM_TRY(hipStreamSynchronize(st));
+    }
+    *n_found = counts[7];
+    if (stats) {
+        stats->n_solid = counts[0];
+        stats->n_surface = counts[7];
+        for (int d = 0; d < 6; ++d) stats->faces[d] = counts[1 + d];
+    }
+    if (info) *info = g.info;
+    return LA3DM_OK;
+}
+
+int la3dm_devmap_surface_device(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_surface_params *params,
+                                uint64_t cap, const la3dm_surface_out *d_out, uint64_t *n_found, la3dm_surface_stats *stats,
+                                la3dm_region_info *info) {
+    return surface_query(dm, false, "la3dm_devmap_surface_device", lo3, dims3, params, cap, d_out, n_found, stats, info);
+}
+
+int la3dm_devmap_surface_host(la3dm_devmap *dm, const float *lo3, const uint32_t *dims3, const la3dm_surface_params *params,
+                              uint64_t cap, const la3dm_surface_out *out, uint64_t *n_found, la3dm_surface_stats *stats,
+                              la3dm_region_info *info) {
+    return surface_query(dm, true, "la3dm_devmap_surface_host", lo3, dims3, params, cap, out, n_found, stats, info);
 }
 
 // ---- gain of candidate viewpoints (devmap_gain.h) ---------------------------------------------------------------

@@ -114,26 +114,33 @@ __device__ __forceinline__ uint32_t ft_stand(const FootingArgs &a, int w) {
     return below & ft_run(c, a.h);
 }
 
-// the bits of word w that belong to the region's interior: pz in [1 + s, nz + s], pj in [r, ny + r), pi in [r, nx + r).
-// A word overlaps at most 32 / PZ + 2 <= 17 padded columns (PZ >= 2).
-__device__ __forceinline__ uint32_t ft_interior(const FootingArgs &a, uint32_t w) {
+// the bits of word w of a stream over a padded box (., PY, PZ) that belong to the region (nx, ny, nz) which starts pad_xy
+// voxels inside the box in x and y and pad_z in z: pz in [pad_z, nz + pad_z), pj in [pad_xy, ny + pad_xy), pi in [pad_xy,
+// nx + pad_xy).  A word overlaps at most 32 / PZ + 2 <= 17 padded columns (PZ >= 2).  (devmap_surface.h uses it as well.)
+__device__ __forceinline__ uint32_t ft_interior_bits(uint32_t nx, uint32_t ny, uint32_t nz, uint32_t PY, uint32_t PZ, uint32_t pad_xy,
+                                                     uint32_t pad_z, uint32_t w) {
     uint32_t mask = 0u;
     const uint32_t first = w << 5;
-    uint32_t col = first / a.PZ, z0 = first % a.PZ;   // the column of bit 0 and where in it the bit lies
-    int at = -(int)z0;                                // the bit of the word at which column `col` starts
+    uint32_t col = first / PZ, z0 = first % PZ;   // the column of bit 0 and where in it the bit lies
+    int at = -(int)z0;                            // the bit of the word at which column `col` starts
 #pragma unroll 1
     for (int piece = 0; piece < 17; ++piece) {
         if (at >= 32) break;
-        const uint32_t pi = col / a.PY, pj = col % a.PY;
-        if (pi >= a.r && pi < a.nx + a.r && pj >= a.r && pj < a.ny + a.r) {
-            const int lo = at + (int)(1u + a.s), hi = lo + (int)a.nz;   // bits [lo, hi) of the word
+        const uint32_t pi = col / PY, pj = col % PY;
+        if (pi >= pad_xy && pi < nx + pad_xy && pj >= pad_xy && pj < ny + pad_xy) {
+            const int lo = at + (int)pad_z, hi = lo + (int)nz;   // bits [lo, hi) of the word
             const int from = lo < 0 ? 0 : lo, to = hi > 32 ? 32 : hi;
             if (from < to) mask |= (to - from == 32 ? 0xFFFFFFFFu : ((1u << (to - from)) - 1u) << from);
         }
         ++col;
-        at += (int)a.PZ;
+        at += (int)PZ;
     }
     return mask;
+}
+
+// footing's own interior: pz in [1 + s, nz + s], pj in [r, ny + r), pi in [r, nx + r)
+__device__ __forceinline__ uint32_t ft_interior(const FootingArgs &a, uint32_t w) {
+    return ft_interior_bits(a.nx, a.ny, a.nz, a.PY, a.PZ, a.r, 1u + a.s, w);
 }
 
 // the sum of v over the wave, in lane 0
@@ -180,12 +187,13 @@ __device__ __forceinline__ uint32_t ft_at_least(const uint32_t planes[kFtPlanes]
     return ge | eq;
 }
 
-// planes += the planes of lane ^ d, bit-sliced: both terms fit kP planes, the sum kP + 1 (at most kFtPlanes: N < 256)
-template <int kP>
-__device__ __forceinline__ void ft_fold(uint32_t planes[kFtPlanes], int d) {
+// planes += the planes of lane ^ d, bit-sliced: both terms fit kP planes, the sum kP + 1 (at most kN, the planes there
+// are: N < 256 here; devmap_surface.h sums up to 729 in 10)
+template <int kP, int kN = (int)kFtPlanes>
+__device__ __forceinline__ void ft_fold(uint32_t *planes, int d) {
     uint32_t carry = 0u;
 #pragma unroll
-    for (int q = 0; q < (int)kFtPlanes; ++q) {
+    for (int q = 0; q < kN; ++q) {
         if (q < kP) {   // a full adder per plane
             const uint32_t other = __shfl_xor(planes[q], d, 64);
             const uint32_t x = planes[q] ^ other;

@@ -1557,6 +1557,51 @@ void BGKOctoMap::footing(const float *lo3, const uint32_t *dims3, const la3dm_fo
     if (stats) *stats = la3dm_footing_stats{(uint32_t)n.n_stand, (uint32_t)n.n_body, (uint32_t)n.n_foot, la3dm_footing::disc_cells(p->radius)};
 }
 
+// ---- surface of a region.  The host form is the definition; the device kernels (csrc/devmap_surface.h) reproduce it
+// exactly.  The classes of the padded box — smooth + 1 voxels round the region on every side — are read as box reads them
+// (the lattice does not stop at the region's faces); host/surface_cells.h does the rest.
+void BGKOctoMap::surface(const float *lo3, const uint32_t *dims3, const la3dm_surface_params *p, uint64_t cap, const la3dm_surface_out &out,
+                         uint64_t *n_found, la3dm_surface_stats *stats, la3dm_region_info *info) const {
+    bind();
+    if (dmap != nullptr) {
+        if (la3dm_devmap_surface_host(dmap, lo3, dims3, p, cap, &out, n_found, stats, info) != LA3DM_OK)
+            throw std::runtime_error(std::string("BGKOctoMap::surface: ") + la3dm_last_error(ctx));
+        return;
+    }
+    const std::string w = "BGKOctoMap::surface";
+    const std::string refusal = la3dm_region::surface_check(p, cap, &out, ".");
+    if (!refusal.empty()) throw std::invalid_argument(w + ": " + refusal);
+    uint32_t g0[3];
+    la3dm_region_info inf;
+    region_anchor(lo3, dims3, la3dm_region::surface_query(*p), true, "surface", g0, inf);
+    if (n_found == nullptr) throw std::invalid_argument(w + ": n_found is NULL");
+    if (info) *info = inf;
+    const la3dm_surface::Params sp = la3dm_region::surface_params(*p);
+    size_t P[3];
+    la3dm_surface::padded_dims(dims3, sp, P);
+    const uint32_t below = p->smooth + 1u;
+    // classes of the padded box: box's loop at the lattice positions g0 - below + (i, j, k)
+    std::vector<uint8_t> cls(P[0] * P[1] * P[2]);
+#pragma omp parallel for schedule(static)
+    for (size_t row = 0; row < P[0] * P[1]; ++row) {
+        const uint32_t gx = g0[0] - below + (uint32_t)(row / P[1]), gy = g0[1] - below + (uint32_t)(row % P[1]);
+        const Block *b = nullptr;
+        BlockHashKey have = -1;
+        for (size_t k = 0; k < P[2]; ++k) {
+            unsigned d;
+            const OcTreeNode *leaf = covering_leaf_at(gx, gy, g0[2] - below + (uint32_t)k, have, b, d);
+            cls[row * P[2] + k] = leaf ? (uint8_t)leaf->state : (uint8_t)LA3DM_RAY_MISSING;
+        }
+    }
+    const la3dm_surface::Counts n = la3dm_surface::cells(cls.data(), dims3, sp, cap, out.index, out.faces, out.normal, out.dense_faces);
+    *n_found = n.n_surface;
+    if (stats) {
+        stats->n_solid = n.n_solid;
+        stats->n_surface = n.n_surface;
+        for (int d = 0; d < 6; ++d) stats->faces[d] = n.faces[d];
+    }
+}
+
 // ---- reach over a region.  The host form below is the definition; the device kernels (csrc/devmap_reach.h) reproduce
 // it bit for bit.  A queue BFS over the passable voxels of the box padded by one voxel that is never passable, so a
 // neighbour is an index offset with no test at the faces.

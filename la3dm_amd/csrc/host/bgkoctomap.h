@@ -472,6 +472,18 @@ public:
     /// definition, and both give the same integers.
     void footing(const float *lo3, const uint32_t *dims3, const la3dm_footing_params *p, uint64_t cap, const la3dm_footing_out &out,
                  uint64_t *n_found, la3dm_footing_stats *stats = nullptr, la3dm_region_info *info = nullptr) const;
+    /// Surface over box's region (contract: include/la3dm_hip.h, la3dm_devmap_surface_host): the exposed faces and integer
+    /// normals of its solid voxels.  A voxel with a class in p->solid_mask has face d (0: -x, 1: +x, 2: -y, 3: +y, 4: -z,
+    /// 5: +z) when its neighbour in that direction has a class in p->open_mask; classes past the region's faces are read
+    /// from the map.  *n_found = the voxels with a face; out.index / faces / normal = the flat indices of the first
+    /// min(*n_found, cap) in ascending order, their face masks and their normals (the sum of the face vectors of every voxel
+    /// within p->smooth voxels, three int16, possibly zero); out.dense_faces (optional) = the face mask of every voxel;
+    /// stats (may be null) = the solid voxels, the surface voxels and the faces per direction.  Bad arguments throw
+    /// std::invalid_argument.  A device-resident map runs the query on the device pool (no mirror refresh); a host-mode map
+    /// reads the classes of the padded box and calls host/surface_cells.h: that form is the definition, and both give the
+    /// same integers.
+    void surface(const float *lo3, const uint32_t *dims3, const la3dm_surface_params *p, uint64_t cap, const la3dm_surface_out &out,
+                 uint64_t *n_found, la3dm_surface_stats *stats = nullptr, la3dm_region_info *info = nullptr) const;
     /// Gain of candidate viewpoints over box's region (contract: include/la3dm_hip.h, la3dm_devmap_gain_host): the n * m
     /// segments origins[v] -> origins[v] + offsets[d] are walked exactly as raycast_many(stop_mask, max_steps) walks them;
     /// every row whose class is in `count_mask` and whose voxel lies in the region sets that voxel's bit in viewpoint v's

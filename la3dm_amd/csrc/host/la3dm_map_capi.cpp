@@ -407,6 +407,14 @@ int la3dm_map_footing(const la3dm_map *m, const float *lo3, const uint32_t *dims
         return 0;)
 }
 
+int la3dm_map_surface(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const la3dm_surface_params *params, uint64_t cap,
+                      const la3dm_surface_out *out, uint64_t *n_found, la3dm_surface_stats *stats, la3dm_region_info *info) {
+    GUARD(
+        const la3dm_surface_out none = la3dm_surface_out();   // (all null)
+        m->map->surface(lo3, dims3, params, cap, out ? *out : none, n_found, stats, info);
+        return 0;)
+}
+
 int la3dm_map_gain(const la3dm_map *m, const float *lo3, const uint32_t *dims3, const float *origins3, uint32_t n,
                    const float *offsets3, uint32_t mdirs, uint32_t count_mask, uint32_t stop_mask, uint32_t max_steps,
                    const la3dm_gain_out *out, la3dm_region_info *info) {

@@ -14,6 +14,7 @@
 #include "../../../include/la3dm_hip.h"
 #include "drive_cells.h"
 #include "footing_cells.h"
+#include "surface_cells.h"
 
 #if defined(__HIPCC__)
 #define LA3DM_HD __host__ __device__
@@ -420,6 +421,31 @@ inline Query footing_query(const la3dm_footing_params &p) {
 inline la3dm_footing::Params footing_params(const la3dm_footing_params &p) {
     return la3dm_footing::Params{p.support_mask, p.clear_mask, p.headroom, p.radius, p.step, p.min_support};
 }
+
+// ---- surface (contract: include/la3dm_hip.h, la3dm_devmap_surface_host) ----
+// the checks of surface's own arguments and of its list, all before the region's (`out` may be null)
+inline std::string surface_check(const la3dm_surface_params *p, uint64_t cap, const la3dm_surface_out *out, const char *member) {
+    if (!p) return "params is NULL";
+    if (p->solid_mask == 0 || (p->solid_mask & ~0x1Fu)) return "solid_mask must hold at least one of the bits 0x1F and no other";
+    if (p->open_mask == 0 || (p->open_mask & ~0x1Fu)) return "open_mask must hold at least one of the bits 0x1F and no other";
+    if (p->solid_mask & p->open_mask) return "solid_mask and open_mask must not overlap";
+    if (p->smooth > LA3DM_SURFACE_MAX_SMOOTH) return "smooth must not exceed LA3DM_SURFACE_MAX_SMOOTH (4)";
+    if (out && out->normal && !out->index) return std::string("out") + member + "normal is set without out" + member + "index";
+    if (cap > 0 && !(out && (out->index || out->faces))) return std::string("out") + member + "index or out" + member + "faces must not be NULL with cap > 0";
+    return "";
+}
+
+// the region's checks of surface: limit and range on the box padded by smooth + 1 voxels on all six sides
+inline Query surface_query(const la3dm_surface_params &p) {
+    const uint32_t pad = p.smooth + 1u;
+    return Query{LA3DM_SURFACE_MAX_CELLS,
+                 "dims: more than LA3DM_SURFACE_MAX_CELLS (2^28) voxels in the padded box",
+                 false,
+                 Pad{{pad, pad, pad}, {pad, pad, pad}, "dims: the block fields of the padded box leave [0, 2^20)"},
+                 ""};
+}
+
+inline la3dm_surface::Params surface_params(const la3dm_surface_params &p) { return la3dm_surface::Params{p.solid_mask, p.open_mask, p.smooth}; }
 
 // ---- drive (contract: include/la3dm_hip.h, la3dm_devmap_drive_host) ----
 static_assert(LA3DM_DRIVE_MAX_STEP == LA3DM_FOOTING_MAX_STEP && LA3DM_DRIVE_MAX_STEP == la3dm_drive::kMaxStep && LA3DM_DRIVE_NONE == la3dm_drive::kNone,
