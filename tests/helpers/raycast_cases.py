@@ -92,7 +92,7 @@ def reduce_rays(m, lv, starts, ends, mask, max_steps, cap=8192):
                 assert (d == nk >> 16) == (rows["state"][j] != 3)      # the raw node reads PRUNED exactly when a coarser leaf covers it
             else:
                 cls, depth, A, B = MISSING, 255, np.float32(a0), np.float32(b0)
-            out["counts"][r, cls] += 1
+            out["counts"][r, UNKNOWN if cls == 4 else cls] += 1          # (a BGK-LV map's UNCERTAIN is counted with UNKNOWN)
             out["p"][r], out["block_key"][r], out["node_key"][r] = rows["p"][j], bk, nk
             out["cls"][r], out["leaf_depth"][r], out["A"][r], out["B"][r] = cls, depth, A, B
             if mask & (1 << cls):
