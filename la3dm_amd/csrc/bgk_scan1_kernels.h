@@ -8,6 +8,12 @@
 // recording all three counter files again.  The pull request that records them again ("BGK scan: merge
 // bgk_predict_fuse_t1 into bgk_kernels.h and re-stamp the counter files") folds this kernel back into
 // bgk_predict_fuse_t and deletes this header.  Until then: a change to the table path of one kernel belongs in the other too.
+// The exceptions, all of them bookkeeping round the same arithmetic (profiles/one_launch_trim/README.md), which the merge
+// carries over: (1) the correctly rounded evaluation (kTrig 0) is a copy here, scan1_sincos_cr_eval / scan1_cov, that takes
+// the four constant addends of its polynomials from vcc instead of four SGPR pairs; (2) alpha, beta, state and the stamp
+// record are read again from the kernarg segment on the way out (scan1_arg_again) instead of being carried through the
+// body; (3) the column groups of a table sub-round are eight trips with immediate offsets, not a loop that moves the
+// three row addresses; (4) the cull's masks are the ballots of its three compares, joined on the scalar side.
 //
 // Everything else — device functions, the LA3DM_TP_* macros, WaveLdsT, the ablation flags — is bgk_kernels.h's, used
 // from here (include this header after it).  One difference in the table path: this kernel notes a training point at no
@@ -18,6 +24,61 @@
 #include "bgk_kernels.h"
 
 namespace la3dm_dev {
+
+// v_fma_f64 d = a * b + CONSTANT with the constant in no register of the kernel's: its two words are moved into vcc right
+// ahead of the instruction (LO, HI: string literals).  fma64_sc (bgk_kernels.h) keeps each addend in an SGPR pair for the whole
+// tile — eight scalar registers that this kernel, at 78 SGPRs, pays for with scalars parked in lanes of a VGPR (a
+// v_writelane / v_readlane each, on the unit that bounds the kernel); two s_mov_b32 per use go to the scalar unit, which has
+// room.  A scalar write of vcc followed by a vector read of it as a constant needs no wait state on gfx9 (the table of the
+// ISA manual lists only VALU writers of an SGPR); the s_nop is there because the compiler pads nothing inside a statement.
+#define LA3DM_FMA64_VCC(D, A, B, LO, HI)                                                             \
+    asm("s_mov_b32 vcc_lo, " LO "\n"                                                                 \
+        "s_mov_b32 vcc_hi, " HI "\n"                                                                 \
+        "s_nop 0\n"                                                                                  \
+        "v_fma_f64 %0, %1, %2, vcc\n" : "=v"(D) : "v"(A), "v"(B) : "vcc")
+
+// sincos_cr_eval of bgk_kernels.h — the same operations on the same constants in the same order — with the four constant
+// addends taken from vcc (tests/test_bgk_one_launch_trim_gpu.py compares the words with the original's)
+__device__ __forceinline__ void scan1_sincos_cr_eval(float y32, double sa, double ca, float &s, float &c) {
+    const double y = (double)y32;
+    const double z = y * y;
+    const double s3 = __builtin_bit_cast(double, 0xbf2a014a5f1de813ull), c3 = __builtin_bit_cast(double, 0x3efa015b846c26deull);
+    double ps, pc;
+    LA3DM_FMA64_VCC(ps, z, s3, "0x10c194d4", "0x3f811111");   // 0x3f81111110c194d4
+    LA3DM_FMA64_VCC(pc, z, c3, "0x1681d56a", "0xbf56c16c");   // 0xbf56c16c1681d56a
+    const double zy = z * y;
+    LA3DM_FMA64_VCC(ps, z, ps, "0x5555552a", "0xbfc55555");   // 0xbfc555555555552a
+    LA3DM_FMA64_VCC(pc, z, pc, "0x55555544", "0x3fa55555");   // 0x3fa5555555555544
+    const double sy = __builtin_fma(zy, ps, y);      // sin y
+    pc = __builtin_fma(z, pc, -0.5);
+    const double cm1 = z * pc;                       // cos y - 1
+    const double sd = __builtin_fma(ca, sy, __builtin_fma(sa, cm1, sa));
+    const double cd = __builtin_fma(-sa, sy, __builtin_fma(ca, cm1, ca));
+    s = (float)sd;
+    c = (float)cd;
+}
+// cov_sparse_fast<kTrig, true, true> (bgk_kernels.h); the correctly rounded instance (kTrig 0) through the evaluation above
+template <int kTrig>
+__device__ __forceinline__ float scan1_cov(float r, float sf2) {
+    if (kTrig != 0) return cov_sparse_fast<kTrig, true, true>(r, sf2);
+    const float t = (r * 2.0f) * 3.1415926f;
+    float y32, s, c;
+    const la3dm_v2d e = sincos_cr_entry(sincos_cr_reduce(t, y32));
+    scan1_sincos_cr_eval(y32, e.x, e.y, s, c);
+    return cov_sparse_formula<true>(r, s, c, sf2);
+}
+
+// A pointer argument read AGAIN from the kernarg segment, at the place that needs it (the statement is volatile: it stays
+// there).  alpha, beta, state and the stamp record are needed on the way out of a tile only; carried through the body they
+// were eight and more scalars parked in lanes of a VGPR, a v_writelane going in and a v_readlane coming out each.  BgkArgs is
+// the kernel's first argument: its members sit at their offsets in the segment.
+template <class T, int kOff>
+__device__ __forceinline__ T *scan1_arg_again() {
+    T *p;
+    asm volatile("s_load_dwordx2 %0, %1, %2\n"
+                 "s_waitcnt lgkmcnt(0)\n" : "=&s"(p) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "i"(kOff));
+    return p;
+}
 
 // BgkArgs as bgk_predict_fuse_t takes them, except: pts = the caller's UNSCALED points (x, y, z, label); blk_desc,
 // nbr_range and label_seq are not read.  Full blocks only (the host verifies it from the leaf count), tpb_shift 0 or more,
@@ -120,10 +181,15 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     const float A0 = a.alpha[li], B0 = a.beta[li];  // needed by the epilogue only: loaded here, a round trip off the tile's tail
 #endif
     if (M == 0u) {  // no training point in the 7 blocks: nothing reaches the tile
-        if (!(a.flags & 1u)) a.state[li] = 0;
+        uint8_t *const state = scan1_arg_again<uint8_t, offsetof(BgkArgs, state)>();
+        if (!(a.flags & 1u)) state[li] = 0;
         else {  // insert_training_data: update() runs with (0, 0)
+#if LA3DM_T_EARLY_AB
+            const float A = A0, B = B0;
+#else
             const float A = a.alpha[li], B = a.beta[li];
-            a.state[li] = (uint8_t)(classify(A, B, a) | 0x80u);
+#endif
+            state[li] = (uint8_t)(classify(A, B, a) | 0x80u);
         }
         return;
     }
@@ -160,7 +226,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     // C: lane evaluates ring entry i and adds k to the leaf's accumulator 0 or 1 (the sign of d2 is the label)
     auto c_eval = [&](uint32_t i) {
         const uint2 e = L.ring[i];
-        const float kv = cov_sparse_fast<kTrig, true, true>(sqrt_cr(__builtin_fabsf(__uint_as_float(e.x))), a.sf2);
+        const float kv = scan1_cov<kTrig>(sqrt_cr(__builtin_fabsf(__uint_as_float(e.x))), a.sf2);
         const double kd = (double)kv;
         const uint32_t ad = e.y | ((e.x >> 22) & 0x200u);  // label 1 (negative d2): acc1[leaf], 512 bytes up
         asm volatile("ds_add_f64 %0, %1\n" : : "v"(ad), "v"(kd) : "memory");
@@ -196,8 +262,11 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
         const bool keep = md < hit_t && cb + lane < M;
         // a point at no finite distance (a NaN coordinate, an overflowing square): the reference's kernel matrix holds NaN in
         // its column, the sums of every leaf are NaN and `kbar > 0` rejects the update (see bgk_poison_nbr in la3dm_hip.hip)
-        nonfinite |= __ballot(!(md < __builtin_inff()) && cb + lane < M);
-        const unsigned long long m = __ballot(keep);
+        // (the masks from the three compares' own ballots, joined on the scalar side: the ballot of a conjunction is rebuilt
+        // from a 0 / 1 value per lane, a v_cndmask and a v_cmp each)
+        const unsigned long long live = __ballot(cb + lane < M);
+        nonfinite |= __ballot(!(md < __builtin_inff())) & live;
+        const unsigned long long m = __ballot(md < hit_t) & live;
         if (m == 0ull) return;
         const float sg = 1.0f - (pu.w + pu.w);  // label 0 -> +1, label 1 -> -1 (exact)
         const la3dm_v2f s2 = {sg, sg};
@@ -224,20 +293,32 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             if (a.flags & 0x200u) continue;  // 0x200: profiling ablation
-            uint32_t aX = ax0, aY = ay0, aZ = az0;
-            for (uint32_t g = 0; g < ngroup; g += 2u) {  // two column groups per trip: the three row addresses move once
-                uint32_t st;
-                float tr;
-                unsigned long long hm0, hm1, hm2, hm3;
-                LA3DM_TP_TRIP("0");
-                if (tailb > tail_cap) c_flush();
-                if (g + 1u < ngroup) {
-                    LA3DM_TP_TRIP("16");
-                    if (tailb > tail_cap) c_flush();
-                }
-                const uint32_t step = g == 2u ? kHalfB - 32u : 32u;   // column groups 0-3 sit in the first half, 4-7 in the second
-                aX += step, aY += step, aZ += step;
-            }
+            // one trip per column group, the group's place in the table as the immediate offset of its three reads (groups
+            // 0-3 sit in the first half, 4-7 kHalfB = 768 bytes up in the second): the lane's three row addresses never move.
+            // The ring is tested after every trip, as before: a trip pushes up to 4 x 64 entries, which is the head room
+            // tail_cap leaves.  Eight trips are eight copies of the C round in the code (a loop over g with the trips behind
+            // a switch or an if-chain, which would share one, does not compile: "illegal VGPR to SGPR copy" where the
+            // trips' scalar outputs meet); a copy that is not entered costs the branch round it, as the loop's two did.
+            const uint32_t aX = ax0, aY = ay0, aZ = az0;
+            static_assert(kHalfB == 768u, "the immediates below");
+#define LA3DM_SCAN1_GROUP(G, OFF)                   \
+    if (G < ngroup) {                               \
+        uint32_t st;                                \
+        float tr;                                   \
+        unsigned long long hm0, hm1, hm2, hm3;      \
+        LA3DM_TP_TRIP(OFF);                         \
+        if (tailb > tail_cap) c_flush();
+            // (nested, so that the last group of a sub-round leaves through one branch)
+            LA3DM_SCAN1_GROUP(0u, "0")
+            LA3DM_SCAN1_GROUP(1u, "16")
+            LA3DM_SCAN1_GROUP(2u, "32")
+            LA3DM_SCAN1_GROUP(3u, "48")
+            LA3DM_SCAN1_GROUP(4u, "768")
+            LA3DM_SCAN1_GROUP(5u, "784")
+            LA3DM_SCAN1_GROUP(6u, "800")
+            LA3DM_SCAN1_GROUP(7u, "816")
+            }}}}}}}}
+#undef LA3DM_SCAN1_GROUP
             // (the next sub-round overwrites the table: LDS operations of a wave complete in order)
         }
     };
@@ -268,19 +349,21 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
         if (nonfinite != 0ull) K = Y = __builtin_nan("");  // (gated: K > 0 is false, the leaf is left alone; ungated: alpha = beta = NaN)
         uint32_t lw = li;
         asm volatile("" : "+v"(lw));
+        float *const alpha = scan1_arg_again<float, offsetof(BgkArgs, alpha)>(), *const beta = scan1_arg_again<float, offsetof(BgkArgs, beta)>();
+        uint8_t *const state = scan1_arg_again<uint8_t, offsetof(BgkArgs, state)>();
         if (K > 0.0 || (a.flags & 1u) != 0u) {  // flag 1: insert_training_data, update() runs unconditionally
 #if LA3DM_T_EARLY_AB
             const float A = (float)((double)A0 + Y);
             const float B = (float)((double)B0 + (K - Y));
 #else
-            const float A = (float)((double)a.alpha[lw] + Y);
-            const float B = (float)((double)a.beta[lw] + (K - Y));
+            const float A = (float)((double)alpha[lw] + Y);
+            const float B = (float)((double)beta[lw] + (K - Y));
 #endif
-            a.alpha[lw] = A;
-            a.beta[lw] = B;
-            a.state[lw] = (uint8_t)(classify_fast(A, B, a) | 0x80u);
+            alpha[lw] = A;
+            beta[lw] = B;
+            state[lw] = (uint8_t)(classify_fast(A, B, a) | 0x80u);
         } else {
-            a.state[lw] = 0;
+            state[lw] = 0;
         }
     }
 }
@@ -313,7 +396,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     const unsigned long long t_out = wall_clock64();
     uint32_t lane = threadIdx.x;
     asm volatile("" : "+v"(lane));  // (compared again here: the entry's comparison is not kept in registers across the body)
-    if (lane == 0) atomicMax(stamps + kStampSlots + kStampExitStride * (blockIdx.x & (kStampSlots - 1u)), t_out);
+    static_assert(sizeof(BgkArgs) % 8 == 0, "the stamp pointer follows BgkArgs in the kernarg segment");
+    unsigned long long *const rec = scan1_arg_again<unsigned long long, sizeof(BgkArgs)>();   // (`stamps`, not carried through the body)
+    if (lane == 0) atomicMax(rec + kStampSlots + kStampExitStride * (blockIdx.x & (kStampSlots - 1u)), t_out);
 }
 
 }  // namespace la3dm_dev
