@@ -159,6 +159,10 @@ const char *la3dm_last_error(const la3dm_ctx *ctx); /* ctx may be NULL: last cre
  *     the leaf count) at block_depth 3 — the first scan into an empty map — runs as ONE launch: bgk_predict_fuse_t1 reads the caller's
  *     unscaled points and the nbr / train_off arrays itself, no scaled copy of the points and no scratch (scratch_bytes 0);
  *     0 = the prescale launch + bgk_predict_fuse_t, as every other scan.  Bit-identical results.
+ *     "bgk_scan1_generic" 0 (default; env LA3DM_BGK_SCAN1_GENERIC) = that one launch runs the instance of the kernel with its scan compiled in
+ *     (depth 3, sf2 == 1, x / ell by the reciprocal, default remap, gated, no profiling switch) wherever those conditions hold, the generic
+ *     instance elsewhere; 1 = the generic instance always (A/B switch).  Bit-identical results.  la3dm_get_option "bgk_scan1_instance" (read-only)
+ *     says what the last la3dm_bgk_scan_device call launched: 2 the production instance, 1 the generic one, 0 not the one launch.
  *     "bgk_tile_desc" 1 (default) = at block_depth >= 4 every 64-leaf tile of a full block gets its own neighbour descriptor
  *     without the face neighbours its voxel cube cannot reach (only while ell <= 4 * resolution; 0 = block-wide descriptors; same results).
  *   0 = the reference's fp32 summation order (bgk_predict_fuse_v5): bit-identical to the CPU restatement, the regression
@@ -183,7 +187,8 @@ const char *la3dm_last_error(const la3dm_ctx *ctx); /* ctx may be NULL: last cre
  * the split tiles' rows are expanded for all items at once (64 KB more scratch per item) and added by a copy-only replay,
  * 0 = the replay expands them itself (results do not depend on it; bgk_sum 0 only — the order-free mode has no replay). */
 int la3dm_set_option(la3dm_ctx *ctx, const char *name, int value);
-/* current value of an option that has one ("bgk_sum", "bgk_tables", "bgk_one_launch", "bgk_tile_desc", "fast_trig", "gp_mode", "grid_order", "waves_per_wg", "remap") */
+/* current value of an option that has one ("bgk_sum", "bgk_tables", "bgk_one_launch", "bgk_scan1_generic", "bgk_tile_desc", "fast_trig", "gp_mode", "grid_order", "waves_per_wg", "remap");
+ * read-only, not an option la3dm_set_option knows: "bgk_scan1_instance" = what the last la3dm_bgk_scan_device call launched (2 / 1 / 0, see "bgk_scan1_generic") */
 int la3dm_get_option(const la3dm_ctx *ctx, const char *name, int *value);
 
 /* All pointers in *scan are HOST pointers. Synchronous: H2D, kernels, D2H. */

@@ -13,7 +13,13 @@
 // the four constant addends of its polynomials from vcc instead of four SGPR pairs; (2) alpha, beta, state and the stamp
 // record are read again from the kernarg segment on the way out (scan1_arg_again) instead of being carried through the
 // body; (3) the column groups of a table sub-round are eight trips with immediate offsets, not a loop that moves the
-// three row addresses; (4) the cull's masks are the ballots of its three compares, joined on the scalar side.
+// three row addresses; (4) the cull's masks are the ballots of its three compares, joined on the scalar side; (5) the tile
+// body has a second, "production" instance (bgk_scan1_tile<0, true>, profiles/one_launch_special/README.md) with what the host
+// has verified for the launch compiled in — depth 3 and one tile per block (no leaf_off load, no full-block compare, the LUT
+// index a literal minus the lane), remap 2, inv_ell != 0 (div_const without div_by_ell's branch), sf2 == 1 (no multiply:
+// scan1_cov_unit, which also forms t = 2 pi r in one multiply), a gated scan, no ablation switch — and with the last column
+// group of a sub-round, where it is not full, through a trip that pushes its candidates only (LA3DM_SCAN1_PAD_TRIP; the table
+// is not padded).  The merge carries the instance over as a template parameter of bgk_predict_fuse_t.
 //
 // Everything else — device functions, the LA3DM_TP_* macros, WaveLdsT, the ablation flags — is bgk_kernels.h's, used
 // from here (include this header after it).  One difference in the table path: this kernel notes a training point at no
@@ -67,6 +73,50 @@ __device__ __forceinline__ float scan1_cov(float r, float sf2) {
     scan1_sincos_cr_eval(y32, e.x, e.y, s, c);
     return cov_sparse_formula<true>(r, s, c, sf2);
 }
+// scan1_cov<0> of a map whose sf2 is 1.0f (the production instance below), two instructions shorter per pair, same bits:
+//  * t = (r * 2.0f) * 3.1415926f is r * 6.2831852f.  r * 2 is exact for every r,
+//    and 2 * RN(3.1415926) = 0x40c90fda is a float, the one the literal 6.2831852f rounds to (tests/test_bgk_one_launch_special_gpu.py
+//    reads the literal here and sweeps both forms): both forms round the same real product r * 0x1.921fb4p+2 once.
+//  * (a + b) * sf2 at sf2 == 1.0f is a + b, for every value including -0 and NaN; the compiler keeps the multiply (no fast-math).
+__device__ __forceinline__ float scan1_cov_unit(float r) {
+    const float t = r * 6.2831852f;
+    float y32, s, c;
+    const la3dm_v2d e = sincos_cr_entry(sincos_cr_reduce(t, y32));
+    scan1_sincos_cr_eval(y32, e.x, e.y, s, c);
+    const float a = div_const((2.0f + c) * (1.0f - r), 3.0f, 0.333333343f);   // cov_sparse_formula<true> (bgk_kernels.h) from here on
+    const float b = div_const(s, 2.0f * 3.1415926f, 0.159154952f);
+    return fmaxf(a + b, 0.0f);
+}
+
+// The last column group of a table sub-round when it holds fewer than four candidates (production instance): LA3DM_TP_TRIP
+// with the pushes of the slots that hold no candidate left out — NP = 1, 2 or 3 pushes, a scalar — and no fourth compare.
+// The ring gets the entries LA3DM_TP_TRIP gives it from a group padded with candidates out of every leaf's reach, in the same order.
+#define LA3DM_SCAN1_PAD_TRIP(OFF)                                                                   \
+    asm volatile("ds_read_b128 v[52:55], %[ax] offset:" OFF "\n"                                    \
+                 "ds_read_b128 v[56:59], %[ay] offset:" OFF "\n"                                    \
+                 "ds_read_b128 v[60:63], %[az] offset:" OFF "\n"                                    \
+                 "s_waitcnt lgkmcnt(0)\n"                                                           \
+                 "v_pk_add_f32 v[56:57], v[56:57], v[60:61]\n"                                      \
+                 "v_pk_add_f32 v[58:59], v[58:59], v[62:63]\n"                                      \
+                 "s_nop 0\n"                                                                        \
+                 "v_pk_add_f32 v[52:53], v[52:53], v[56:57]\n"                                      \
+                 "v_pk_add_f32 v[54:55], v[54:55], v[58:59]\n"                                      \
+                 "s_nop 0\n"                                                                        \
+                 "v_cmp_gt_f32_e64 %[m0], %[T], |v52|\n"                                            \
+                 "v_cmp_gt_f32_e64 %[m1], %[T], |v53|\n"                                            \
+                 "v_cmp_gt_f32_e64 %[m2], %[T], |v54|\n"                                            \
+                 LA3DM_TP_PUSH("v52", "%[m0]")                                                      \
+                 "s_cmp_lt_u32 %[np], 2\n"                                                          \
+                 "s_cbranch_scc1 .Lscan1_pad_%=\n"                                                  \
+                 LA3DM_TP_PUSH("v53", "%[m1]")                                                      \
+                 "s_cmp_lt_u32 %[np], 3\n"                                                          \
+                 "s_cbranch_scc1 .Lscan1_pad_%=\n"                                                  \
+                 LA3DM_TP_PUSH("v54", "%[m2]")                                                      \
+                 ".Lscan1_pad_%=:\n"                                                                \
+                 "s_mov_b64 exec, -1\n"                                                             \
+                 : [tail] "+s"(tailb), [tr] "=&v"(tr), [st] "=&s"(st), [m0] "=&s"(hm0), [m1] "=&s"(hm1), [m2] "=&s"(hm2) \
+                 : [ax] "v"(aX), [ay] "v"(aY), [az] "v"(aZ), [T] "s"(hit_t), [w] "v"(w0), [np] "s"(np) \
+                 : "scc", "memory", "v52", "v53", "v54", "v55", "v56", "v57", "v58", "v59", "v60", "v61", "v62", "v63")
 
 // A pointer argument read AGAIN from the kernarg segment, at the place that needs it (the statement is volatile: it stays
 // there).  alpha, beta, state and the stamp record are needed on the way out of a tile only; carried through the body they
@@ -83,12 +133,27 @@ __device__ __forceinline__ T *scan1_arg_again() {
 // BgkArgs as bgk_predict_fuse_t takes them, except: pts = the caller's UNSCALED points (x, y, z, label); blk_desc,
 // nbr_range and label_seq are not read.  Full blocks only (the host verifies it from the leaf count), tpb_shift 0 or more,
 // one descriptor per block (desc_shift is not read: the host takes this path at block_depth 3 only).
-template <int kTrig>
+//
+// kProd: the instance for the scan this kernel runs in production — what la3dm_bgk_scan_device has verified for the launch or
+// what la3dm_create fixed for the map is compiled in instead of carried in scalar registers and tested per tile, chunk,
+// sub-round or batch.  The host picks it when, beside the conditions of the one launch (block_depth 3, hence tpb_shift 0: a
+// tile is a block, task == blk, 64 leaves, leaf_off[blk] == 64 * blk; one workgroup per tile: gridDim.x == n_tasks), all of
+// these hold: kTrig 0, inv_ell != 0, sf2 == 1.0f, remap 2, no ablation switch, no extra LDS, a gated scan.  Same pairs, same
+// fp32 terms, same ring contents at every flush, hence the same order of a leaf's double additions: same bits.
+template <int kTrig, bool kProd = false>
 __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
+    static_assert(!kProd || kTrig == 0, "the production instance is the correctly rounded evaluation");
     __shared__ __attribute__((aligned(16))) unsigned char s_lds[5120];
-    const uint32_t task = bgk_task_of_workgroup(a);
-    if (task >= a.n_tasks) return;
-    const uint32_t blk = task >> a.tpb_shift;
+    uint32_t task;
+    if (kProd) {  // bgk_task_of_workgroup at remap 2; every workgroup of the grid has a tile
+        uint32_t wg = blockIdx.x;
+        if (wg < (gridDim.x & ~63u)) wg = (wg & ~63u) | ((wg & 7u) << 3) | ((wg >> 3) & 7u);
+        task = __builtin_amdgcn_readfirstlane(wg);
+    } else {
+        task = bgk_task_of_workgroup(a);
+        if (task >= a.n_tasks) return;
+    }
+    const uint32_t blk = kProd ? task : task >> a.tpb_shift;
     // the block's scalar inputs — leaf range, the 7 neighbour indices, centre — in one round trip.  The row of a block is
     // 7 words at a 4-byte-aligned address and the last block's row ends the array: 4 + 2 + 1 words, never word 7.
     typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -97,6 +162,17 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     u32x2 n45, lbr;
     uint32_t n6;
     float cx, cy, cz;
+    if (kProd)   // the block's leaves are [64 * blk, 64 * blk + 64): nothing to load, nothing to compare
+        asm("s_load_dwordx4 %[n03], %[nr], 0x0\n"
+            "s_load_dwordx2 %[n45], %[nr], 0x10\n"
+            "s_load_dword %[n6], %[nr], 0x18\n"
+            "s_load_dword %[cx], %[ctr], 0x0\n"
+            "s_load_dword %[cy], %[ctr], 0x4\n"
+            "s_load_dword %[cz], %[ctr], 0x8\n"
+            "s_waitcnt lgkmcnt(0)\n"
+            : [n03] "=&s"(n03), [n45] "=&s"(n45), [n6] "=&s"(n6), [cx] "=&s"(cx), [cy] "=&s"(cy), [cz] "=&s"(cz)
+            : [nr] "s"(a.nbr + 7 * (size_t)blk), [ctr] "s"(a.blk_center + 3 * (size_t)blk));
+    else
     asm("s_load_dwordx2 %[lb], %[lop], 0x0\n"
         "s_load_dwordx4 %[n03], %[nr], 0x0\n"
         "s_load_dwordx2 %[n45], %[nr], 0x10\n"
@@ -107,10 +183,11 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
         "s_waitcnt lgkmcnt(0)\n"
         : [lb] "=&s"(lbr), [n03] "=&s"(n03), [n45] "=&s"(n45), [n6] "=&s"(n6), [cx] "=&s"(cx), [cy] "=&s"(cy), [cz] "=&s"(cz)
         : [lop] "s"(a.leaf_off + blk), [nr] "s"(a.nbr + 7 * (size_t)blk), [ctr] "s"(a.blk_center + 3 * (size_t)blk));
-    const uint32_t lb0 = lbr[0];
-    if (lbr[1] - lb0 != 1u << (3u * (a.depth - 1u))) return;  // (the host vouched for full blocks: a tile that is not is left untouched)
+    const uint32_t lb0 = kProd ? blk << 6 : lbr[0];
+    if (!kProd && lbr[1] - lb0 != 1u << (3u * (a.depth - 1u))) return;  // (the host vouched for full blocks: a tile that is not is left untouched)
     // second round trip: train_off[tb], train_off[tb + 1] of every neighbour that exists (tb < 0: the block's leaf range is
-    // read instead — two words that are always there, train_off may hold a single one — and dropped), then bgk_prepare's
+    // read instead — two words that are always there, train_off may hold a single one — and dropped; the production instance
+    // keeps this stand-in although it no longer reads the range: leaf_off has n_test_blk + 1 words whatever n_train_blk is), then bgk_prepare's
     // thirteen words at shift 0 in scalar registers: adj[b] = first point of neighbour b minus the flat index where b starts, pend[b] = flat index where b ends, M = pend[6]
     uint32_t adj[7], pend[7];
     {
@@ -139,12 +216,14 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     const uint32_t M = pend[6];
     WaveLdsT &L = *reinterpret_cast<WaveLdsT *>(s_lds);
     const uint32_t lane = threadIdx.x;
-    const uint32_t tile = task & ((1u << a.tpb_shift) - 1u);
+    const uint32_t tile = kProd ? 0u : task & ((1u << a.tpb_shift) - 1u);
     const uint32_t li = lb0 + tile * kWave + lane;
     // LeafIterator order is descending: the leaf at list position j of a full block has the finest-level index
     // 8^(depth-1) - 1 - j, so the key needs no load
-    const uint32_t n_fine = 1u << (3u * (a.depth - 1u));
-    const uint32_t lut_idx = lut_layer_base(a.depth - 1u) + (n_fine - 1u - tile * kWave) - lane;
+    const uint32_t n_fine = kProd ? 64u : 1u << (3u * (a.depth - 1u));
+    const uint32_t lut_idx = (kProd ? lut_layer_base(2u) : lut_layer_base(a.depth - 1u)) + (n_fine - 1u - tile * kWave) - lane;
+    // x / ell: the production instance runs only where inv_ell != 0, div_by_ell without its branch
+    auto by_ell = [&](float x) { return kProd ? div_const(x, a.ell, a.inv_ell) : div_by_ell(x, a.ell, a.inv_ell); };
 
     // the UNSCALED points of flat indices cb + lane (chunk() divides them by ell); a lane past the end reads the range's
     // last point (the caller masks it).  The descriptor stays in scalar registers for the whole tile; its offsets are
@@ -182,7 +261,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
 #endif
     if (M == 0u) {  // no training point in the 7 blocks: nothing reaches the tile
         uint8_t *const state = scan1_arg_again<uint8_t, offsetof(BgkArgs, state)>();
-        if (!(a.flags & 1u)) state[li] = 0;
+        if (kProd || !(a.flags & 1u)) state[li] = 0;
         else {  // insert_training_data: update() runs with (0, 0)
 #if LA3DM_T_EARLY_AB
             const float A = A0, B = B0;
@@ -197,8 +276,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     if (M > (uint32_t)kWave) pn = gather(kWave);
 
     const float4 off4 = a.lut[lut_idx];
-    const float xs0 = div_by_ell(off4.x + cx, a.ell, a.inv_ell), ys0 = div_by_ell(off4.y + cy, a.ell, a.inv_ell),
-                zs0 = div_by_ell(off4.z + cz, a.ell, a.inv_ell);
+    const float xs0 = by_ell(off4.x + cx), ys0 = by_ell(off4.y + cy), zs0 = by_ell(off4.z + cz);
     L.acc0[lane] = 0.0;
     L.acc1[lane] = 0.0;
 
@@ -226,7 +304,8 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     // C: lane evaluates ring entry i and adds k to the leaf's accumulator 0 or 1 (the sign of d2 is the label)
     auto c_eval = [&](uint32_t i) {
         const uint2 e = L.ring[i];
-        const float kv = scan1_cov<kTrig>(sqrt_cr(__builtin_fabsf(__uint_as_float(e.x))), a.sf2);
+        const float r = sqrt_cr(__builtin_fabsf(__uint_as_float(e.x)));
+        const float kv = kProd ? scan1_cov_unit(r) : scan1_cov<kTrig>(r, a.sf2);
         const double kd = (double)kv;
         const uint32_t ad = e.y | ((e.x >> 22) & 0x200u);  // label 1 (negative d2): acc1[leaf], 512 bytes up
         asm volatile("ds_add_f64 %0, %1\n" : : "v"(ad), "v"(kd) : "memory");
@@ -237,7 +316,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
         __builtin_amdgcn_wave_barrier();
         const uint32_t tail = (tailb - ring_base) >> 3;
         const uint32_t rem = tail & 63u;
-        if (!(a.flags & 0x100u))  // 0x100: profiling ablation
+        if (kProd || !(a.flags & 0x100u))  // 0x100: profiling ablation
             for (uint32_t p = rem; p < tail; p += kWave) c_eval(p + lane);
         tailb = ring_base + 8u * rem;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -249,7 +328,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     auto chunk = [&](const float4 &pu, const uint32_t cb) {
         // x / ell, y / ell, z / ell as bgk_prepare's IEEE divisions leave them (div_by_ell is the correctly rounded quotient;
         // a zero may come out with the other sign, which the squares below remove); the label is untouched
-        const float px = div_by_ell(pu.x, a.ell, a.inv_ell), py = div_by_ell(pu.y, a.ell, a.inv_ell), pz = div_by_ell(pu.z, a.ell, a.inv_ell);
+        const float px = by_ell(pu.x), py = by_ell(pu.y), pz = by_ell(pu.z);
         const la3dm_v2f bx = {px, px}, by = {py, py}, bz = {pz, pz};
         la3dm_v2f x01 = bx - X01, x23 = bx - X23, y01 = by - Y01, y23 = by - Y23, z01 = bz - Z01, z23 = bz - Z23;
         x01 *= x01, x23 *= x23, y01 *= y01, y23 *= y23, z01 *= z01, z23 *= z23;
@@ -275,8 +354,9 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
         const uint32_t n = (uint32_t)__popcll(m);
         for (uint32_t base = 0; base < n; base += kTabSlots) {
             const uint32_t nr = min(n - base, (uint32_t)kTabSlots), ngroup = (nr + 3u) >> 2;
-            // pad the last column group with entries no leaf can reach (an X row suffices: the sum stays huge or NaN)
-            if (lane < 4u && nr + lane < 4u * ngroup) {
+            // pad the last column group with entries no leaf can reach (an X row suffices: the sum stays huge or NaN); the
+            // production instance pushes nothing from those slots (LA3DM_SCAN1_PAD_TRIP) and leaves them as they are
+            if (!kProd && lane < 4u && nr + lane < 4u * ngroup) {
                 float big;
                 asm volatile("v_mov_b32 %0, 0x5e268890" : "=v"(big));
 #pragma unroll
@@ -292,7 +372,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
-            if (a.flags & 0x200u) continue;  // 0x200: profiling ablation
+            if (!kProd && (a.flags & 0x200u)) continue;  // 0x200: profiling ablation
             // one trip per column group, the group's place in the table as the immediate offset of its three reads (groups
             // 0-3 sit in the first half, 4-7 kHalfB = 768 bytes up in the second): the lane's three row addresses never move.
             // The ring is tested after every trip, as before: a trip pushes up to 4 x 64 entries, which is the head room
@@ -301,6 +381,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
             // trips' scalar outputs meet); a copy that is not entered costs the branch round it, as the loop's two did.
             const uint32_t aX = ax0, aY = ay0, aZ = az0;
             static_assert(kHalfB == 768u, "the immediates below");
+            if (!kProd) {
 #define LA3DM_SCAN1_GROUP(G, OFF)                   \
     if (G < ngroup) {                               \
         uint32_t st;                                \
@@ -319,6 +400,46 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
             LA3DM_SCAN1_GROUP(7u, "816")
             }}}}}}}}
 #undef LA3DM_SCAN1_GROUP
+            } else {
+                // production: the same trips for the nr / 4 full groups; then, where nr is no multiple of four, the last group
+                // through the trip that pushes its nr % 4 candidates only, and the ring test that follows every trip (after a
+                // full group it has just been made: it fails again, or the ring was drained).  Nested as above; a group that
+                // is not full is the last of its sub-round, so each level ends in it or in nothing.
+                const uint32_t nfull = nr >> 2, np = nr & 3u;
+#define LA3DM_SCAN1_GROUP(G, OFF)                   \
+    if (G < nfull) {                                \
+        uint32_t st;                                \
+        float tr;                                   \
+        unsigned long long hm0, hm1, hm2, hm3;      \
+        LA3DM_TP_TRIP(OFF);                         \
+        if (tailb > tail_cap) c_flush();
+#define LA3DM_SCAN1_LAST(OFF)                       \
+    } else if (np != 0u) {                          \
+        uint32_t st;                                \
+        float tr;                                   \
+        unsigned long long hm0, hm1, hm2;           \
+        LA3DM_SCAN1_PAD_TRIP(OFF);                  \
+    }
+                LA3DM_SCAN1_GROUP(0u, "0")
+                LA3DM_SCAN1_GROUP(1u, "16")
+                LA3DM_SCAN1_GROUP(2u, "32")
+                LA3DM_SCAN1_GROUP(3u, "48")
+                LA3DM_SCAN1_GROUP(4u, "768")
+                LA3DM_SCAN1_GROUP(5u, "784")
+                LA3DM_SCAN1_GROUP(6u, "800")
+                LA3DM_SCAN1_GROUP(7u, "816")
+                LA3DM_SCAN1_LAST("816")   // (G == nfull: the group after the full ones, at its own place in the table)
+                LA3DM_SCAN1_LAST("800")
+                LA3DM_SCAN1_LAST("784")
+                LA3DM_SCAN1_LAST("768")
+                LA3DM_SCAN1_LAST("48")
+                LA3DM_SCAN1_LAST("32")
+                LA3DM_SCAN1_LAST("16")
+                LA3DM_SCAN1_LAST("0")
+#undef LA3DM_SCAN1_GROUP
+#undef LA3DM_SCAN1_LAST
+                if (tailb > tail_cap) c_flush();
+            }
             // (the next sub-round overwrites the table: LDS operations of a wave complete in order)
         }
     };
@@ -336,7 +457,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
     __builtin_amdgcn_wave_barrier();
     {
         const uint32_t tail = (tailb - ring_base) >> 3;
-        if (!(a.flags & 0x100u))
+        if (kProd || !(a.flags & 0x100u))
             for (uint32_t p = 0; p < tail; p += kWave)
                 if (p + lane < tail) c_eval(p + lane);
     }
@@ -351,7 +472,7 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
         asm volatile("" : "+v"(lw));
         float *const alpha = scan1_arg_again<float, offsetof(BgkArgs, alpha)>(), *const beta = scan1_arg_again<float, offsetof(BgkArgs, beta)>();
         uint8_t *const state = scan1_arg_again<uint8_t, offsetof(BgkArgs, state)>();
-        if (K > 0.0 || (a.flags & 1u) != 0u) {  // flag 1: insert_training_data, update() runs unconditionally
+        if (K > 0.0 || (!kProd && (a.flags & 1u) != 0u)) {  // flag 1: insert_training_data, update() runs unconditionally
 #if LA3DM_T_EARLY_AB
             const float A = (float)((double)A0 + Y);
             const float B = (float)((double)B0 + (K - Y));
@@ -369,9 +490,9 @@ __device__ __forceinline__ void bgk_scan1_tile(BgkArgs a) {
 }
 
 // the untimed launch: the tile body and nothing else
-template <int kTrig>
+template <int kTrig, bool kProd = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) void bgk_predict_fuse_t1(BgkArgs a) {
-    bgk_scan1_tile<kTrig>(a);
+    bgk_scan1_tile<kTrig, kProd>(a);
 }
 
 // One record of stamps per launch, all zero before the launch (la3dm_ctx.h: the stamp pool): kStampSlots entry stamps of
@@ -388,11 +509,11 @@ constexpr uint32_t kStampRecordBytes = 8u * (kStampSlots + kStampSlots * kStampE
 // 40 000 waves was 40 us longer and the 20 000-ray scan took 101 us instead of 36; a line per slot costs nothing that can be
 // measured (profiles/kernel_stamps/README.md).  The clock reads and the entry stores are free.  The stamps leave through
 // `stamps` only; nothing the scan computes depends on them.
-template <int kTrig>
+template <int kTrig, bool kProd = false>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(8, 8))) void bgk_predict_fuse_t1s(BgkArgs a, unsigned long long *stamps) {
     const unsigned long long t_in = wall_clock64();
     if (blockIdx.x < kStampSlots && threadIdx.x == 0) stamps[blockIdx.x] = t_in;
-    bgk_scan1_tile<kTrig>(a);
+    bgk_scan1_tile<kTrig, kProd>(a);
     const unsigned long long t_out = wall_clock64();
     uint32_t lane = threadIdx.x;
     asm volatile("" : "+v"(lane));  // (compared again here: the entry's comparison is not kept in registers across the body)

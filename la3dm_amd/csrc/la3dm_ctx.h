@@ -29,6 +29,9 @@ struct la3dm_ctx {
                              // other tiles through the general path in the same launch), 0 = bgk_predict_fuse_r for every tile
     int opt_bgk_one_launch = 1;  // bgk_sum = 1, tables, block_depth 3, a scan of full blocks only: 1 (default) = one launch, bgk_predict_fuse_t1 on the caller's
                                  // unscaled points (bgk_scan1_kernels.h), 0 = bgk_prepare + bgk_predict_fuse_t<.., false>; env LA3DM_BGK_ONE_LAUNCH sets the default
+    int opt_bgk_scan1_generic = 0;  // the one launch: 0 (default) = the production instance of the kernel (bgk_scan1_tile<0, true>) where la3dm_bgk_scan_device finds its
+                                    // conditions, 1 = the generic instance always (A/B, tests); env LA3DM_BGK_SCAN1_GENERIC sets the default
+    int last_scan1_instance = 0;    // what the last la3dm_bgk_scan_device call launched: 0 not the one launch, 1 its generic instance, 2 its production instance (la3dm_get_option "bgk_scan1_instance")
     float inv_ell = 0.0f;   // RN(1 / ell), or 0 when x / ell must stay an IEEE division (bgk_kernels.h div_by_ell)
     int opt_fast_trig = 0;  // 0 correctly rounded (f64 kernels), 1 f32 polynomial, 2 OCML, 3 Eigen 3.3.7 psin / pcos without FMA (the likely reference build)
     int opt_gp_mode = 0;    // GPOctoMap: 0 = FMA chains in ascending order (VALU and matrix cores alike: the parity configuration), 1 = the order of an

@@ -309,6 +309,9 @@ int la3dm_create(const la3dm_params *params, la3dm_ctx **out) {
     if (const char *ev = getenv("LA3DM_BGK_ONE_LAUNCH")) {  // full-block table scans at block_depth 3: 0 = bgk_prepare + bgk_predict_fuse_t
         if (ev[0] == '0' || ev[0] == '1') ctx->opt_bgk_one_launch = ev[0] - '0';
     }
+    if (const char *ev = getenv("LA3DM_BGK_SCAN1_GENERIC")) {  // the one launch: 1 = never the production instance of the kernel
+        if (ev[0] == '0' || ev[0] == '1') ctx->opt_bgk_scan1_generic = ev[0] - '0';
+    }
     if (const char *ev = getenv("LA3DM_BGKL_SPLIT_ROWS")) {   // default of "bgkl_split_rows": an integer (< 0: never split); anything else is ignored
         char *end = nullptr;
         const long v = strtol(ev, &end, 10);
@@ -385,6 +388,11 @@ int la3dm_set_option(la3dm_ctx *ctx, const char *name, int value) {
         ctx->opt_bgk_one_launch = value;
         return LA3DM_OK;
     }
+    if (!strcmp(name, "bgk_scan1_generic")) {  // the one launch: 0 = the production instance of bgk_predict_fuse_t1 where its conditions hold (la3dm_bgk_scan_device), 1 = the generic instance always
+        if (value < 0 || value > 1) return bad_value("0 or 1");
+        ctx->opt_bgk_scan1_generic = value;
+        return LA3DM_OK;
+    }
     if (!strcmp(name, "fast_trig")) {  // 0 correctly rounded (default, the parity configuration), 1 f32 polynomial, 2 OCML, 3 = Eigen 3.3.7's psin / pcos
         // without FMA, the likely reference build (BGK, BGK-L and BGK-LV kernels; 1 and 2: the BGK kernels only)
         if (value < 0 || value > 3) return bad_value("0, 1, 2 or 3");
@@ -454,6 +462,8 @@ int la3dm_get_option(const la3dm_ctx *ctx, const char *name, int *value) {
     if (!strcmp(name, "bgk_sum")) *value = ctx->opt_bgk_sum;
     else if (!strcmp(name, "bgk_tables")) *value = ctx->opt_bgk_tables;
     else if (!strcmp(name, "bgk_one_launch")) *value = ctx->opt_bgk_one_launch;
+    else if (!strcmp(name, "bgk_scan1_generic")) *value = ctx->opt_bgk_scan1_generic;
+    else if (!strcmp(name, "bgk_scan1_instance")) *value = ctx->last_scan1_instance;  // read-only: what the last la3dm_bgk_scan_device call launched
     else if (!strcmp(name, "fast_trig")) *value = ctx->opt_fast_trig;
     else if (!strcmp(name, "gp_mode")) *value = ctx->opt_gp_mode;
     else if (!strcmp(name, "grid_order")) *value = ctx->opt_grid_order;
@@ -498,6 +508,13 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     // full-block table scans at block_depth 3 (the first scan into an empty map): ONE launch — bgk_predict_fuse_t1 scales the
     // caller's points and resolves the neighbour ranges itself (bgk_scan1_kernels.h); option "bgk_one_launch" 0 = the two launches below
     const bool one_launch = use_tables && full_blocks && ctx->p.block_depth == 3 && ctx->opt_bgk_one_launch == 1;
+    // the instance of that kernel with the scan it always runs compiled in (bgk_scan1_tile<0, true>): the correctly rounded
+    // evaluation, x / ell by the reciprocal, sf2 exactly 1, the default remap, no profiling switch (ablation, extra LDS), a gated
+    // scan; anything else, or option "bgk_scan1_generic" 1, takes the generic instance.  Same bits either way.
+    static_assert(LA3DM_SCAN_UPDATE_UNGATED == 1u, "flag 1 of BgkArgs::flags");
+    const bool production = one_launch && ctx->opt_fast_trig == 0 && ctx->inv_ell != 0.0f && ctx->p.sf2 == 1.0f && ctx->opt_remap == 2 &&
+                            ctx->opt_ablate == 0 && ctx->opt_lds_pad == 0 && !(s->flags & LA3DM_SCAN_UPDATE_UNGATED) && ctx->opt_bgk_scan1_generic == 0;
+    ctx->last_scan1_instance = production ? 2 : one_launch ? 1 : 0;
 
     // 1. x / ell once per training point
     if (!one_launch) {
@@ -605,7 +622,11 @@ int la3dm_bgk_scan_device(la3dm_ctx *ctx, const la3dm_bgk_scan *s, void *stream_
     if (sum_f64) {
         grid = dim3(a.n_tasks);
         block = dim3(kWave);
-        if (stamps) {
+        if (stamps && production) {   // (one workgroup per tile: the production instance does not compare its tile with n_tasks)
+            hipLaunchKernelGGL((bgk_predict_fuse_t1s<0, true>), grid, block, 0, stream, a, stamps);
+        } else if (production) {
+            LAUNCH_BGK_AS((bgk_predict_fuse_t1<0, true>))
+        } else if (stamps) {
             switch (ctx->opt_fast_trig) {
             case 1: hipLaunchKernelGGL(bgk_predict_fuse_t1s<1>, grid, block, (size_t)ctx->opt_lds_pad, stream, a, stamps); break;
             case 2: hipLaunchKernelGGL(bgk_predict_fuse_t1s<2>, grid, block, (size_t)ctx->opt_lds_pad, stream, a, stamps); break;
